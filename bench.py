@@ -125,6 +125,26 @@ def bits_of(t):
     return np.ascontiguousarray(a).view(np.uint64)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, api, blocks, P):
+    """The orientation bitsets of one pass as DIR/amplify_fr.npy and DIR/amplify_rf.npy: float32 [P, targets], 1.0 where the
+    pair amplifies the target.  `blocks` = [(u64 [2, P, words], targets), ...] in target order.  Above DUMP_MAX_BYTES a fixed,
+    seeded sample of target columns is written, its global indices in DIR/target_index.npy (float64)."""
+    fr = np.concatenate([np.stack([api.bits_to_bool(w[0, p], n) for p in range(P)]) for w, n in blocks], axis=1)
+    rf = np.concatenate([np.stack([api.bits_to_bool(w[1, p], n) for p in range(P)]) for w, n in blocks], axis=1)
+    T = fr.shape[1]
+    idx = np.arange(T)
+    if 2 * P * T * 4 > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - T * 8) // (2 * P * 4 + 8)
+        idx = np.sort(np.random.RandomState(12345).choice(T, size=keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "amplify_fr.npy"), fr[:, idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "amplify_rf.npy"), rf[:, idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "target_index.npy"), idx.astype(np.float64))
+
+
 def assemble_gathered(gathered0, ranges):
     """The all-gathered [world, 2, P, wmax] words of one pass -> [2, P, total words] of the global set: rank r owns
     ceil((hi_r - lo_r) / 64) words and its block starts at a multiple of 64, so the words concatenate."""
@@ -529,7 +549,11 @@ def main():
                     help="pcr_select_words + pcr_amplify_device per step (host wait between them) instead of pcr_screen_device")
     ap.add_argument("--target-threshold", type=float, default=1.0, help="--target.threshold of the reference (pcramp.h:39 default 1.0)")
     ap.add_argument("--search-multiplier", type=float, default=0.9, help="target search multiplier of the reference (pcramp.h:51 default 0.9)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the orientation bitsets of the last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -736,16 +760,8 @@ def main():
             d = float(tt.item())
         return d
 
-    # A short block (the driver's --steps 20 is 1.5 ms) is a noisy sample and mostly warm-up (three rotating handles, the lean
-    # pass starts with a handle's second pass): the block of `steps` steps is repeated until MIN_TIMED_S have been timed and the
-    # MEDIAN block is reported.  Every block is bracketed as the contract says; the count is derived from the first block's
-    # max-over-ranks time, so all ranks run the same number.
-    MIN_TIMED_S, MAX_BLOCKS = 0.3, 400
-    block_dts = [timed_block()]
-    n_blocks = int(min(MAX_BLOCKS, max(1, np.ceil(MIN_TIMED_S / max(block_dts[0], 1e-6)))))
-    for _ in range(n_blocks - 1):
-        block_dts.append(timed_block())
-    dt = float(np.median(block_dts))
+    # ONE block of exactly `steps` timed steps: ms_per_step = its time / steps
+    dt = timed_block()
     scan_ms = scan_launches = 0
     for s in scrs:
         a, b = s.profile_read(reset=True)
@@ -753,8 +769,15 @@ def main():
         scan_launches += b
         s.profile(False)
 
-    last = bits_of(local[0][0])              # the first pass of the first batch buffer
+    # where the last timed step left its bitsets (step_no restarted at 0 for the timed block)
+    last_k = (args.steps - 1) % K
+    last_b = ((args.steps - 1) // K) % NBUF
+    last = bits_of(local[last_b][last_k])
     n_set = int(np.unpackbits((last[0] | last[1]).view(np.uint8)).sum())
+    if args.dump_outputs and rank == 0:
+        # every rank's block of the last step (gathered) or this rank's own: [P, targets] per orientation
+        blocks = [(bits_of(gathered[last_b][r, last_k]), b1 - a1) for r, (a1, b1) in enumerate(ranges)] if use_dist else [(last, T_local)]
+        dump_outputs(args.dump_outputs, api, blocks, P)
     # per-GPU work fixed (weak): every rank screens its block of every pass; strong: the blocks add up to the fixed set
     evals_total = float(P) * T_total * args.steps
     value = evals_total / dt
@@ -833,9 +856,8 @@ def main():
                        "exchange": ((("pcr_exchange_bits (ncclAllGather behind the C-ABI, on the handle's stream)" if comm is not None else "all_gather_into_tensor, pipelined")
                                      + " of [%d passes, 2, P, words] u64 per rank; handles drained before each gather" % K) if use_dist else "none"),
                        "sharded_equals_unsharded": verify,
-                       "timed_region_s": dt, "timed_blocks": len(block_dts), "timed_total_s": float(sum(block_dts)),
-                       "block_ms_min_median_max": [min(block_dts) * 1e3, dt * 1e3, max(block_dts) * 1e3],
-                       "timing": "median over the timed blocks of `steps` steps each (a block is repeated until %.1f s have been timed)" % MIN_TIMED_S,
+                       "timed_region_s": dt,
+                       "timing": "one block of exactly `steps` steps between barrier + synchronize on both sides",
                        "staging": scrs[0].staging_mode() + (" (fused pass without a staging launch from a handle's second consecutive pass on)" if scrs[0].staging_mode() == "lean" else ""),
                        "amplification_calls_set_rank0": n_set},
             "roofline": {"bound": bound,

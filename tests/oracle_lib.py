@@ -7,6 +7,7 @@
 Both expose the same Python surface so the tests can run one against the other.
 """
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -53,6 +54,16 @@ def build_reference():
 
 def _w(x):
     return U64x2(int(x[0]), int(x[1]))
+
+
+def _taped(fn):
+    """A helper taking a checker as its first argument: a reference_tape proxy records / replays the whole call."""
+    @functools.wraps(fn)
+    def wrapper(lib, *args, **kwargs):
+        if hasattr(lib, "_tape_call"):
+            return lib._tape_call(None, fn.__name__, args, kwargs, helper=fn)
+        return fn(lib, *args, **kwargs)
+    return wrapper
 
 
 class _Lib:
@@ -291,6 +302,7 @@ DEFAULT_MOVE_OPTIONS = dict(degen=1, primer_min=18, primer_max=25, salt=0.05, pr
                             bg_amp_max=2000)
 
 
+@_taped
 def optimization_move(lib, target_session, background_session, pair, move, side, **mo):
     """One complete local-search move (optimize_pcr.cpp) -> ((w0, w1), (tc, bc, overlap), (base tc, base bc))."""
     o = dict(DEFAULT_MOVE_OPTIONS)
@@ -310,6 +322,7 @@ def optimization_move(lib, target_session, background_session, pair, move, side,
     return (int(w[0]), int(w[1])), tuple(float(x) for x in sc), tuple(float(x) for x in base)
 
 
+@_taped
 def optimize(lib, target_session, background_session, pair, moves=(0, 1, 2, 4, 3, 5), **mo):
     """optimize() (optimize.cpp:14-207), non-multiplex; moves in main.cpp:82-95 order by default
     -> (best pair, (tc, bc, overlap))."""
@@ -330,6 +343,7 @@ def optimize(lib, target_session, background_session, pair, moves=(0, 1, 2, 4, 3
     return ((int(flat[0]), int(flat[1])), (int(flat[2]), int(flat[3]))), tuple(float(x) for x in sc)
 
 
+@_taped
 def make_degenerate(lib, target_session, pair, max_dimer=40.0, **mo):
     """make_degenerate (optimize.cpp:356-398 -> PCR::maximize_degeneracy) -> (assay, valid)."""
     o = dict(DEFAULT_MOVE_OPTIONS)
@@ -346,6 +360,7 @@ def make_degenerate(lib, target_session, pair, max_dimer=40.0, **mo):
     return ((int(flat[0]), int(flat[1])), (int(flat[2]), int(flat[3]))), bool(ok.value)
 
 
+@_taped
 def optimization_move_multiplex(lib, target_session, background_session, amplicon_session, pool, pair, move, side, **mo):
     """One local-search move with opt.use_multiplex -> ((w0, w1), (tc, bc, overlap), base (tc, bc, overlap))."""
     o = dict(DEFAULT_MOVE_OPTIONS)
@@ -367,6 +382,7 @@ def optimization_move_multiplex(lib, target_session, background_session, amplico
     return (int(w[0]), int(w[1])), tuple(float(x) for x in sc), tuple(float(x) for x in base)
 
 
+@_taped
 def optimize_multiplex(lib, target_session, background_session, amplicon_session, pool, pair, moves=(0, 1, 2, 4, 3, 5), **mo):
     """optimize() with opt.use_multiplex: multiplex background = pack of amplicon_session's sequences, pool = assays
     designed so far -> (best pair, (tc, bc incl. the multiplex term, oligo_overlap))."""
@@ -398,6 +414,7 @@ DEFAULT_SAMPLER_OPTIONS = dict(primer_min=18, primer_max=25, amp_min=80, amp_max
                                primer_strand=9.0e-7, tm_min=50.0, tm_max=70.0, max_hairpin=40.0, max_dimer=40.0)
 
 
+@_taped
 def rand_r(lib, seed):
     """glibc rand_r -> (value, next seed)."""
     s = C.c_uint(seed)
@@ -407,6 +424,7 @@ def rand_r(lib, seed):
     return fn(C.byref(s)), s.value
 
 
+@_taped
 def random_assays(lib, session, seed, n_trials, **so):
     """PCR::random_assay x n_trials on one running seed (main.cpp:544-550 at one thread)
     -> ([(F, R)], seed afterwards)."""

@@ -1,6 +1,7 @@
-"""Pins the CPU restatement (oracle/pcr_oracle.cpp) against the REAL reference, compiled from
-/root/reference by oracle/Makefile behind oracle/ref_harness.cpp.  Runs only where that build
-exists (this container); the committed goldens in tests/golden/ carry the same pins to the GPU box.
+"""Pins the CPU restatement (oracle/pcr_oracle.cpp) against the REAL reference, compiled by oracle/Makefile
+behind oracle/ref_harness.cpp where the reference sources are present.  Everywhere else the `reference`
+fixture replays the answers the compiled reference gave these same calls (tests/reference_tape.py,
+tests/golden/reference_calls.json.gz).
 """
 import random
 
