@@ -212,6 +212,33 @@ int pcr_exchange_bits(pcr_ctx *ctx, pcr_comm *comm, const uint64_t *d_local, uin
 void pcr_comm_destroy(pcr_comm *comm);
 const char *pcr_comm_library(void);      /* which librccl was bound ("" before the first use / when none was found) */
 
+/* A host-collective communicator: every exchange goes through fn, an all-gather the caller provides -- `bytes` from `send` on
+ * every rank into `recv`, world x bytes in rank order, host memory; 0 = ok.  It is how an MPI program binds the library
+ * (MPI_Allgather), and how two ranks share one GPU (RCCL refuses that).  pcr_exchange_bits on it copies
+ * device -> host, calls fn and copies host -> device; pcr_comm_world / _rank / _destroy take both kinds. */
+typedef int (*pcr_host_allgather_fn)(const void *send, uint64_t bytes, void *recv, void *user);
+pcr_comm *pcr_comm_init_host(pcr_ctx *ctx, int world, int rank, pcr_host_allgather_fn fn, void *user);
+
+/* ---- the local search over targets sharded across ranks (pcr_shard.inc)
+ * pcr_shard_targets: the loaded PCR_SET_TARGET holds rows [first_seq, first_seq + n) of n_total targets spread over comm, in
+ * rank order (boundaries at any index).  Collective: one all-gather checks that the ranges are contiguous in rank order and
+ * cover n_total (else PCR_ERR_ARG on every rank) and picks the combine.  comm = NULL detaches (not collective); reloading the
+ * target set detaches too; the communicator must outlive the attachment.  With a shard attached:
+ *   pcr_optimize_batch / pcr_optimization_move  combine every trial word's target coverage over the ranks, bit-exact with the
+ *       reference's compute_coverage (pcr_assay.cpp:271-302: weights summed in double, ascending global sequence index, the
+ *       F(+)/R(-) bits first, then the R(+)/F(-) bits not yet counted, cast to float).  Backgrounds and the multiplex set are
+ *       whole on every rank and not combined.  All ranks must call with the same batch (checked: PCR_ERR_ARG on every rank).
+ *   pcr_make_degenerate  gathers every rank's candidate amplicons and merges them into the reference's order (order_amplicons:
+ *       by pair, orientation, global sequence, plus site, minus site) before the unchanged walk.
+ *   pcr_design  returns PCR_ERR_STATE.
+ * A failure on one rank (incl. the has_split range error) is returned by every rank; no rank leaves a collective out.
+ * pcr_shard_combine_mode: 0 = not sharded, 1 = exact partials (every partial sum is exactly representable in double, so one
+ * all-gather of per-rank sums per iteration is exact), 2 = ordered chain (the reference's sequential sum, rank after rank, 2 x world
+ * all-gathers per iteration).  PCRAMP_SHARD_COMBINE=auto|exact|chain, read at attach time: auto and exact take 1 where it is
+ * provably exact, else 2. */
+int pcr_shard_targets(pcr_ctx *ctx, pcr_comm *comm, uint64_t first_seq, uint64_t n_total);
+int pcr_shard_combine_mode(pcr_ctx *ctx);
+
 
 /* ---- Smith-Waterman primer x template alignment (rows a7/a8 of the scope table) */
 

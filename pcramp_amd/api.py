@@ -117,9 +117,13 @@ ABI_SYMBOLS = [
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode",
-    "pcr_design", "pcr_design_output",
+    "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
     "pcr_comm_unique_id", "pcr_comm_init_rank", "pcr_comm_world", "pcr_comm_rank", "pcr_exchange_bits", "pcr_comm_destroy", "pcr_comm_library",
 ]
+
+
+# pcr_host_allgather_fn: (send, bytes, recv, user) -> 0 on success
+HOST_ALLGATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p)
 
 
 def load_library():
@@ -176,6 +180,10 @@ def load_library():
     L.pcr_comm_destroy.argtypes = [C.c_void_p]
     L.pcr_comm_destroy.restype = None
     L.pcr_comm_library.restype = C.c_char_p
+    L.pcr_comm_init_host.restype = C.c_void_p
+    L.pcr_comm_init_host.argtypes = [C.c_void_p, C.c_int, C.c_int, HOST_ALLGATHER, C.c_void_p]
+    L.pcr_shard_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]
+    L.pcr_shard_combine_mode.argtypes = [C.c_void_p]
     L.pcr_sw_align_words.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.pcr_background_match.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(BackgroundArgs), C.c_void_p]
     L.pcr_multiplex_match.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_void_p]
@@ -762,8 +770,40 @@ class Screener:
         """ncclAllGather of words_per_rank u64 per rank into d_full [world, words_per_rank] (device pointers), in stream order."""
         self._check(self.L.pcr_exchange_bits(self.h, comm, int(d_local_ptr), int(words_per_rank), int(d_full_ptr)))
 
+    def comm_init_host(self, world, rank, allgather):
+        """A host-collective communicator (pcr_comm_init_host): allgather(send: bytes) -> bytes of world x len(send), in rank
+        order (e.g. pcramp_amd.shard.gloo_allgather()).  The callback stays referenced by this Screener until comm_destroy."""
+        def cb(send, nbytes, recv, _user):
+            try:
+                data = C.string_at(send, nbytes) if nbytes else b""
+                out = allgather(data)
+                if len(out) != int(world) * nbytes:
+                    return 1
+                if out:
+                    C.memmove(recv, bytes(out), len(out))
+                return 0
+            except Exception:                                       # an exception must not cross the C frames
+                return 1
+        fn = HOST_ALLGATHER(cb)
+        h = self.L.pcr_comm_init_host(self.h, int(world), int(rank), fn, None)
+        if not h:
+            raise PcrError(_err(self.L))
+        if not hasattr(self, "_host_comms"):
+            self._host_comms = {}
+        self._host_comms[h] = fn
+        return h
+
     def comm_destroy(self, comm):
         self.L.pcr_comm_destroy(comm)
+        getattr(self, "_host_comms", {}).pop(comm, None)
+
+    def shard_targets(self, comm, first, n_total):
+        """Collective: the loaded targets are rows [first, first + n) of n_total spread over comm (None detaches)."""
+        self._check(self.L.pcr_shard_targets(self.h, comm, int(first), int(n_total)))
+
+    def shard_combine_mode(self):
+        """0 = not sharded, 1 = exact partials, 2 = ordered chain (include/pcramp_hip.h)."""
+        return int(self.L.pcr_shard_combine_mode(self.h))
 
     def staging_mode(self):
         """'lean' (the CPU stores the per-pass tables straight into device memory, no staging launch) or 'k_stage'."""

@@ -63,46 +63,104 @@ inline Planes planes_union(const Planes &w, const Planes &key)
 
 struct DegAmp { Planes fkey, rkey; float score; };
 
+// one candidate amplicon with its sort key and site words, as the ranks of a sharded call exchange them
+struct ShardAmp { uint32_t pair, orient; uint64_t seq; /* global sequence index */ uint4 f, r; };
+static_assert(sizeof(ShardAmp) == 48, "exchanged as raw bytes");
+
+// The candidate amplicons of every assay on this handle's targets, in the reference's order (candidate_amplicons +
+// order_amplicons: by pair, orientation, sequence, plus site, minus site), with the words of their sites; seq_base is added to
+// the sequence indices (the shard's first row).
+int degenerate_amplicons(pcr_ctx *ctx, SeqSet &S, const pcr_pair *assays, uint32_t n, const pcr_optimize_args *o, uint64_t seq_base, std::vector<ShardAmp> &out)
+{
+	out.clear();
+	if(!S.have_db){ g_err = "pcr_make_degenerate: no word DB (call pcr_select_words on the targets first)"; return PCR_ERR_STATE; }
+	int rc;
+	if((rc = ensure_touched(ctx, S)) != PCR_OK) return rc;
+	if(!S.n_entries) return PCR_OK;
+	uint32_t n_amp = 0;
+	if((rc = candidate_amplicons(ctx, S, assays, n, o->target.collect_threshold, o->target.amp_min, o->target.amp_max, &n_amp)) != PCR_OK) return rc;
+	if(!n_amp) return PCR_OK;
+	const AmpRec *d_recs = nullptr; const uint32_t *d_pair_start = nullptr;
+	if((rc = order_amplicons(ctx, S, n_amp, n, &d_recs, &d_pair_start)) != PCR_OK) return rc;
+	DevBuf<uint4> d_words;
+	if((rc = d_words.ensure(2*(size_t)n_amp)) != PCR_OK) return rc;
+	hipLaunchKernelGGL(k_amp_words, dim3((n_amp + 255)/256), dim3(256), 0, ctx->stream, d_recs, n_amp, S.db.p, d_words.p);
+	std::vector<AmpRec> recs(n_amp); std::vector<uint4> words(2*(size_t)n_amp);
+	hipError_t e = hipGetLastError();
+	if(e == hipSuccess) e = hipMemcpyAsync(recs.data(), d_recs, (size_t)n_amp*sizeof(AmpRec), hipMemcpyDeviceToHost, ctx->stream);
+	if(e == hipSuccess) e = hipMemcpyAsync(words.data(), d_words.p, 2*(size_t)n_amp*sizeof(uint4), hipMemcpyDeviceToHost, ctx->stream);
+	if(e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	d_words.release();
+	if(e != hipSuccess){ g_err = std::string("pcr_make_degenerate: ") + hipGetErrorString(e); return PCR_ERR_DEVICE; }
+	for(uint32_t k = 0;k < n_amp;++k){                                            // (sorted by pair, inside a pair in the reference's order)
+		if(recs[k].pair >= n) continue;
+		ShardAmp a;
+		a.pair = recs[k].pair; a.orient = (recs[k].f_entry > recs[k].r_entry) ? 1u : 0u; a.seq = seq_base + recs[k].seq;   // (k_amp_keys' orientation)
+		a.f = words[2*(size_t)k]; a.r = words[2*(size_t)k + 1];
+		out.push_back(a);
+	}
+	return PCR_OK;
+}
+
+// Sharded: every rank's list (local_rc: how this rank's collection went) -> the whole list on every rank, in the reference's order.
+// Each rank's list is sorted by (pair, orientation, sequence, sites) and the ranks hold disjoint ascending sequence ranges, so a
+// stable sort of the rank-order concatenation by (pair, orientation, sequence) is the merge.  One size all-gather, then one padded
+// all-gather of the records.
+int shard_gather_amplicons(pcr_ctx *ctx, int local_rc, std::vector<ShardAmp> &amps)
+{
+	pcr_comm *c = ctx->shard_comm;
+	const size_t W = (size_t)c->world;
+	const uint64_t me[2] = {local_rc != PCR_OK ? sh_fail_bit(local_rc) : 0ull, local_rc != PCR_OK ? 0ull : (uint64_t)amps.size()};
+	std::vector<uint64_t> sizes(2*W);
+	int rc = sh_allgather_host(ctx, c, me, sizeof(me), sizes.data());
+	if(rc != PCR_OK) return rc;
+	uint64_t st = 0, most = 0;
+	for(size_t r = 0;r < W;++r){ st |= sizes[2*r]; most = std::max(most, sizes[2*r + 1]); }
+	if(st) return sh_status_rc(st, local_rc, "pcr_make_degenerate");
+	std::vector<ShardAmp> send((size_t)most), all((size_t)most*W);
+	if(most){
+		std::copy(amps.begin(), amps.end(), send.begin());
+		if((rc = sh_allgather_host(ctx, c, send.data(), most*sizeof(ShardAmp), all.data())) != PCR_OK) return rc;
+	}
+	amps.clear();
+	for(size_t r = 0;r < W;++r) amps.insert(amps.end(), all.begin() + r*most, all.begin() + r*most + sizes[2*r + 1]);
+	std::stable_sort(amps.begin(), amps.end(), [](const ShardAmp &l, const ShardAmp &r){
+		return (l.pair != r.pair) ? l.pair < r.pair : (l.orient != r.orient) ? l.orient < r.orient : l.seq < r.seq; });
+	return PCR_OK;
+}
+
 } // namespace
 
 extern "C" int pcr_make_degenerate(pcr_ctx *ctx, pcr_pair *assays, uint32_t n, const pcr_optimize_args *o, uint8_t *valid_out)
 {
-	if(!ctx || !o || (n && (!assays || !valid_out))){ g_err = "pcr_make_degenerate: bad argument"; return PCR_ERR_ARG; }
+	if(!ctx){ g_err = "pcr_make_degenerate: bad argument"; return PCR_ERR_ARG; }
+	const bool args_ok = o && !(n && (!assays || !valid_out));
+	if(!args_ok) g_err = "pcr_make_degenerate: bad argument";
+	if(ctx->shard_comm){                                                           // sharded: every rank enters with the same call, or none goes on
+		int rc0 = args_ok ? enter_device(ctx) : PCR_ERR_ARG;
+		rc0 = shard_agree(ctx, rc0 == PCR_OK ? opt_fingerprint(3, assays, n, o, nullptr, 0) : 0, rc0, "pcr_make_degenerate");
+		if(rc0 != PCR_OK) return rc0;
+	}
+	if(!args_ok) return PCR_ERR_ARG;
 	DRAIN(ctx);
 	HIP_TRY(hipSetDevice(ctx->device));
 	if(n == 0) return PCR_OK;
 	SeqSet &S = ctx->sets[PCR_SET_TARGET];
-	if(!S.have_db){ g_err = "pcr_make_degenerate: no word DB (call pcr_select_words on the targets first)"; return PCR_ERR_STATE; }
-	{ const int erc = ensure_touched(ctx, S); if(erc != PCR_OK) return erc; }
 	int rc;
 	const bool use_taq = o->target.use_taq_mama != 0;
-	// ---- the candidate amplicons of every assay in the reference's order, with the words of their sites
+	// ---- the candidate amplicons of every assay in the reference's order, with the words of their sites (sharded: every rank's,
+	// merged; the rest of the call is local and the same on every rank)
+	std::vector<ShardAmp> cand;
+	rc = degenerate_amplicons(ctx, S, assays, n, o, ctx->shard_comm ? ctx->shard_first : 0, cand);
+	if(ctx->shard_comm) rc = shard_gather_amplicons(ctx, rc, cand);
+	if(rc != PCR_OK) return rc;
 	std::vector<std::vector<DegAmp> > amps(n);
-	if(S.n_entries){
-		uint32_t n_amp = 0;
-		if((rc = candidate_amplicons(ctx, S, assays, n, o->target.collect_threshold, o->target.amp_min, o->target.amp_max, &n_amp)) != PCR_OK) return rc;
-		if(n_amp){
-			const AmpRec *d_recs = nullptr; const uint32_t *d_pair_start = nullptr;
-			if((rc = order_amplicons(ctx, S, n_amp, n, &d_recs, &d_pair_start)) != PCR_OK) return rc;
-			DevBuf<uint4> d_words;
-			if((rc = d_words.ensure(2*(size_t)n_amp)) != PCR_OK) return rc;
-			hipLaunchKernelGGL(k_amp_words, dim3((n_amp + 255)/256), dim3(256), 0, ctx->stream, d_recs, n_amp, S.db.p, d_words.p);
-			std::vector<AmpRec> recs(n_amp); std::vector<uint4> words(2*(size_t)n_amp);
-			hipError_t e = hipGetLastError();
-			if(e == hipSuccess) e = hipMemcpyAsync(recs.data(), d_recs, (size_t)n_amp*sizeof(AmpRec), hipMemcpyDeviceToHost, ctx->stream);
-			if(e == hipSuccess) e = hipMemcpyAsync(words.data(), d_words.p, 2*(size_t)n_amp*sizeof(uint4), hipMemcpyDeviceToHost, ctx->stream);
-			if(e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-			d_words.release();
-			if(e != hipSuccess){ g_err = std::string("pcr_make_degenerate: ") + hipGetErrorString(e); return PCR_ERR_DEVICE; }
-			for(uint32_t k = 0;k < n_amp;++k){                                    // (sorted by pair, inside a pair in the reference's order)
-				if(recs[k].pair >= n) continue;
-				DegAmp a;
-				a.fkey = Planes{words[2*(size_t)k].x, words[2*(size_t)k].y, words[2*(size_t)k].z, words[2*(size_t)k].w};
-				a.rkey = Planes{words[2*(size_t)k + 1].x, words[2*(size_t)k + 1].y, words[2*(size_t)k + 1].z, words[2*(size_t)k + 1].w};
-				a.score = 0.0f;
-				amps[recs[k].pair].push_back(a);
-			}
-		}
+	for(const ShardAmp &x : cand){
+		DegAmp a;
+		a.fkey = Planes{x.f.x, x.f.y, x.f.z, x.f.w};
+		a.rkey = Planes{x.r.x, x.r.y, x.r.z, x.r.w};
+		a.score = 0.0f;
+		amps[x.pair].push_back(a);
 	}
 	// ---- identities, score, sort_target_candidates (assay.h:166-195)
 	std::vector<Planes> F(n), R(n);

@@ -41,6 +41,7 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 	pcr_pair *pool_out, uint32_t pool_cap, uint32_t *n_pool_out)
 {
 	if(!ctx || !a || !o || argc < 0 || (argc && !argv) || (pool_cap && !pool_out)){ g_err = "pcr_design: bad argument"; return PCR_ERR_ARG; }
+	if(ctx->shard_comm){ g_err = "pcr_design: a target shard is attached (pcr_shard_targets); the design loop does not run over shards -- detach it first"; return PCR_ERR_STATE; }
 	SeqSet &T = ctx->sets[PCR_SET_TARGET], &B = ctx->sets[PCR_SET_BACKGROUND];
 	if(T.n == 0){ g_err = "pcr_design: no target sequences loaded"; return PCR_ERR_STATE; }
 	if(o->n_target != T.n || o->n_background != B.n){ g_err = "pcr_design: the output description does not match the loaded sets"; return PCR_ERR_ARG; }

@@ -751,6 +751,10 @@ struct pcr_ctx {
 	DevBuf<pcr_amplicon> mx_amp;   // pcr_collect_amplicons records
 	DevBuf<OligoDev> opt_oligos; DevBuf<uint2> opt_jobs; DevBuf<float> opt_cov; DevBuf<uint32_t> opt_loc, opt_tasks;   // pcr_optimize_batch: base oligos + trial words, per-oligo variant ranges, coverages
 	DevBuf<Planes> mx_keys; uint32_t mx_n_keys = 0; DevBuf<uint32_t> mx_count;   // multiplex background: unique words of the accepted amplicons (pcr_multiplex.inc)
+	// an attached target shard (pcr_shard_targets, pcr_shard.inc): PCR_SET_TARGET holds rows [shard_first, shard_first + n) of
+	// shard_n_total, and the local search combines target coverage over shard_comm; NULL = not sharded
+	pcr_comm *shard_comm = nullptr; uint64_t shard_first = 0, shard_n_total = 0; int shard_mode = 0;
+	DevBuf<uint64_t> sh_rec, sh_full; DevBuf<uint8_t> sh_stage;   // the combine's record, the gathered records, staging of host collectives on RCCL
 	size_t amp_cap = size_t(1) << 20;
 	uint32_t n_cu = 256;        // compute units of the device (hipDeviceProp)
 	DevBuf<uint64_t> fin_scratch;   // k_finalize_big's keys
@@ -1603,6 +1607,7 @@ static int load_sequences_impl(pcr_ctx *ctx, int which, const uint8_t *packed4, 
 	S.n = n;
 	S.packed.assign(n, std::vector<uint8_t>());
 	S.len.assign(lengths, lengths + n);
+	if(which == PCR_SET_TARGET){ ctx->shard_comm = nullptr; ctx->shard_mode = 0; }   // a new target set is not the shard that was attached
 	S.weight.assign(n, 1.0f);
 	if(weights) S.weight.assign(weights, weights + n);
 	S.weight_dirty = true;
@@ -2933,7 +2938,8 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 
 } // extern "C"
 
+#include "pcr_exchange.inc"
+#include "pcr_shard.inc"
 #include "pcr_entry_sw_thermo.inc"
 #include "pcr_multiplex_screen.inc"
 #include "pcr_writers.inc"
-#include "pcr_exchange.inc"

@@ -11,7 +11,8 @@
 #include <rccl/rccl.h>       // types and enumerators only: no RCCL symbol is referenced at link time
 
 struct pcr_comm {
-	ncclComm_t comm = nullptr;
+	ncclComm_t comm = nullptr;   // RCCL communicator (pcr_comm_init_rank); nullptr for a host-collective one
+	pcr_host_allgather_fn host_fn = nullptr; void *host_user = nullptr;   // the caller's all-gather (pcr_comm_init_host)
 	int world = 0, rank = 0;
 	int device = 0;              // the communicator belongs to this device: any handle on it may exchange through it
 };
@@ -89,12 +90,33 @@ pcr_comm *pcr_comm_init_rank(pcr_ctx *ctx, const uint8_t id[PCR_COMM_ID_BYTES], 
 	return c;
 }
 
+pcr_comm *pcr_comm_init_host(pcr_ctx *ctx, int world, int rank, pcr_host_allgather_fn fn, void *user)
+{
+	if(!ctx || !fn || world < 1 || rank < 0 || rank >= world){ g_err = "pcr_comm_init_host: bad argument"; return nullptr; }
+	pcr_comm *c = new pcr_comm();
+	c->host_fn = fn; c->host_user = user;
+	c->world = world; c->rank = rank; c->device = ctx->device;
+	return c;
+}
+
 int pcr_comm_world(const pcr_comm *comm) { return comm ? comm->world : 0; }
 int pcr_comm_rank(const pcr_comm *comm) { return comm ? comm->rank : -1; }
 
 int pcr_exchange_bits(pcr_ctx *ctx, pcr_comm *comm, const uint64_t *d_local, uint64_t words_per_rank, uint64_t *d_full)
 {
 	if(!ctx || !comm || comm->device != ctx->device || (words_per_rank && (!d_local || !d_full))){ g_err = "pcr_exchange_bits: bad argument (the communicator belongs to another device?)"; return PCR_ERR_ARG; }
+	if(comm->host_fn){                                                            // host collective: device -> host, the caller's all-gather, host -> device
+		DRAIN(ctx);
+		HIP_TRY(hipSetDevice(ctx->device));
+		if(words_per_rank == 0) return PCR_OK;
+		std::vector<uint64_t> send(words_per_rank), recv((size_t)words_per_rank*comm->world);
+		HIP_TRY(hipMemcpyAsync(send.data(), d_local, words_per_rank*sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(hipStreamSynchronize(ctx->stream));
+		if(comm->host_fn(send.data(), words_per_rank*sizeof(uint64_t), recv.data(), comm->host_user) != 0){ g_err = "pcr_exchange_bits: the host all-gather failed"; return PCR_ERR_DEVICE; }
+		HIP_TRY(hipMemcpyAsync(d_full, recv.data(), recv.size()*sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+		HIP_TRY(hipStreamSynchronize(ctx->stream));                               // (recv is about to go away)
+		return PCR_OK;
+	}
 	RcclApi *api = rccl_api();
 	if(!api) return PCR_ERR_STATE;
 	// a pass enqueued by pcr_screen_device has final bitsets only once its counters have been looked at (a bucket overflow replays
@@ -109,7 +131,7 @@ int pcr_exchange_bits(pcr_ctx *ctx, pcr_comm *comm, const uint64_t *d_local, uin
 void pcr_comm_destroy(pcr_comm *comm)
 {
 	if(!comm) return;
-	RcclApi *api = rccl_api();
+	RcclApi *api = comm->comm ? rccl_api() : nullptr;
 	if(api && comm->comm){
 		(void)hipSetDevice(comm->device); (void)hipDeviceSynchronize();
 		(void)api->CommDestroy(comm->comm);

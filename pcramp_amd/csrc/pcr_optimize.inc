@@ -516,13 +516,15 @@ struct IterAssay {
 	ScoreH base;                                          // Score of the unmodified assay
 };
 
-// The coverage pass of one sequence set for all assays of the iteration: variant 0 of (assay, side 0) is the assay's own
-// forward oligo (the base Score), the valid trial words follow.  cov_out[v] for the flat variant list.
-int coverage_pass(pcr_ctx *ctx, SeqSet &S, const std::vector<OligoDev> &base, const std::vector<MoveJob> &jobs, const std::vector<OligoDev> &variants,
-	const pcr_amplify_args &a, std::vector<float> &cov_out)
+// The move-coverage bitsets of one sequence set for all assays of the iteration, enqueued on the handle's stream: variant 0 of
+// (assay, side 0) is the assay's own forward oligo (the base Score), the valid trial words follow.  *words_out = bitset words per
+// variant in ctx->bits_fr / bits_rf (0: the set has no DB entries or there are no variants -- every coverage is 0); the has_split
+// flag of the pass is in ctx->status.
+int coverage_bits(pcr_ctx *ctx, SeqSet &S, const std::vector<OligoDev> &base, const std::vector<MoveJob> &jobs, const std::vector<OligoDev> &variants,
+	const pcr_amplify_args &a, uint64_t *words_out)
 {
+	*words_out = 0;
 	const uint32_t nv = (uint32_t)variants.size();
-	cov_out.assign(nv, 0.0f);
 	if(!S.have_db){ g_err = "pcr_optimize_batch: no word DB (call pcr_select_words on the set first)"; return PCR_ERR_STATE; }
 	{ const int erc = ensure_touched(ctx, S); if(erc != PCR_OK) return erc; }
 	if(S.n_entries == 0 || nv == 0) return PCR_OK;
@@ -579,6 +581,19 @@ int coverage_pass(pcr_ctx *ctx, SeqSet &S, const std::vector<OligoDev> &base, co
 	hipLaunchKernelGGL(k_pair_moves_tasks, dim3(ctx->n_cu*8), dim3(256), 0, ctx->stream, (const MoveTask *)ctx->opt_tasks.p, d_task_count, task_cap, S.db.p,
 		(const MoveJob *)ctx->opt_jobs.p, ctx->opt_oligos.p + base.size(), a.ident_threshold, a.use_taq_mama, ctx->bits_fr.p, ctx->bits_rf.p, words);
 	HIP_TRY(hipGetLastError());
+	*words_out = words;
+	return PCR_OK;
+}
+
+// The coverage pass of one sequence set: cov_out[v] for the flat variant list (coverage_bits + compute_coverage's sum).
+int coverage_pass(pcr_ctx *ctx, SeqSet &S, const std::vector<OligoDev> &base, const std::vector<MoveJob> &jobs, const std::vector<OligoDev> &variants,
+	const pcr_amplify_args &a, std::vector<float> &cov_out)
+{
+	const uint32_t nv = (uint32_t)variants.size();
+	cov_out.assign(nv, 0.0f);
+	uint64_t words = 0;
+	const int rc = coverage_bits(ctx, S, base, jobs, variants, a, &words);
+	if(rc != PCR_OK || words == 0) return rc;
 	hipLaunchKernelGGL(k_cov_from_bits, dim3((nv + 127)/128), dim3(128), 0, ctx->stream, ctx->bits_fr.p, ctx->bits_rf.p, words, S.d_weight.p, (uint64_t)S.n, nv, ctx->opt_cov.p);
 	HIP_TRY(hipGetLastError());
 	uint32_t status = 0;
@@ -587,6 +602,23 @@ int coverage_pass(pcr_ctx *ctx, SeqSet &S, const std::vector<OligoDev> &base, co
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
 	if(status & 1u){ g_err = "Sequence::has_split: range is out of bounds"; return PCR_ERR_RANGE; }   // sequence.cpp:306-308
 	return PCR_OK;
+}
+
+// The target pass of a sharded iteration (pcr_shard.inc): the header agreement (local_rc: what this rank met earlier in the
+// iteration), this rank's bitsets, the combine over the ranks.  `late` runs while the bitsets are computed (the thermodynamics'
+// verdicts); its outcome travels in the combine's status word.  Every rank returns the same code.
+int coverage_pass_sharded(pcr_ctx *ctx, SeqSet &S, const std::vector<OligoDev> &base, const std::vector<MoveJob> &jobs, const std::vector<OligoDev> &variants,
+	const pcr_amplify_args &a, std::vector<float> &cov_out, int local_rc, const std::function<int()> &late)
+{
+	const uint32_t nv = (uint32_t)variants.size();
+	cov_out.assign(nv, 0.0f);
+	const int rc = shard_header(ctx, local_rc, nv, sh_hash(SH_HASH0, jobs.data(), jobs.size()*sizeof(MoveJob)));
+	if(rc != PCR_OK) return rc;
+	if(nv == 0) return late();                                                     // (an assay always has its base word: not reached)
+	uint64_t words = 0;
+	const int brc = coverage_bits(ctx, S, base, jobs, variants, a, &words);
+	const int lrc = late();
+	return shard_combine(ctx, S, nv, words, words != 0, brc != PCR_OK ? brc : lrc, cov_out);
 }
 
 int multiplex_pass(pcr_ctx *ctx, const std::vector<OligoDev> &base, const std::vector<MoveJob> &jobs, const std::vector<OligoDev> &variants,
@@ -688,6 +720,9 @@ int evaluate_iteration(pcr_ctx *ctx, std::vector<IterAssay> &A, const pcr_optimi
 	OptTimer timer(ctx->timing);
 	const bool multiplex = pool != nullptr;
 	const uint32_t n = (uint32_t)A.size();
+	// sharded (pcr_shard.inc): a failure before the target combine is reported to the other ranks at its header step
+	const bool sharded = ctx->shard_comm != nullptr;
+	auto fail = [&](int rc) -> int { return sharded ? shard_header(ctx, rc, 0, 0) : rc; };
 	// ---- trial words and their is_valid jobs.  The assays are independent: ranges of them go to a few host threads (1 000
 	// trial assays make ~200 000 trial words per iteration), whose lists are then joined in assay order.
 	std::vector<thermo::Job> tj;                                                  // one packed record per trial word that needs thermodynamics
@@ -729,8 +764,8 @@ int evaluate_iteration(pcr_ctx *ctx, std::vector<IterAssay> &A, const pcr_optimi
 			}
 		});
 		for(const Part &P : parts){
-			if(P.err == 1){ g_err = "pcr_optimize_batch: unknown move"; return PCR_ERR_ARG; }
-			if(P.err == 2){ g_err = "pcr_optimize_batch: a trial oligo is longer than 32, holds a non-base slot or has more than 65536 expansions"; return PCR_ERR_ARG; }
+			if(P.err == 1){ g_err = "pcr_optimize_batch: unknown move"; return fail(PCR_ERR_ARG); }
+			if(P.err == 2){ g_err = "pcr_optimize_batch: a trial oligo is longer than 32, holds a non-base slot or has more than 65536 expansions"; return fail(PCR_ERR_ARG); }
 		}
 		for(const Part &P : parts){
 			const uint32_t off = (uint32_t)tj.size();
@@ -753,8 +788,10 @@ int evaluate_iteration(pcr_ctx *ctx, std::vector<IterAssay> &A, const pcr_optimi
 	std::thread th_thread;
 	bool beside = !tj.empty() && !getenv("PCRAMP_OPT_SERIAL");
 	if(beside){
-		if(!ctx->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-		HIP_TRY(hipStreamSynchronize(ctx->stream));                                // (nothing of this handle is in flight that the records could race with)
+		hipError_t e = hipSuccess;
+		if(!ctx->aux_stream) e = hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking);
+		if(e == hipSuccess) e = hipStreamSynchronize(ctx->stream);               // (nothing of this handle is in flight that the records could race with)
+		if(e != hipSuccess){ g_err = std::string("pcr_optimize_batch: ") + hipGetErrorString(e); return fail(PCR_ERR_DEVICE); }
 		try{
 			th_thread = std::thread([&]{
 				if(hipSetDevice(ctx->device) != hipSuccess){ rc_th = PCR_ERR_DEVICE; err_th = "hipSetDevice failed on the thermodynamics thread"; return; }
@@ -765,12 +802,12 @@ int evaluate_iteration(pcr_ctx *ctx, std::vector<IterAssay> &A, const pcr_optimi
 		catch(const std::exception &){                                                // no thread to be had: one after the other, as below
 			beside = false;
 			rc = run_thermo_valid(ctx, tj, n_exp, &o->thermo, bad);
-			if(rc != PCR_OK) return rc;
+			if(rc != PCR_OK) return fail(rc);
 		}
 	}
 	else{
 		rc = run_thermo_valid(ctx, tj, n_exp, &o->thermo, bad);
-		if(rc != PCR_OK) return rc;
+		if(rc != PCR_OK) return fail(rc);
 	}
 	struct Joiner { std::thread &t; ~Joiner(){ if(t.joinable()) t.join(); } } joiner{th_thread};   // every return path waits for the thread
 	auto apply_verdicts = [&](){
@@ -834,20 +871,40 @@ int evaluate_iteration(pcr_ctx *ctx, std::vector<IterAssay> &A, const pcr_optimi
 		}
 	}
 	std::vector<float> tcov, bcov, mcov;
-	timer.next(3);
-	if((rc = coverage_pass(ctx, ctx->sets[PCR_SET_TARGET], base_t, jobs, var_t, o->target, tcov)) != PCR_OK) return rc;
-	timer.next(4);
-	if(o->have_background){ if((rc = coverage_pass(ctx, ctx->sets[PCR_SET_BACKGROUND], base_b, jobs, var_b, o->background, bcov)) != PCR_OK) return rc; }
-	else bcov.assign(var_t.size(), 0.0f);
-	timer.next(5);
-	if(multiplex){ if((rc = multiplex_pass(ctx, base_m, jobs, var_m, o->multiplex_threshold, o->target.use_taq_mama, mcov)) != PCR_OK) return rc; }
-	else mcov.assign(var_t.size(), 0.0f);
 	std::vector<uint8_t> took;                                                    // per trial word: it has a slot in the variant lists
-	if(beside){
+	auto join_verdicts = [&]() -> int {
 		for(uint32_t a = 0;a < n;++a) for(int side = 0;side < 2;++side) for(const TrialRow &r : A[a].rows[side]) took.push_back(r.valid ? 1 : 0);
 		th_thread.join();
 		if(rc_th != PCR_OK){ g_err = err_th; return rc_th; }
 		apply_verdicts();
+		return PCR_OK;
+	};
+	timer.next(3);
+	if(sharded){
+		// everything local first -- background and multiplex passes beside the thermodynamics -- so that the target combine's
+		// header carries the failures of the iteration, and the verdicts' (joined while the target bitsets are computed) its
+		// status word: after the header, no rank can leave on its own
+		int lrc = PCR_OK;
+		if(o->have_background) lrc = coverage_pass(ctx, ctx->sets[PCR_SET_BACKGROUND], base_b, jobs, var_b, o->background, bcov);
+		else bcov.assign(var_t.size(), 0.0f);
+		if(lrc == PCR_OK){
+			if(multiplex) lrc = multiplex_pass(ctx, base_m, jobs, var_m, o->multiplex_threshold, o->target.use_taq_mama, mcov);
+			else mcov.assign(var_t.size(), 0.0f);
+		}
+		timer.next(4);
+		if((rc = coverage_pass_sharded(ctx, ctx->sets[PCR_SET_TARGET], base_t, jobs, var_t, o->target, tcov, lrc,
+			[&]() -> int { return beside ? join_verdicts() : PCR_OK; })) != PCR_OK) return rc;
+		timer.next(5);
+	}
+	else{
+		if((rc = coverage_pass(ctx, ctx->sets[PCR_SET_TARGET], base_t, jobs, var_t, o->target, tcov)) != PCR_OK) return rc;
+		timer.next(4);
+		if(o->have_background){ if((rc = coverage_pass(ctx, ctx->sets[PCR_SET_BACKGROUND], base_b, jobs, var_b, o->background, bcov)) != PCR_OK) return rc; }
+		else bcov.assign(var_t.size(), 0.0f);
+		timer.next(5);
+		if(multiplex){ if((rc = multiplex_pass(ctx, base_m, jobs, var_m, o->multiplex_threshold, o->target.use_taq_mama, mcov)) != PCR_OK) return rc; }
+		else mcov.assign(var_t.size(), 0.0f);
+		if(beside){ if((rc = join_verdicts()) != PCR_OK) return rc; }
 	}
 	size_t tk = 0;
 	for(uint32_t a = 0;a < n;++a){
@@ -887,7 +944,15 @@ extern "C" {
 int pcr_optimize_batch(pcr_ctx *ctx, const pcr_pair *assays, uint32_t n, const pcr_optimize_args *o, const pcr_pair *pool, uint32_t n_pool,
 	pcr_pair *best_out, float *score_out, uint32_t *iterations_out)
 {
-	if(!ctx || !check_opt_args(o) || (n && (!assays || !best_out)) || (n_pool && !pool)){ g_err = "pcr_optimize_batch: bad argument"; return PCR_ERR_ARG; }
+	if(!ctx){ g_err = "pcr_optimize_batch: bad argument"; return PCR_ERR_ARG; }
+	const bool args_ok = check_opt_args(o) && !(n && (!assays || !best_out)) && !(n_pool && !pool);
+	if(!args_ok) g_err = "pcr_optimize_batch: bad argument";
+	if(ctx->shard_comm){                                                           // sharded: every rank enters with the same call, or none goes on
+		int rc0 = args_ok ? enter_device(ctx) : PCR_ERR_ARG;
+		rc0 = shard_agree(ctx, rc0 == PCR_OK ? opt_fingerprint(1, assays, n, o, pool, n_pool) : 0, rc0, "pcr_optimize_batch");
+		if(rc0 != PCR_OK) return rc0;
+	}
+	if(!args_ok) return PCR_ERR_ARG;
 	DRAIN(ctx);
 	HIP_TRY(hipSetDevice(ctx->device));
 	const bool multiplex = o->use_multiplex != 0;
@@ -953,9 +1018,21 @@ int pcr_optimize_batch(pcr_ctx *ctx, const pcr_pair *assays, uint32_t n, const p
 int pcr_optimization_move(pcr_ctx *ctx, const pcr_pair *assay, int move, int side, const pcr_optimize_args *o, const pcr_pair *pool, uint32_t n_pool,
 	const float *score_threshold, pcr_word128 *word_out, float *score_out, float *base_score_out)
 {
-	if(!ctx || !assay || !check_opt_args(o) || (side != 0 && side != 1) || move < 0 || move > PCR_MOVE_GROW3 || !word_out || !score_out || (n_pool && !pool)){
-		g_err = "pcr_optimization_move: bad argument"; return PCR_ERR_ARG;
+	if(!ctx){ g_err = "pcr_optimization_move: bad argument"; return PCR_ERR_ARG; }
+	const bool args_ok = assay && check_opt_args(o) && (side == 0 || side == 1) && move >= 0 && move <= PCR_MOVE_GROW3 && word_out && score_out && !(n_pool && !pool);
+	if(!args_ok) g_err = "pcr_optimization_move: bad argument";
+	if(ctx->shard_comm){
+		int rc0 = args_ok ? enter_device(ctx) : PCR_ERR_ARG;
+		uint64_t fp = 0;
+		if(rc0 == PCR_OK){
+			const uint64_t extra[3] = {(uint64_t)move, (uint64_t)side, score_threshold ? 1ull : 0ull};
+			fp = sh_hash(opt_fingerprint(2, assay, 1, o, pool, n_pool), extra, sizeof(extra));
+			if(score_threshold) fp = sh_hash(fp, score_threshold, 3*sizeof(float));
+		}
+		rc0 = shard_agree(ctx, fp, rc0, "pcr_optimization_move");
+		if(rc0 != PCR_OK) return rc0;
 	}
+	if(!args_ok) return PCR_ERR_ARG;
 	DRAIN(ctx);
 	HIP_TRY(hipSetDevice(ctx->device));
 	const bool multiplex = o->use_multiplex != 0;

@@ -7,6 +7,10 @@ ONE all-gather of the per-pair bitset words (RCCL over xGMI on the GPU box, gloo
 tests).  Weighted coverage is then re-summed identically on every rank from the gathered bits
 (pcr_coverage_from_bits keeps the reference's summation order).  The reference itself has no
 target sharding (its MPI mode shards trials, main.cpp:65); this layer is new.
+
+The local search (pcr_optimize_batch, pcr_make_degenerate) runs over the same kind of shard with any boundaries: the library
+combines every trial word's target coverage over a communicator (Screener.shard_targets); gloo_allgather() is the host
+collective that drives it from torch.distributed (Screener.comm_init_host).
 """
 import numpy as np
 
@@ -45,3 +49,20 @@ def gather_bitsets(local_words, ranges, group=None):
     dist.all_gather_into_tensor(flat_out, flat_in, group=group)
     out = flat_out.view((world,) + lead + (wmax,))
     return torch.cat([out[r][..., :words[r]] for r in range(world)], dim=-1)
+
+
+def gloo_allgather(group=None):
+    """-> allgather(bytes) -> bytes: world x len(send) in rank order, ONE dist.all_gather_into_tensor on CPU uint8 tensors (the
+    callback of Screener.comm_init_host; needs a process group with a CPU backend, e.g. gloo)."""
+    import torch
+    import torch.distributed as dist
+
+    def allgather(send):
+        world = dist.get_world_size(group)
+        if not send:
+            return b""
+        src = torch.frombuffer(bytearray(send), dtype=torch.uint8)
+        out = torch.empty(world * src.numel(), dtype=torch.uint8)
+        dist.all_gather_into_tensor(out, src, group=group)
+        return out.numpy().tobytes()
+    return allgather
