@@ -230,7 +230,11 @@ pcr_comm *pcr_comm_init_host(pcr_ctx *ctx, int world, int rank, pcr_host_allgath
  *       whole on every rank and not combined.  All ranks must call with the same batch (checked: PCR_ERR_ARG on every rank).
  *   pcr_make_degenerate  gathers every rank's candidate amplicons and merges them into the reference's order (order_amplicons:
  *       by pair, orientation, global sequence, plus site, minus site) before the unchanged walk.
- *   pcr_design  returns PCR_ERR_STATE.
+ *   pcr_design  runs the design loop over the shard once the handle is design-ready (pcr_shard_sampler_targets below); before
+ *       that it returns PCR_ERR_STATE at once, on each rank by itself (no collective).  Every rank must then call it with the
+ *       same arguments, command line and pcr_output describing all n_total targets (checked: PCR_ERR_ARG on every rank); every
+ *       rank leaves the same text and the same pool, equal to the unsharded call on the whole set.  Rank 0 samples the trials
+ *       over its host copy and sends them; select / amplify run over local rows, the best assay's bits and amplicons are gathered.
  * A failure on one rank (incl. the has_split range error) is returned by every rank; no rank leaves a collective out.
  * pcr_shard_combine_mode: 0 = not sharded, 1 = exact partials (every partial sum is exactly representable in double, so one
  * all-gather of per-rank sums per iteration is exact), 2 = ordered chain (the reference's sequential sum, rank after rank, 2 x world
@@ -238,6 +242,22 @@ pcr_comm *pcr_comm_init_host(pcr_ctx *ctx, int world, int rank, pcr_host_allgath
  * provably exact, else 2. */
 int pcr_shard_targets(pcr_ctx *ctx, pcr_comm *comm, uint64_t first_seq, uint64_t n_total);
 int pcr_shard_combine_mode(pcr_ctx *ctx);
+
+/* pcr_shard_gather_bits: collective over the attached shard.  d_local (device): n_vec bitsets over this rank's n rows, row i at bit
+ * i%64 of word i/64, bitset v at d_local + v*local_stride_words; d_global (device, every rank): the same n_vec bitsets over all
+ * n_total rows at d_global + v*global_stride_words, bits at or past n_total zero (the whole stride is written).  Boundaries may
+ * lie anywhere (pcr_exchange_bits needs multiples of 64).  One agreement on n_vec, one all-gather of padded records (on the
+ * handle's stream over RCCL; device -> host -> fn -> device over a host communicator), then k_shard_stitch on the stream; returns
+ * after the result is complete.  A bad argument on any rank: PCR_ERR_ARG on every rank; no shard attached: PCR_ERR_STATE. */
+int pcr_shard_gather_bits(pcr_ctx *ctx, const uint64_t *d_local, uint32_t n_vec, uint64_t local_stride_words,
+	uint64_t *d_global, uint64_t global_stride_words);
+
+/* pcr_shard_sampler_targets: collective; makes the handle design-ready.  Rank 0 passes the whole target set packed as for
+ * pcr_load_sequences (n == n_total), every other rank n = 0 and null pointers.  The copy stays on the host (0.5 B per base) and
+ * is what rank 0's sampler of pcr_design walks; one all-gather checks it against every rank's rows (lengths and a hash of the
+ * bytes).  A mismatch, a wrong n or rank 0 passing nothing: PCR_ERR_ARG on every rank.  Detaching, re-attaching or reloading
+ * the target set drops the copy and the design-ready flag. */
+int pcr_shard_sampler_targets(pcr_ctx *ctx, const uint8_t *packed4, const uint64_t *byte_offsets, const uint64_t *lengths, uint64_t n);
 
 
 /* ---- Smith-Waterman primer x template alignment (rows a7/a8 of the scope table) */

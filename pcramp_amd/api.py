@@ -118,6 +118,7 @@ ABI_SYMBOLS = [
     "pcr_format_oligos", "pcr_format_header", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
+    "pcr_shard_gather_bits", "pcr_shard_sampler_targets",
     "pcr_comm_unique_id", "pcr_comm_init_rank", "pcr_comm_world", "pcr_comm_rank", "pcr_exchange_bits", "pcr_comm_destroy", "pcr_comm_library",
 ]
 
@@ -184,6 +185,8 @@ def load_library():
     L.pcr_comm_init_host.argtypes = [C.c_void_p, C.c_int, C.c_int, HOST_ALLGATHER, C.c_void_p]
     L.pcr_shard_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]
     L.pcr_shard_combine_mode.argtypes = [C.c_void_p]
+    L.pcr_shard_gather_bits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64]
+    L.pcr_shard_sampler_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     L.pcr_sw_align_words.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.pcr_background_match.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(BackgroundArgs), C.c_void_p]
     L.pcr_multiplex_match.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_void_p]
@@ -447,7 +450,9 @@ class Screener:
 
     def _check(self, rc):
         if rc != 0:
-            raise PcrError(_err(self.L))
+            e = PcrError(_err(self.L))
+            e.rc = rc
+            raise e
 
     def load_sequences(self, packed, byte_offsets, lengths, weights=None, which=TARGET):
         packed = np.ascontiguousarray(packed, dtype=np.uint8)
@@ -804,6 +809,31 @@ class Screener:
     def shard_combine_mode(self):
         """0 = not sharded, 1 = exact partials, 2 = ordered chain (include/pcramp_hip.h)."""
         return int(self.L.pcr_shard_combine_mode(self.h))
+
+    def shard_gather_bits(self, d_local, n_vec, local_stride_words, d_global, global_stride_words):
+        """Collective (pcr_shard_gather_bits): n_vec bitsets over this rank's rows (device: a torch tensor or a pointer) ->
+        the same bitsets over all n_total rows into d_global on every rank, boundaries anywhere; bits past n_total are zero."""
+        ptr = lambda x: 0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        self._check(self.L.pcr_shard_gather_bits(self.h, ptr(d_local), int(n_vec), int(local_stride_words), ptr(d_global),
+                                                 int(global_stride_words)))
+
+    def shard_sampler_targets(self, texts=None, packed=None, byte_offsets=None, lengths=None):
+        """Collective (pcr_shard_sampler_targets): makes the handle design-ready.  Rank 0 passes the whole target set -- IUPAC
+        texts, or packed bytes / byte offsets / lengths as for load_sequences; every other rank passes nothing."""
+        if texts is not None:
+            packs = [W.pack_codes(W.codes_from_text(t)) for t in texts]
+            lengths = [len(t) for t in texts]
+            byte_offsets = np.cumsum([0] + [p.size for p in packs[:-1]]) if packs else []
+            packed = np.concatenate(packs) if packs else np.zeros(1, np.uint8)
+        if lengths is None:
+            self._check(self.L.pcr_shard_sampler_targets(self.h, None, None, None, 0))
+            return
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        if packed.size == 0:
+            packed = np.zeros(1, np.uint8)
+        bo = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+        self._check(self.L.pcr_shard_sampler_targets(self.h, packed.ctypes.data, bo.ctypes.data, ln.ctypes.data, ln.size))
 
     def staging_mode(self):
         """'lean' (the CPU stores the per-pass tables straight into device memory, no staging launch) or 'k_stage'."""

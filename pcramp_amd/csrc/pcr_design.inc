@@ -8,16 +8,23 @@
 // word DBs, the top-down start, the local search, the compatibility flags: each a pure function of the trial and of state that
 // does not change inside an iteration); what only the record-setting trials need (the alignment-based covers) is asked for as the
 // walk reaches them, as the reference does.
+//
+// Over a target shard (pcr_shard_targets + pcr_shard_sampler_targets) the same loop runs on every rank, with global host copies
+// of the weights and active flags: rank 0 samples over its copy of the whole set and sends the trials; the target word DB,
+// amplify and amplicon collection run over local rows; the pool cover and the best assay's amplicons and bits are gathered
+// (pcr_shard_design.inc); the local search and the top-down start combine on their own.  Steps over data every rank holds
+// whole (backgrounds, the multiplex set, the pool) compute the same on every rank; a failure in a step over local rows is kept
+// in `lrc` and travels in the status word of the next exchange, so that every rank returns the same code.
 
 namespace {
 
 struct DesignState { std::vector<pcr_pair> pool; };
 
 // summed weights of the active sequences in index order, float accumulation (main.cpp:603, :649)
-inline float active_norm(const SeqSet &S, uint32_t &n_active)
+inline float active_norm(const std::vector<float> &weight, const std::vector<uint8_t> &active, uint32_t &n_active)
 {
 	float norm = 0.0f; n_active = 0;
-	for(uint32_t i = 0;i < S.n;++i){ if(S.active[i]){ ++n_active; norm += S.weight[i]; } }
+	for(size_t i = 0;i < active.size();++i){ if(active[i]){ ++n_active; norm += weight[i]; } }
 	return norm;
 }
 
@@ -41,16 +48,37 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 	pcr_pair *pool_out, uint32_t pool_cap, uint32_t *n_pool_out)
 {
 	if(!ctx || !a || !o || argc < 0 || (argc && !argv) || (pool_cap && !pool_out)){ g_err = "pcr_design: bad argument"; return PCR_ERR_ARG; }
-	if(ctx->shard_comm){ g_err = "pcr_design: a target shard is attached (pcr_shard_targets); the design loop does not run over shards -- detach it first"; return PCR_ERR_STATE; }
+	if(ctx->shard_comm && !ctx->design_ready){ g_err = "pcr_design: a target shard is attached (pcr_shard_targets) but the handle is not design-ready (pcr_shard_sampler_targets)"; return PCR_ERR_STATE; }
+	const bool sharded = ctx->shard_comm != nullptr;
 	SeqSet &T = ctx->sets[PCR_SET_TARGET], &B = ctx->sets[PCR_SET_BACKGROUND];
-	if(T.n == 0){ g_err = "pcr_design: no target sequences loaded"; return PCR_ERR_STATE; }
-	if(o->n_target != T.n || o->n_background != B.n){ g_err = "pcr_design: the output description does not match the loaded sets"; return PCR_ERR_ARG; }
-	if(a->num_trial == 0 || a->num_trial > (1u << 20)){ g_err = "pcr_design: num_trial out of range"; return PCR_ERR_ARG; }
-	DRAIN(ctx);
-	HIP_TRY(hipSetDevice(ctx->device));
+	const uint64_t n_all = sharded ? ctx->shard_n_total : T.n;                                // the targets the loop designs over
+	int lrc = PCR_OK;                                                                          // this rank's outcome since the last exchange
+	if(n_all == 0){ g_err = "pcr_design: no target sequences loaded"; lrc = PCR_ERR_STATE; }
+	else if(o->n_target != n_all || o->n_background != B.n){ g_err = "pcr_design: the output description does not match the loaded sets"; lrc = PCR_ERR_ARG; }
+	else if(a->num_trial == 0 || a->num_trial > (1u << 20)){ g_err = "pcr_design: num_trial out of range"; lrc = PCR_ERR_ARG; }
+	if(!sharded && lrc != PCR_OK) return lrc;
+	int rc;
+	std::vector<float> g_weight; std::vector<uint8_t> g_active;                                // all n_all targets, global index order
+	auto now_ms = [](){ return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+	double t_exchange = 0.0;
+	if(sharded){
+		const double t0 = now_ms();
+		if(lrc == PCR_OK) lrc = enter_device(ctx);
+		if((rc = shard_agree(ctx, lrc == PCR_OK ? design_fingerprint(a, n_all, o, argc, argv) : 0ull, lrc, "pcr_design")) != PCR_OK) return rc;
+		if((rc = shard_gather_rows(ctx, PCR_OK, g_weight, g_active)) != PCR_OK) return rc;
+		t_exchange += now_ms() - t0;
+	}
+	else{
+		DRAIN(ctx);
+		HIP_TRY(hipSetDevice(ctx->device));
+		g_weight = T.weight; g_active = T.active;
+	}
+	// pcr_set_active on this rank's slice of the global flags
+	auto set_local_active = [&]() -> int {
+		return pcr_set_active(ctx, PCR_SET_TARGET, g_active.data() + (sharded ? ctx->shard_first : 0));
+	};
 	DesignState D;
 	ctx->design_text.clear();
-	int rc;
 	// ---- options as the entry points take them
 	pcr_optimize_args oa; memset(&oa, 0, sizeof(oa));
 	oa.max_degen = a->max_degen; oa.primer_min = a->primer_min; oa.primer_max = a->primer_max; oa.thermo = a->thermo;
@@ -82,21 +110,23 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 
 	uint32_t global_seed = a->seed;
 	uint32_t assay_iteration = 0, major_id = 1, minor_id = 1;
-	const uint64_t t_words = (T.n + 63)/64, b_words = (B.n + 63)/64;
+	const uint64_t t_words = (T.n + 63)/64, g_words = (n_all + 63)/64, b_words = (B.n + 63)/64;
 	std::vector<uint64_t> total_background(std::max<uint64_t>(b_words, 1), 0);
 	std::vector<std::vector<uint8_t> > amplicon_codes;                                         // multiplex_background_seq, in the order it grew
 	const uint32_t n_trial = a->num_trial;
-	auto now_ms = [](){ return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	while(true){
 		++assay_iteration;
-		double t_mark = now_ms(), t_phase[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+		double t_mark = now_ms(), t_phase[8] = {t_exchange, 0, 0, 0, 0, 0, 0, 0};
+		t_exchange = 0.0;
 		auto lap = [&](int k){ const double t = now_ms(); t_phase[k] += t - t_mark; t_mark = t; };
 		uint32_t targets_remaining = 0;
-		for(uint32_t i = 0;i < T.n;++i) targets_remaining += T.active[i] ? 1u : 0u;
+		for(uint8_t x : g_active) targets_remaining += x ? 1u : 0u;
 		if(targets_remaining == 0){                                                             // main.cpp:488-502
-			std::vector<uint8_t> all(T.n, 1);
-			if((rc = pcr_set_active(ctx, PCR_SET_TARGET, all.data())) != PCR_OK) return rc;
-			targets_remaining = T.n; ++major_id; minor_id = 1;
+			std::fill(g_active.begin(), g_active.end(), (uint8_t)1);
+			rc = set_local_active();
+			if(!sharded && rc != PCR_OK) return rc;
+			if(lrc == PCR_OK) lrc = rc;
+			targets_remaining = (uint32_t)n_all; ++major_id; minor_id = 1;
 		}
 		struct It { const pcr_output *o; uint32_t it, major, minor, remaining; };
 		It itr = {o, assay_iteration, major_id, minor_id, targets_remaining};
@@ -104,18 +134,33 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 		// ---- the trial assays (main.cpp:538-550, one thread: one local seed per iteration)
 		uint32_t local_seed = pcr_host_rand_r(&global_seed);
 		std::vector<pcr_pair> trial(n_trial);
-		if((rc = pcr_random_assays(ctx, PCR_SET_TARGET, &local_seed, n_trial, &sa, &a->thermo, trial.data(), nullptr)) != PCR_OK) return rc;
+		if(!sharded){ if((rc = pcr_random_assays(ctx, PCR_SET_TARGET, &local_seed, n_trial, &sa, &a->thermo, trial.data(), nullptr)) != PCR_OK) return rc; }
+		else{
+			// rank 0 samples over its copy of the whole set with the global flags; the trials go to every rank with its status
+			if(ctx->shard_comm->rank == 0 && lrc == PCR_OK){
+				const SampView v = {ctx->samp_packed.data(), ctx->samp_len.data(), g_active.data(), (uint32_t)n_all};
+				lrc = sampler_args_ok(&sa) ? random_assays_view(ctx, v, &local_seed, n_trial, &sa, &a->thermo, trial.data(), nullptr) : PCR_ERR_ARG;
+			}
+			lap(0);
+			if((rc = shard_share_trials(ctx, lrc, trial)) != PCR_OK) return rc;
+			lap(7);
+		}
 		lap(0);
 		// ---- the word DBs for them (main.cpp:579-615, :644-691)
 		uint32_t num_active_background = 0, num_active_target = 0;
 		float active_background_norm = 0.0f;
 		if(B.n > 0){
-			active_background_norm = active_norm(B, num_active_background);
+			active_background_norm = active_norm(B.weight, B.active, num_active_background);
 			if((rc = pcr_select_words(ctx, PCR_SET_BACKGROUND, trial.data(), n_trial, a->optimize_5, a->optimize_3, oa.background.collect_threshold, min_len_bg, nullptr)) != PCR_OK) return rc;
 		}
-		const float active_target_norm = active_norm(T, num_active_target);
-		if((rc = pcr_select_words(ctx, PCR_SET_TARGET, trial.data(), n_trial, a->optimize_5, a->optimize_3, oa.target.collect_threshold, min_len, nullptr)) != PCR_OK) return rc;
+		const float active_target_norm = active_norm(g_weight, g_active, num_active_target);
+		rc = pcr_select_words(ctx, PCR_SET_TARGET, trial.data(), n_trial, a->optimize_5, a->optimize_3, oa.target.collect_threshold, min_len, nullptr);
+		if(!sharded && rc != PCR_OK) return rc;
 		lap(1);
+		if(sharded){                                                                            // (the local target DB's outcome)
+			if((rc = shard_agree(ctx, 0ull, rc, "pcr_design")) != PCR_OK) return rc;
+			lap(7);
+		}
 		// ---- top-down start and local search of every trial (main.cpp:707-735)
 		std::vector<uint8_t> usable(n_trial, 1);
 		if(a->top_down_search){ if((rc = pcr_make_degenerate(ctx, trial.data(), n_trial, &oa, usable.data())) != PCR_OK) return rc; }
@@ -156,7 +201,16 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 				if(!compatible[g]) continue;                                                      // :748-757
 				if(score_lt(best_score, s)){
 					uint8_t ok1 = 1; float mc1 = 0.0f, pc1 = 0.0f;
-					if((rc = pcr_multiplex_screen(ctx, &gp[g], 1, D.pool.data(), (uint32_t)D.pool.size(), &ma, nullptr, &ok1, &mc1, &pc1)) != PCR_OK) return rc;
+					if(!sharded){ if((rc = pcr_multiplex_screen(ctx, &gp[g], 1, D.pool.data(), (uint32_t)D.pool.size(), &ma, nullptr, &ok1, &mc1, &pc1)) != PCR_OK) return rc; }
+					else{
+						// (a) is `compatible`, (b) runs over the multiplex set every rank holds; (c) needs the amplicons over all targets
+						if((rc = pcr_multiplex_screen(ctx, &gp[g], 1, nullptr, 0, &ma, nullptr, &ok1, &mc1, &pc1)) != PCR_OK) return rc;
+						if(!D.pool.empty()){
+							lap(3);
+							if((rc = shard_pool_cover(ctx, &gp[g], D.pool.data(), (uint32_t)D.pool.size(), &ma, pc1)) != PCR_OK) return rc;
+							lap(7);
+						}
+					}
 					s.bc += mc1;                                                                   // :767-771
 					if(s.bc <= a->max_background_cover) s.bc += pc1;                               // :783-803
 				}
@@ -180,9 +234,26 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 		if(best_score.tc <= 0.0f) break;                                                        // :926-930: nothing detects a target
 		// ---- the best assay: the targets it detects, its amplicons (main.cpp:898-922)
 		std::vector<uint64_t> target_match(t_words, 0);
-		if((rc = pcr_amplify(ctx, PCR_SET_TARGET, &best_assay, 1, &find_args, target_match.data(), nullptr, nullptr, nullptr)) != PCR_OK) return rc;
+		rc = pcr_amplify(ctx, PCR_SET_TARGET, &best_assay, 1, &find_args, target_match.data(), nullptr, nullptr, nullptr);
+		if(!sharded && rc != PCR_OK) return rc;
 		std::vector<pcr_amplicon> amp;
-		if(a->use_multiplex){
+		std::vector<std::vector<uint8_t> > amp_codes_all;                                      // sharded: the inner stretches of `amp`
+		if(sharded){
+			// the bits over all targets; then the amplicons over all targets, records with global sequence indices
+			lrc = rc;
+			lap(4);
+			if(lrc == PCR_OK && (lrc = ctx->sh_bits.ensure((size_t)(t_words + g_words))) == PCR_OK){
+				const hipError_t e = hipMemcpyAsync(ctx->sh_bits.p, target_match.data(), t_words*sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream);
+				if(e != hipSuccess){ g_err = std::string("pcr_design: ") + hipGetErrorString(e); lrc = PCR_ERR_DEVICE; }
+			}
+			if((rc = shard_gather_bits_impl(ctx, ctx->sh_bits.p, 1u, t_words, lrc == PCR_OK ? ctx->sh_bits.p + t_words : nullptr, g_words, lrc)) != PCR_OK) return rc;
+			target_match.assign(g_words, 0);
+			HIP_TRY(hipMemcpyAsync(target_match.data(), ctx->sh_bits.p + t_words, g_words*sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+			HIP_TRY(hipStreamSynchronize(ctx->stream));
+			if(a->use_multiplex){ if((rc = shard_gather_amplicons(ctx, &best_assay, &ma, PCR_OK, amp, amp_codes_all)) != PCR_OK) return rc; }
+			lap(7);
+		}
+		else if(a->use_multiplex){
 			amp.resize(4096);
 			int64_t n = pcr_collect_amplicons(ctx, PCR_SET_TARGET, &best_assay, a->target_threshold, a->target_amp_min, a->target_amp_max, amp.data(), amp.size());
 			if(n < 0) return (int)n;
@@ -206,7 +277,8 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 		// ---- the multiplex background grows by the assay's unique amplicons; the targets are split (main.cpp:989-1017)
 		if(a->use_multiplex){
 			std::vector<std::vector<uint8_t> > mine;
-			for(const pcr_amplicon &r : amp){
+			if(sharded) mine.swap(amp_codes_all);
+			else for(const pcr_amplicon &r : amp){
 				if(r.sequence >= T.n || r.inner_start < 0 || r.inner_length < 0 || (uint64_t)r.inner_start + (uint64_t)r.inner_length > T.len[r.sequence]){ g_err = "pcr_design: amplicon outside its sequence"; return PCR_ERR_RANGE; }
 				const std::vector<uint8_t> &buf = T.packed[r.sequence];
 				std::vector<uint8_t> codes((size_t)r.inner_length);
@@ -234,35 +306,46 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 			// (an amplicon whose last primer hangs over the end of its sequence -- a partial word matched there -- has `end` at or past
 			// the sequence's length: the reference's split_sequence then writes past the logical end of its buffer, sequence.h:232-241,
 			// which leaves the sequence as it was; here such a split is skipped.  A negative `begin` makes AmpliconBounds throw, assay.h:85.)
+			// (sharded: `amp` holds every rank's amplicons with global indices; a rank splits its own rows, rank 0 its copy too)
 			std::vector<uint32_t> sp_seq; std::vector<uint64_t> sp_pos;
+			const bool copy = sharded && ctx->shard_comm->rank == 0;
 			for(const pcr_amplicon &r : amp){
 				if(r.begin < 0 || r.begin > r.end){ g_err = "AmpliconBounds(): Amplicon begin > amplicon end"; return PCR_ERR_RANGE; }
 				const int64_t at[3] = {r.begin, (int64_t)(((uint32_t)r.begin + (uint32_t)r.end)/2u), r.end};
+				const uint64_t first = sharded ? ctx->shard_first : 0;
+				const bool mine_row = r.sequence >= first && r.sequence - first < T.n;
 				for(int k = 0;k < 3;++k){
-					if((uint64_t)at[k] >= T.len[r.sequence]) continue;
-					sp_seq.push_back(r.sequence); sp_pos.push_back((uint64_t)at[k]);
+					if(copy && r.sequence < n_all && (uint64_t)at[k] < ctx->samp_len[r.sequence]){
+						uint8_t &v = ctx->samp_packed[r.sequence][(size_t)((uint64_t)at[k] >> 1)];
+						v = (at[k] & 1) ? (v & 0xF0) : (v & 0x0F);                                   // sequence.h:232-241
+					}
+					if(!mine_row || (uint64_t)at[k] >= T.len[r.sequence - first]) continue;
+					sp_seq.push_back(r.sequence - (uint32_t)first); sp_pos.push_back((uint64_t)at[k]);
 				}
 			}
-			if((rc = pcr_split_many(ctx, PCR_SET_TARGET, sp_seq.data(), sp_pos.data(), (uint32_t)sp_seq.size())) != PCR_OK) return rc;
+			rc = pcr_split_many(ctx, PCR_SET_TARGET, sp_seq.data(), sp_pos.data(), (uint32_t)sp_seq.size());
+			if(!sharded && rc != PCR_OK) return rc;
+			if(lrc == PCR_OK) lrc = rc;
 		}
 		lap(5);
 		// ---- the detected targets leave the search; the assay joins the pool (main.cpp:1105-1124)
-		{
-			std::vector<uint8_t> act(T.active.begin(), T.active.end());
-			for(uint32_t i = 0;i < T.n;++i){ if((target_match[i/64] >> (i % 64)) & 1u) act[i] = 0; }
-			if((rc = pcr_set_active(ctx, PCR_SET_TARGET, act.data())) != PCR_OK) return rc;
+		for(uint64_t i = 0;i < n_all;++i){ if((target_match[i/64] >> (i % 64)) & 1u) g_active[(size_t)i] = 0; }
+		if(lrc == PCR_OK){
+			rc = set_local_active();
+			if(!sharded && rc != PCR_OK) return rc;
+			lrc = rc;
 		}
 		for(uint64_t w = 0;w < b_words;++w) total_background[w] |= best_background[w];
 		D.pool.push_back(best_assay);
 		lap(6);
-		if(ctx->timing) fprintf(stderr, "[pcramp] design iteration %u ms: sample %.1f  word DBs %.1f  local search %.1f  gates %.1f  best assay %.1f  amplicon DB + splits %.1f  flags %.1f\n",
-			assay_iteration, t_phase[0], t_phase[1], t_phase[2], t_phase[3], t_phase[4], t_phase[5], t_phase[6]);
+		if(ctx->timing) fprintf(stderr, "[pcramp] design iteration %u ms: sample %.1f  word DBs %.1f  local search %.1f  gates %.1f  best assay %.1f  amplicon DB + splits %.1f  flags %.1f  exchanges %.1f\n",
+			assay_iteration, t_phase[0], t_phase[1], t_phase[2], t_phase[3], t_phase[4], t_phase[5], t_phase[6], t_phase[7]);
 		if(assay_iteration >= a->num_assay) break;
 	}
+	if(sharded){ if((rc = shard_agree(ctx, 0ull, lrc, "pcr_design")) != PCR_OK) return rc; }   // (the last iteration's splits and flags)
 	{
-		std::vector<uint8_t> act(T.active.begin(), T.active.end());
 		struct Ft { const pcr_output *o; const uint8_t *act; const uint64_t *bg; };
-		Ft ft = {o, act.data(), B.n ? total_background.data() : nullptr};
+		Ft ft = {o, g_active.data(), B.n ? total_background.data() : nullptr};
 		if((rc = append_text(ctx->design_text, [](char *out, uint64_t cap, void *p) -> int64_t { const Ft *h = (const Ft *)p; return pcr_format_footer(h->o, h->act, h->bg, out, cap); }, &ft)) != PCR_OK) return rc;
 	}
 	if(n_pool_out) *n_pool_out = (uint32_t)D.pool.size();

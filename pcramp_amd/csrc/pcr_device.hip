@@ -755,6 +755,12 @@ struct pcr_ctx {
 	// shard_n_total, and the local search combines target coverage over shard_comm; NULL = not sharded
 	pcr_comm *shard_comm = nullptr; uint64_t shard_first = 0, shard_n_total = 0; int shard_mode = 0;
 	DevBuf<uint64_t> sh_rec, sh_full; DevBuf<uint8_t> sh_stage;   // the combine's record, the gathered records, staging of host collectives on RCCL
+	std::vector<uint64_t> shard_bounds; DevBuf<uint64_t> d_shard_bounds;   // every rank's first row, rank order, and n_total last (world + 1)
+	// the design loop over a shard (pcr_shard_sampler_targets): rank 0's host-only copy of the whole target set for the sampler
+	// (packed 4 bits per base as loaded, EOS splits applied as the loop makes them; empty on the other ranks)
+	bool design_ready = false; DevBuf<uint64_t> sh_bits;   // (and the best assay's local + global bits)
+	std::vector<std::vector<uint8_t> > samp_packed; std::vector<uint64_t> samp_len;
+	void drop_shard(){ shard_comm = nullptr; shard_mode = 0; shard_bounds.clear(); design_ready = false; samp_packed.clear(); samp_len.clear(); }
 	size_t amp_cap = size_t(1) << 20;
 	uint32_t n_cu = 256;        // compute units of the device (hipDeviceProp)
 	DevBuf<uint64_t> fin_scratch;   // k_finalize_big's keys
@@ -1607,7 +1613,7 @@ static int load_sequences_impl(pcr_ctx *ctx, int which, const uint8_t *packed4, 
 	S.n = n;
 	S.packed.assign(n, std::vector<uint8_t>());
 	S.len.assign(lengths, lengths + n);
-	if(which == PCR_SET_TARGET){ ctx->shard_comm = nullptr; ctx->shard_mode = 0; }   // a new target set is not the shard that was attached
+	if(which == PCR_SET_TARGET) ctx->drop_shard();                                  // a new target set is not the shard that was attached
 	S.weight.assign(n, 1.0f);
 	if(weights) S.weight.assign(weights, weights + n);
 	S.weight_dirty = true;

@@ -76,26 +76,9 @@ int pcr_multiplex_screen(pcr_ctx *ctx, const pcr_pair *trial, uint32_t n_trial, 
 	}
 	first[want.size()] = (uint32_t)amp.size();
 	if(amp.empty()) return PCR_OK;
-	std::vector<uint8_t> packed; std::vector<uint64_t> off(amp.size()), len(amp.size());
-	for(size_t i = 0;i < amp.size();++i){
-		off[i] = packed.size(); len[i] = amp[i].size();
-		for(size_t j = 0;j < amp[i].size();j += 2) packed.push_back((uint8_t)((amp[i][j] << 4) | ((j + 1 < amp[i].size()) ? amp[i][j + 1] : 0)));
-	}
-	if((rc = load_sequences_impl(ctx, PCR_SET_SCRATCH, packed.data(), off.data(), len.data(), nullptr, (uint32_t)amp.size())) != PCR_OK) return rc;
-	const uint64_t words = (amp.size() + 63)/64;
-	std::vector<uint64_t> bits((size_t)n_pool*words);
-	if((rc = multiplex_match_impl(ctx, PCR_SET_SCRATCH, pool, n_pool, a->background_threshold, a->use_taq_mama, bits.data())) != PCR_OK) return rc;
-	for(size_t k = 0;k < want.size();++k){
-		// union over the pool (every pool assay sets bits in the same BitSet, main.cpp:792-797); amplicon Sequences carry the
-		// default weight 1 (sequence.h:146), so weighted_coverage is the count -- a float sum of ones, exact
-		double cov = 0.0;
-		for(uint32_t s = first[k];s < first[k + 1];++s){
-			bool hit = false;
-			for(uint32_t i = 0;i < n_pool && !hit;++i) hit = ((bits[(size_t)i*words + s/64] >> (s % 64)) & 1u) != 0;
-			if(hit) cov += 1.0;
-		}
-		pool_cover[want[k]] = (float)cov;
-	}
+	std::vector<float> cover(want.size());
+	if((rc = pool_cover_pass(ctx, amp, first, pool, n_pool, a, cover.data())) != PCR_OK) return rc;
+	for(size_t k = 0;k < want.size();++k) pool_cover[want[k]] = cover[k];
 	return PCR_OK;
 }
 

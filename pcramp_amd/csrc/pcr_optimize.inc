@@ -1059,4 +1059,5 @@ int pcr_optimization_move(pcr_ctx *ctx, const pcr_pair *assay, int move, int sid
 } // extern "C"
 
 #include "pcr_degenerate.inc"
+#include "pcr_shard_design.inc"
 #include "pcr_design.inc"

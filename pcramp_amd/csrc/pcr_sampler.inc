@@ -117,7 +117,11 @@ struct SpecWindow {
 	std::vector<SpecAttempt> spec;
 };
 
-bool build_window(const SeqSet &S, uint32_t si, uint32_t s0, int window, const pcr_sampler_args *o, const pcr_thermo_args *th,
+// What the sampler reads of a sequence set: the packed bytes (as loaded, splits applied), lengths and active flags of n sequences --
+// a loaded SeqSet, or the host-only copy of the whole target set that rank 0 of a sharded design loop samples from.
+struct SampView { const std::vector<uint8_t> *packed; const uint64_t *len; const uint8_t *active; uint32_t n; };
+
+bool build_window(const SampView &S, uint32_t si, uint32_t s0, int window, const pcr_sampler_args *o, const pcr_thermo_args *th,
 	SpecWindow &w, std::vector<thermo::Job> &jobs)
 {
 	w.si = si; w.window = window;
@@ -157,28 +161,21 @@ int walk_window(const SpecWindow &w, const std::vector<thermo::JobOut> &res, con
 	return 0;
 }
 
-} // namespace
+bool sampler_args_ok(const pcr_sampler_args *o)
+{
+	if(o->primer_min < 1 || o->primer_max < o->primer_min || o->primer_max > 32 || o->amp_min < 1 || o->amp_max < o->amp_min){
+		g_err = "pcr_random_assays: bad primer or amplicon range"; return false;
+	}
+	return true;
+}
 
-extern "C" {
-
-uint32_t pcr_host_rand_r(uint32_t *seed) { return pcrhost::rand_r_glibc(seed); }
-
-int pcr_random_assays(pcr_ctx *ctx, pcr_set which, uint32_t *seed, uint32_t n_trials, const pcr_sampler_args *o,
+// pcr_random_assays over a view (the arguments are checked by the caller)
+int random_assays_view(pcr_ctx *ctx, const SampView &S, uint32_t *seed, uint32_t n_trials, const pcr_sampler_args *o,
 	const pcr_thermo_args *th, pcr_pair *pairs_out, pcr_sample_info *info_out)
 {
-	if(!set_ok(which)){ g_err = "pcr_random_assays: unknown sequence set"; return PCR_ERR_ARG; }
-	if(!ctx || !seed || !o || !th || (which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND) || (n_trials && !pairs_out)){
-		g_err = "pcr_random_assays: bad argument"; return PCR_ERR_ARG;
-	}
-	if(o->primer_min < 1 || o->primer_max < o->primer_min || o->primer_max > 32 || o->amp_min < 1 || o->amp_max < o->amp_min){
-		g_err = "pcr_random_assays: bad primer or amplicon range"; return PCR_ERR_ARG;
-	}
-	HIP_TRY(hipSetDevice(ctx->device));
-	const SeqSet &S = ctx->sets[which];
 	std::vector<uint32_t> act;                                                   // pcr_assay.cpp:593-599
 	for(uint32_t i = 0;i < S.n;++i){ if(S.active[i]) act.push_back(i); }
 	if(act.empty()){ g_err = "PCR::random_assay: No active sequences found"; return PCR_ERR_ARG; }
-
 	// Most trials succeed at their first or second attempt, so a launch for one trial is mostly round trip.  A launch
 	// therefore carries a CHAIN of trials: trial k+1 is speculated from the state trial k leaves if its first attempt
 	// succeeds (pick + 4 draws); the chain is used as far as the walk confirms it and rebuilt from the real state
@@ -250,6 +247,26 @@ int pcr_random_assays(pcr_ctx *ctx, pcr_set which, uint32_t *seed, uint32_t n_tr
 		}
 	}
 	return PCR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+uint32_t pcr_host_rand_r(uint32_t *seed) { return pcrhost::rand_r_glibc(seed); }
+
+int pcr_random_assays(pcr_ctx *ctx, pcr_set which, uint32_t *seed, uint32_t n_trials, const pcr_sampler_args *o,
+	const pcr_thermo_args *th, pcr_pair *pairs_out, pcr_sample_info *info_out)
+{
+	if(!set_ok(which)){ g_err = "pcr_random_assays: unknown sequence set"; return PCR_ERR_ARG; }
+	if(!ctx || !seed || !o || !th || (which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND) || (n_trials && !pairs_out)){
+		g_err = "pcr_random_assays: bad argument"; return PCR_ERR_ARG;
+	}
+	if(!sampler_args_ok(o)) return PCR_ERR_ARG;
+	HIP_TRY(hipSetDevice(ctx->device));
+	const SeqSet &S = ctx->sets[which];
+	const SampView v = {S.packed.data(), S.len.data(), S.active.data(), S.n};
+	return random_assays_view(ctx, v, seed, n_trials, o, th, pairs_out, info_out);
 }
 
 } // extern "C"

@@ -258,6 +258,100 @@ void weight_facts(const std::vector<float> &w, AttachRec &a)
 	}
 }
 
+// ---- pcr_shard_gather_bits: rank-local bitsets at arbitrary row boundaries -> bitsets over all n_total rows
+// The record of a rank: [0] status word, [1 + v*pad + k] word k of its bitset v (pad = the largest local word count; words past
+// its own count and every word of a rank that failed are zero).
+__global__ void k_shard_pack(const uint64_t *__restrict__ local, uint64_t local_stride, uint64_t local_words, uint32_t n_vec, uint64_t pad,
+	uint64_t status, uint64_t *__restrict__ rec)
+{
+	const uint64_t i = (uint64_t)blockIdx.x*blockDim.x + threadIdx.x;
+	if(i == 0) rec[0] = status;
+	if(i >= (uint64_t)n_vec*pad) return;
+	const uint64_t v = i/pad, k = i - v*pad;
+	rec[1 + i] = (local && k < local_words) ? local[v*local_stride + k] : 0ull;
+}
+
+// One thread per global output word (consecutive threads: consecutive words of one bitset, so the loads of a rank's words are
+// contiguous too).  bounds[r] = rank r's first row, bounds[world] = n_total.  For every rank whose rows meet the word: the 64
+// local bits that land in it (a funnel shift of two adjacent local words), masked to the part of the word the rank owns.
+// Words at or past n_total are zero.  Thread 0 also ORs the status words into *status_out.
+__global__ void k_shard_stitch(const uint64_t *__restrict__ full, uint64_t rec_words, uint64_t pad, const uint64_t *__restrict__ bounds,
+	uint32_t world, uint32_t n_vec, uint64_t global_stride, uint64_t *__restrict__ global, uint64_t *__restrict__ status_out)
+{
+	const uint64_t i = (uint64_t)blockIdx.x*blockDim.x + threadIdx.x;
+	if(i == 0){
+		uint64_t st = 0;
+		for(uint32_t r = 0;r < world;++r) st |= full[(size_t)r*rec_words];
+		*status_out = st;
+	}
+	if(i >= (uint64_t)n_vec*global_stride) return;
+	const uint64_t v = i/global_stride, gw = i - v*global_stride;
+	const uint64_t base = gw*64, n_total = bounds[world];
+	uint64_t out = 0;
+	for(uint32_t r = 0;r < world && base < n_total;++r){
+		const uint64_t f = bounds[r], e = min(bounds[r + 1], n_total);
+		if(f >= e || e <= base || f >= base + 64) continue;
+		const uint64_t *L = full + (size_t)r*rec_words + 1 + v*pad;
+		const uint64_t nw = (e - f + 63)/64;
+		uint64_t x;
+		if(base >= f){
+			const uint64_t off = base - f, lo = off >> 6;
+			const uint32_t sh = (uint32_t)(off & 63);
+			x = (lo < nw) ? (L[lo] >> sh) : 0ull;
+			if(sh && lo + 1 < nw) x |= L[lo + 1] << (64 - sh);
+		}
+		else x = L[0] << (uint32_t)(f - base);                                      // 1 <= f - base <= 63
+		const uint32_t lo_b = (uint32_t)(f > base ? f - base : 0), hi_b = (uint32_t)min<uint64_t>(64, e - base);
+		const uint32_t width = hi_b - lo_b;
+		const uint64_t m = (width == 64) ? ~0ull : (((1ull << width) - 1ull) << lo_b);
+		out |= x & m;
+	}
+	global[v*global_stride + gw] = out;
+}
+
+// The gather itself (the ranks have agreed on n_vec): d_local = this rank's bitsets (nullptr or local_rc != PCR_OK: it sends
+// zeros with its failure in the status word), d_global = the result (may be nullptr when local_rc != PCR_OK).  Returns the same
+// code on every rank.
+int shard_gather_bits_impl(pcr_ctx *ctx, const uint64_t *d_local, uint32_t n_vec, uint64_t local_stride, uint64_t *d_global,
+	uint64_t global_stride, int local_rc)
+{
+	pcr_comm *c = ctx->shard_comm;
+	const std::vector<uint64_t> &b = ctx->shard_bounds;
+	const uint32_t W = (uint32_t)c->world;
+	uint64_t pad = 0;
+	for(uint32_t r = 0;r < W;++r) pad = std::max<uint64_t>(pad, (b[r + 1] - b[r] + 63)/64);
+	const uint64_t rec_words = 1 + (uint64_t)n_vec*pad;
+	int rc;
+	if((rc = ctx->sh_rec.ensure((size_t)rec_words + 1)) != PCR_OK) return rc;
+	if((rc = ctx->sh_full.ensure((size_t)rec_words*W)) != PCR_OK) return rc;
+	const uint64_t me_words = (b[c->rank + 1] - b[c->rank] + 63)/64;
+	const bool ok = local_rc == PCR_OK;
+	const uint64_t n_pack = (uint64_t)n_vec*pad;
+	hipLaunchKernelGGL(k_shard_pack, dim3((unsigned)std::max<uint64_t>(1, (n_pack + 255)/256)), dim3(256), 0, ctx->stream, ok ? d_local : nullptr,
+		local_stride, me_words, n_vec, pad, ok ? 0ull : sh_fail_bit(local_rc), ctx->sh_rec.p);
+	HIP_TRY(hipGetLastError());
+	if((rc = sh_allgather_rec(ctx, c, ctx->sh_rec.p, rec_words, ctx->sh_full.p)) != PCR_OK) return rc;
+	const uint32_t nv_out = (ok && d_global) ? n_vec : 0u;
+	const uint64_t n_out = (uint64_t)nv_out*global_stride;
+	hipLaunchKernelGGL(k_shard_stitch, dim3((unsigned)std::max<uint64_t>(1, (n_out + 255)/256)), dim3(256), 0, ctx->stream, ctx->sh_full.p, rec_words, pad,
+		ctx->d_shard_bounds.p, W, nv_out, global_stride, d_global, ctx->sh_rec.p + rec_words);
+	HIP_TRY(hipGetLastError());
+	uint64_t st = 0;
+	HIP_TRY(hipMemcpyAsync(&st, ctx->sh_rec.p + rec_words, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	return sh_status_rc(st, local_rc, "pcr_shard_gather_bits");
+}
+
+// a row's bytes as the sampler reads them: the length, then the packed bytes (the pad nibble of an odd length masked)
+uint64_t sh_row_hash(uint64_t h, const uint8_t *bytes, uint64_t len)
+{
+	h = sh_hash(h, &len, sizeof(len));
+	const uint64_t nb = (len + 1)/2;
+	if(nb > 1) h = sh_hash(h, bytes, (size_t)nb - 1);
+	if(nb){ const uint8_t last = (len & 1) ? (uint8_t)(bytes[nb - 1] & 0xF0) : bytes[nb - 1]; h = sh_hash(h, &last, 1); }
+	return h;
+}
+
 } // namespace
 
 extern "C" {
@@ -265,9 +359,9 @@ extern "C" {
 int pcr_shard_targets(pcr_ctx *ctx, pcr_comm *comm, uint64_t first_seq, uint64_t n_total)
 {
 	if(!ctx){ g_err = "pcr_shard_targets: bad argument"; return PCR_ERR_ARG; }
-	if(!comm){ ctx->shard_comm = nullptr; ctx->shard_mode = 0; return PCR_OK; }
+	if(!comm){ ctx->drop_shard(); return PCR_OK; }
 	if(!comm->host_fn && comm->device != ctx->device){ g_err = "pcr_shard_targets: the communicator belongs to another device"; return PCR_ERR_ARG; }
-	ctx->shard_comm = nullptr; ctx->shard_mode = 0;
+	ctx->drop_shard();
 	const SeqSet &S = ctx->sets[PCR_SET_TARGET];
 	AttachRec me;
 	memset(&me, 0, sizeof(me));
@@ -301,8 +395,83 @@ int pcr_shard_targets(pcr_ctx *ctx, pcr_comm *comm, uint64_t first_seq, uint64_t
 	// exact partials: every weight is a multiple of 2^q and every partial sum is at most n_total * max|w| in magnitude; below
 	// 2^52 * 2^q (one bit of margin for the rounding of the product) it is an integer multiple of 2^q with at most 52 bits: exact
 	const bool exact = !nonfinite && (maxabs == 0.0 || (double)n_total*maxabs <= std::ldexp(1.0, (int)std::max<int64_t>(-1074, 52 + q)));
+	ctx->shard_bounds.resize(all.size() + 1);
+	for(size_t r = 0;r < all.size();++r) ctx->shard_bounds[r] = all[r].first;
+	ctx->shard_bounds[all.size()] = n_total;
+	if((rc = ctx->d_shard_bounds.ensure(ctx->shard_bounds.size())) != PCR_OK){ ctx->shard_bounds.clear(); return rc; }
+	HIP_TRY(hipMemcpy(ctx->d_shard_bounds.p, ctx->shard_bounds.data(), ctx->shard_bounds.size()*sizeof(uint64_t), hipMemcpyHostToDevice));
 	ctx->shard_comm = comm; ctx->shard_first = first_seq; ctx->shard_n_total = n_total;
 	ctx->shard_mode = (want_mode == 1 && exact) ? 1 : 2;
+	return PCR_OK;
+}
+
+int pcr_shard_gather_bits(pcr_ctx *ctx, const uint64_t *d_local, uint32_t n_vec, uint64_t local_stride_words, uint64_t *d_global,
+	uint64_t global_stride_words)
+{
+	if(!ctx){ g_err = "pcr_shard_gather_bits: bad argument"; return PCR_ERR_ARG; }
+	if(!ctx->shard_comm){ g_err = "pcr_shard_gather_bits: no target shard is attached (pcr_shard_targets)"; return PCR_ERR_STATE; }
+	int local_rc = enter_device(ctx);
+	const uint64_t n_me = ctx->sets[PCR_SET_TARGET].n;
+	if(local_rc == PCR_OK && n_vec && (!d_local || !d_global || local_stride_words < (n_me + 63)/64 || global_stride_words < (ctx->shard_n_total + 63)/64)){
+		g_err = "pcr_shard_gather_bits: bad argument (null buffer or a stride below the bitset's word count)"; local_rc = PCR_ERR_ARG;
+	}
+	// the record size depends on n_vec: the ranks agree on it first
+	const int rc = shard_agree(ctx, sh_hash(SH_HASH0, &n_vec, sizeof(n_vec)), local_rc, "pcr_shard_gather_bits");
+	if(rc != PCR_OK) return rc;
+	if(n_vec == 0) return PCR_OK;
+	return shard_gather_bits_impl(ctx, d_local, n_vec, local_stride_words, d_global, global_stride_words, PCR_OK);
+}
+
+int pcr_shard_sampler_targets(pcr_ctx *ctx, const uint8_t *packed4, const uint64_t *byte_offsets, const uint64_t *lengths, uint64_t n)
+{
+	if(!ctx){ g_err = "pcr_shard_sampler_targets: bad argument"; return PCR_ERR_ARG; }
+	pcr_comm *c = ctx->shard_comm;
+	if(!c){ g_err = "pcr_shard_sampler_targets: no target shard is attached (pcr_shard_targets)"; return PCR_ERR_STATE; }
+	ctx->design_ready = false; ctx->samp_packed.clear(); ctx->samp_len.clear();
+	const uint32_t W = (uint32_t)c->world;
+	const std::vector<uint64_t> &b = ctx->shard_bounds;
+	int local_rc = enter_device(ctx);
+	// this rank's record: status, the n it was given, the hash of its own rows, and (rank 0) the hashes of its copy's slices
+	std::vector<uint64_t> me(3 + W, 0);
+	std::vector<std::vector<uint8_t> > copy;
+	std::vector<uint64_t> copy_len;
+	if(local_rc == PCR_OK){
+		if(c->rank == 0 && (n != ctx->shard_n_total || (n && (!packed4 || !byte_offsets || !lengths)))){
+			g_err = "pcr_shard_sampler_targets: rank 0 must pass the whole target set (n == n_total)"; local_rc = PCR_ERR_ARG;
+		}
+		else if(c->rank != 0 && (n != 0 || packed4 || byte_offsets || lengths)){
+			g_err = "pcr_shard_sampler_targets: only rank 0 passes the target set (n = 0 and null pointers elsewhere)"; local_rc = PCR_ERR_ARG;
+		}
+	}
+	if(local_rc == PCR_OK && c->rank == 0){
+		copy.resize((size_t)n); copy_len.assign(lengths, lengths + n);
+		for(uint64_t i = 0;i < n;++i) copy[i].assign(packed4 + byte_offsets[i], packed4 + byte_offsets[i] + (lengths[i] + 1)/2);
+		for(uint32_t r = 0;r < W;++r){
+			uint64_t h = SH_HASH0;
+			for(uint64_t i = b[r];i < b[r + 1];++i) h = sh_row_hash(h, copy[i].data(), copy_len[i]);
+			me[3 + r] = h;
+		}
+	}
+	if(local_rc == PCR_OK){
+		const SeqSet &T = ctx->sets[PCR_SET_TARGET];
+		uint64_t h = SH_HASH0;
+		for(uint32_t i = 0;i < T.n;++i) h = sh_row_hash(h, T.packed[i].data(), T.len[i]);
+		me[1] = n; me[2] = h;
+	}
+	me[0] = local_rc != PCR_OK ? sh_fail_bit(local_rc) : 0ull;
+	std::vector<uint64_t> all(me.size()*W);
+	const int rc = sh_allgather_host(ctx, c, me.data(), me.size()*sizeof(uint64_t), all.data());
+	if(rc != PCR_OK) return rc;
+	uint64_t st = 0;
+	for(uint32_t r = 0;r < W;++r) st |= all[(size_t)r*me.size()];
+	if(st) return sh_status_rc(st, local_rc, "pcr_shard_sampler_targets");
+	for(uint32_t r = 0;r < W;++r){
+		if(all[3 + r] != all[(size_t)r*me.size() + 2]){
+			g_err = "pcr_shard_sampler_targets: rank 0's copy differs from the rows of rank " + std::to_string(r); return PCR_ERR_ARG;
+		}
+	}
+	ctx->samp_packed.swap(copy); ctx->samp_len.swap(copy_len);
+	ctx->design_ready = true;
 	return PCR_OK;
 }
 

@@ -91,6 +91,8 @@ def design(scr, target_deflines, target_lengths, background_deflines=(), backgro
     ptr = L.pcr_design_output(scr.h, C.byref(n))
     text = C.string_at(ptr, n.value) if ptr else b""
     if rc != 0:
-        raise api.PcrError("pcr_design: %s (output so far: %d bytes)" % (api._err(L), len(text)))
+        e = api.PcrError("pcr_design: %s (output so far: %d bytes)" % (api._err(L), len(text)))
+        e.rc = rc
+        raise e
     pairs = [((int(r[0]), int(r[1])), (int(r[2]), int(r[3]))) for r in pool[:n_pool.value]]
     return text, pairs
