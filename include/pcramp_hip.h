@@ -259,6 +259,32 @@ int pcr_shard_gather_bits(pcr_ctx *ctx, const uint64_t *d_local, uint32_t n_vec,
  * the target set drops the copy and the design-ready flag. */
 int pcr_shard_sampler_targets(pcr_ctx *ctx, const uint8_t *packed4, const uint64_t *byte_offsets, const uint64_t *lengths, uint64_t n);
 
+/* ---- the design loop in the reference's MPI mode: trials split across ranks (pcr_trial_ranks.inc)
+ * pcr_design_trial_ranks: attaches comm (RCCL, pcr_comm_init_rank, or a host all-gather, pcr_comm_init_host).  Every rank has
+ * loaded the same TARGET and BACKGROUND sets.  Collective: one all-gather checks count, lengths, a hash of the packed bytes (EOS
+ * splits included), weights and active flags of both sets; a mismatch gives PCR_ERR_ARG on every rank.  With a target shard
+ * attached it returns PCR_ERR_STATE at once (and pcr_shard_targets returns PCR_ERR_STATE while trial ranks are attached): the two
+ * modes do not combine.  comm = NULL detaches (not collective); reloading either set detaches too; the communicator must outlive
+ * the attachment.  While attached, pcr_design is collective and runs as `mpirun -np W pcramp` does (main.cpp:60-113, :926-932,
+ * :1420-1601):
+ *   - on entry the ranks agree on the arguments, command line, pcr_output sizes and the sets' state (PCR_ERR_ARG on every rank
+ *     when they differ);
+ *   - args->num_trial is the trials of THIS rank (the caller divides as main.cpp:65 does: max(1, ceil(num_trial / W))); the
+ *     sampler's running seed starts at args->seed + rank (unsigned wrap); the header still prints args->seed;
+ *   - every rank runs the one-rank iteration over its own trials; after the walk, and before the `target coverage <= 0` stop, one
+ *     all-gather of a fixed-size record per rank (status, Score, assay, background bits) reduces the ranks' best assays: rank 0's
+ *     is the starting best, then in ascending rank order a record replaces it iff it scores higher, or ties with a lower
+ *     total degeneracy (the reference's root takes the ranks in arrival order);
+ *   - the winner's target bits and amplicons depend on the word DB only the winning rank built, so that rank computes them and a
+ *     second exchange ships them (as the reference does); the rest of the iteration (record text, multiplex set, EOS splits, active
+ *     flags, pool) is the one-rank code on every rank.
+ * Every rank leaves the output file the reference's root writes and the same pool.  Any rank's failure (the sampler's throws
+ * included) is returned as the same code by every rank; no rank leaves a collective out.  PCRAMP_TIMING=1 reports the exchanges
+ * as "reduction".  Without an attachment pcr_design is unchanged.
+ * pcr_design_trial_world: the attached world size, 0 when nothing is attached. */
+int pcr_design_trial_ranks(pcr_ctx *ctx, pcr_comm *comm);
+int pcr_design_trial_world(pcr_ctx *ctx);
+
 
 /* ---- Smith-Waterman primer x template alignment (rows a7/a8 of the scope table) */
 
@@ -547,7 +573,8 @@ int64_t pcr_format_footer(const pcr_output *o, const uint8_t *target_active, con
 	char *out, uint64_t cap);
 
 /* ---- The design loop over all of the above (scope row f-7): what `pcramp` does between reading its FASTA files and closing
- * its output file (main.cpp:131-163, 440-443, 471-1264), one rank, one thread. */
+ * its output file (main.cpp:131-163, 440-443, 471-1264), one rank, one thread; over a target shard (pcr_shard_targets) the same
+ * file, and with trial ranks attached (pcr_design_trial_ranks) the file of the reference's MPI mode at that world size. */
 
 /* The `Options` fields that loop reads (pcramp.h:83-128; the pack filters are pcr_create's, sequences, weights and deflines
  * are the loaded sets' and pcr_output's). */

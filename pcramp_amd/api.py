@@ -118,7 +118,7 @@ ABI_SYMBOLS = [
     "pcr_format_oligos", "pcr_format_header", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
-    "pcr_shard_gather_bits", "pcr_shard_sampler_targets",
+    "pcr_shard_gather_bits", "pcr_shard_sampler_targets", "pcr_design_trial_ranks", "pcr_design_trial_world",
     "pcr_comm_unique_id", "pcr_comm_init_rank", "pcr_comm_world", "pcr_comm_rank", "pcr_exchange_bits", "pcr_comm_destroy", "pcr_comm_library",
 ]
 
@@ -187,6 +187,8 @@ def load_library():
     L.pcr_shard_combine_mode.argtypes = [C.c_void_p]
     L.pcr_shard_gather_bits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64]
     L.pcr_shard_sampler_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.pcr_design_trial_ranks.argtypes = [C.c_void_p, C.c_void_p]
+    L.pcr_design_trial_world.argtypes = [C.c_void_p]
     L.pcr_sw_align_words.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.pcr_background_match.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(BackgroundArgs), C.c_void_p]
     L.pcr_multiplex_match.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_void_p]
@@ -834,6 +836,15 @@ class Screener:
         bo = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
         ln = np.ascontiguousarray(lengths, dtype=np.uint64)
         self._check(self.L.pcr_shard_sampler_targets(self.h, packed.ctypes.data, bo.ctypes.data, ln.ctypes.data, ln.size))
+
+    def design_trial_ranks(self, comm):
+        """Collective (pcr_design_trial_ranks): pcr_design runs in the reference's MPI mode over comm -- every rank holds the
+        same whole sets and designs with its own trials, the ranks' best assays reduced each iteration.  None detaches."""
+        self._check(self.L.pcr_design_trial_ranks(self.h, comm))
+
+    def design_trial_world(self):
+        """The world size of the attached trial ranks, 0 when none are attached."""
+        return int(self.L.pcr_design_trial_world(self.h))
 
     def staging_mode(self):
         """'lean' (the CPU stores the per-pass tables straight into device memory, no staging launch) or 'k_stage'."""

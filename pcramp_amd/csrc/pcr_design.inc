@@ -15,6 +15,11 @@
 // (pcr_shard_design.inc); the local search and the top-down start combine on their own.  Steps over data every rank holds
 // whole (backgrounds, the multiplex set, the pool) compute the same on every rank; a failure in a step over local rows is kept
 // in `lrc` and travels in the status word of the next exchange, so that every rank returns the same code.
+//
+// With trial ranks attached (pcr_design_trial_ranks, the reference's MPI mode) every rank holds the whole sets and runs the loop
+// as one rank does, on its own trials from the seed `seed + rank`; after the walk the ranks' best assays are reduced to one
+// winner (pcr_trial_ranks.inc), whose target bits and amplicons the winning rank sends; the rest of the iteration is the one-rank
+// code on every rank.  Here too a local failure is kept in `lrc` and travels in the status word of the next exchange.
 
 namespace {
 
@@ -40,6 +45,57 @@ inline int append_text(std::string &text, int64_t (*fn)(char *, uint64_t, void *
 	return PCR_OK;
 }
 
+// Trial ranks: the winner's target bits and amplicons, from the winning rank to every rank.  They depend on the word DB of the
+// iteration, which only the winning rank built from its own trials (main.cpp:906-908), so they are computed there and shipped, as
+// the reference ships them (:1421-1601).  The winning rank's record: its t_words bitset words, then per amplicon the pcr_amplicon
+// (3 u64) and its inner stretch 8 codes per u64; every other rank sends nothing.  Returns the same code on every rank.
+int trial_share_winner(pcr_ctx *ctx, size_t win, const pcr_pair *best, const pcr_amplify_args *find_args, bool use_multiplex,
+	uint64_t t_words, std::vector<uint64_t> &target_match, std::vector<pcr_amplicon> &amp, std::vector<std::vector<uint8_t> > &codes_all)
+{
+	const SeqSet &T = ctx->sets[PCR_SET_TARGET];
+	std::vector<uint64_t> words;
+	int local_rc = PCR_OK;
+	if((size_t)ctx->trial_comm->rank == win){
+		words.assign((size_t)t_words, 0);
+		local_rc = pcr_amplify(ctx, PCR_SET_TARGET, best, 1, find_args, words.data(), nullptr, nullptr, nullptr);
+		std::vector<pcr_amplicon> mine;
+		if(local_rc == PCR_OK && use_multiplex) local_rc = collect_amps(ctx, best, find_args->ident_threshold, find_args->amp_min, find_args->amp_max, mine);
+		std::vector<uint8_t> codes;
+		for(size_t i = 0;i < mine.size() && local_rc == PCR_OK;++i){
+			if((local_rc = amp_codes(T, mine[i], codes)) != PCR_OK) break;
+			const size_t at = words.size();
+			words.resize(at + 3 + (codes.size() + 7)/8, 0);
+			memcpy(&words[at], &mine[i], sizeof(pcr_amplicon));
+			if(!codes.empty()) memcpy(&words[at + 3], codes.data(), codes.size());
+		}
+		if(local_rc != PCR_OK) words.clear();
+	}
+	std::vector<uint64_t> all; std::vector<size_t> first;
+	const int rc = sh_gather_var(ctx, local_rc, words, all, first, ctx->trial_comm);
+	if(rc != PCR_OK) return rc;
+	const size_t lo = first[win], hi = first[win + 1];
+	if(hi - lo < t_words){ g_err = "pcr_design: a malformed winner record"; return PCR_ERR_STATE; }
+	target_match.assign(all.begin() + lo, all.begin() + lo + t_words);
+	amp.clear(); codes_all.clear();
+	for(size_t at = lo + t_words;at < hi;){
+		pcr_amplicon g;
+		if(at + 3 > hi){ g_err = "pcr_design: a malformed winner record"; return PCR_ERR_STATE; }
+		memcpy(&g, &all[at], sizeof(g));
+		if(g.inner_length < 0 || at + 3 + ((size_t)g.inner_length + 7)/8 > hi){ g_err = "pcr_design: a malformed winner record"; return PCR_ERR_STATE; }
+		const uint8_t *p = (const uint8_t *)&all[at + 3];
+		amp.push_back(g);
+		codes_all.emplace_back(p, p + g.inner_length);
+		at += 3 + ((size_t)g.inner_length + 7)/8;
+	}
+	return PCR_OK;
+}
+
+// PCR::total_degeneracy (assay.h:536-539)
+inline double total_degeneracy(const pcr_pair &p)
+{
+	return pcrhost::planes_degeneracy(pcrhost::planes_of_word(p.f.w)) + pcrhost::planes_degeneracy(pcrhost::planes_of_word(p.r.w));
+}
+
 } // namespace
 
 extern "C" {
@@ -50,13 +106,15 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 	if(!ctx || !a || !o || argc < 0 || (argc && !argv) || (pool_cap && !pool_out)){ g_err = "pcr_design: bad argument"; return PCR_ERR_ARG; }
 	if(ctx->shard_comm && !ctx->design_ready){ g_err = "pcr_design: a target shard is attached (pcr_shard_targets) but the handle is not design-ready (pcr_shard_sampler_targets)"; return PCR_ERR_STATE; }
 	const bool sharded = ctx->shard_comm != nullptr;
+	pcr_comm *const ranks = sharded ? nullptr : ctx->trial_comm;                              // the reference's MPI mode
+	const bool ranked = ranks != nullptr, carry = sharded || ranked;                          // carry: a local failure waits for the next collective
 	SeqSet &T = ctx->sets[PCR_SET_TARGET], &B = ctx->sets[PCR_SET_BACKGROUND];
 	const uint64_t n_all = sharded ? ctx->shard_n_total : T.n;                                // the targets the loop designs over
 	int lrc = PCR_OK;                                                                          // this rank's outcome since the last exchange
 	if(n_all == 0){ g_err = "pcr_design: no target sequences loaded"; lrc = PCR_ERR_STATE; }
 	else if(o->n_target != n_all || o->n_background != B.n){ g_err = "pcr_design: the output description does not match the loaded sets"; lrc = PCR_ERR_ARG; }
 	else if(a->num_trial == 0 || a->num_trial > (1u << 20)){ g_err = "pcr_design: num_trial out of range"; lrc = PCR_ERR_ARG; }
-	if(!sharded && lrc != PCR_OK) return lrc;
+	if(!carry && lrc != PCR_OK) return lrc;
 	int rc;
 	std::vector<float> g_weight; std::vector<uint8_t> g_active;                                // all n_all targets, global index order
 	auto now_ms = [](){ return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -66,6 +124,16 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 		if(lrc == PCR_OK) lrc = enter_device(ctx);
 		if((rc = shard_agree(ctx, lrc == PCR_OK ? design_fingerprint(a, n_all, o, argc, argv) : 0ull, lrc, "pcr_design")) != PCR_OK) return rc;
 		if((rc = shard_gather_rows(ctx, PCR_OK, g_weight, g_active)) != PCR_OK) return rc;
+		t_exchange += now_ms() - t0;
+	}
+	else if(ranked){
+		// the same call on every rank, over the same sets as they stand now
+		const double t0 = now_ms();
+		if(lrc == PCR_OK) lrc = enter_device(ctx);
+		uint64_t fp = 0;
+		if(lrc == PCR_OK){ const uint64_t hs = trial_sets_hash(ctx); fp = design_fingerprint(a, n_all, o, argc, argv); fp = sh_hash(fp, &hs, sizeof(hs)); }
+		if((rc = shard_agree(ctx, fp, lrc, "pcr_design", ranks)) != PCR_OK) return rc;
+		g_weight = T.weight; g_active = T.active;
 		t_exchange += now_ms() - t0;
 	}
 	else{
@@ -108,7 +176,7 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 	Hdr hdr = {o, argc, argv, a->seed};
 	if((rc = append_text(ctx->design_text, [](char *out, uint64_t cap, void *p) -> int64_t { const Hdr *h = (const Hdr *)p; return pcr_format_header(h->o, h->argc, h->argv, h->seed, out, cap); }, &hdr)) != PCR_OK) return rc;
 
-	uint32_t global_seed = a->seed;
+	uint32_t global_seed = a->seed + (ranked ? (uint32_t)ranks->rank : 0u);                  // main.cpp:99-113: every task's seed is seed + rank
 	uint32_t assay_iteration = 0, major_id = 1, minor_id = 1;
 	const uint64_t t_words = (T.n + 63)/64, g_words = (n_all + 63)/64, b_words = (B.n + 63)/64;
 	std::vector<uint64_t> total_background(std::max<uint64_t>(b_words, 1), 0);
@@ -124,13 +192,20 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 		if(targets_remaining == 0){                                                             // main.cpp:488-502
 			std::fill(g_active.begin(), g_active.end(), (uint8_t)1);
 			rc = set_local_active();
-			if(!sharded && rc != PCR_OK) return rc;
+			if(!carry && rc != PCR_OK) return rc;
 			if(lrc == PCR_OK) lrc = rc;
 			targets_remaining = (uint32_t)n_all; ++major_id; minor_id = 1;
 		}
 		struct It { const pcr_output *o; uint32_t it, major, minor, remaining; };
 		It itr = {o, assay_iteration, major_id, minor_id, targets_remaining};
 		if((rc = append_text(ctx->design_text, [](char *out, uint64_t cap, void *p) -> int64_t { const It *h = (const It *)p; return pcr_format_iteration(h->o, h->it, h->major, h->minor, h->remaining, out, cap); }, &itr)) != PCR_OK) return rc;
+		// ---- this rank's walk: the trials, their local search and the gates; its best assay
+		ScoreH best_score = EMPTY_SCORE;
+		pcr_pair best_assay; memset(&best_assay, 0, sizeof(best_assay));
+		std::vector<uint64_t> best_background(std::max<uint64_t>(b_words, 1), 0);
+		uint32_t num_active_background = 0, num_active_target = 0;
+		float active_background_norm = 0.0f, active_target_norm = 0.0f;
+		auto walk = [&]() -> int {
 		// ---- the trial assays (main.cpp:538-550, one thread: one local seed per iteration)
 		uint32_t local_seed = pcr_host_rand_r(&global_seed);
 		std::vector<pcr_pair> trial(n_trial);
@@ -147,13 +222,11 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 		}
 		lap(0);
 		// ---- the word DBs for them (main.cpp:579-615, :644-691)
-		uint32_t num_active_background = 0, num_active_target = 0;
-		float active_background_norm = 0.0f;
 		if(B.n > 0){
 			active_background_norm = active_norm(B.weight, B.active, num_active_background);
 			if((rc = pcr_select_words(ctx, PCR_SET_BACKGROUND, trial.data(), n_trial, a->optimize_5, a->optimize_3, oa.background.collect_threshold, min_len_bg, nullptr)) != PCR_OK) return rc;
 		}
-		const float active_target_norm = active_norm(g_weight, g_active, num_active_target);
+		active_target_norm = active_norm(g_weight, g_active, num_active_target);
 		rc = pcr_select_words(ctx, PCR_SET_TARGET, trial.data(), n_trial, a->optimize_5, a->optimize_3, oa.target.collect_threshold, min_len, nullptr);
 		if(!sharded && rc != PCR_OK) return rc;
 		lap(1);
@@ -191,9 +264,7 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 		// ---- the walk over the trials in their order (main.cpp:743-866).  The alignment-based covers are asked for only where the
 		// reference computes them -- for a trial that beats the running best, i.e. at the record highs of the sequence of scores, a
 		// handful per iteration -- one trial per call.
-		ScoreH best_score = EMPTY_SCORE;
-		pcr_pair best_assay; memset(&best_assay, 0, sizeof(best_assay));
-		std::vector<uint64_t> best_background(std::max<uint64_t>(b_words, 1), 0), bits(std::max<uint64_t>(b_words, 1), 0);
+		std::vector<uint64_t> bits(std::max<uint64_t>(b_words, 1), 0);
 		for(size_t g = 0;g < gate.size();++g){
 			const size_t k = gate[g];
 			ScoreH s = {sc[3*k], 0.0f, sc[3*k + 2]};                                             // "Recompute the background coverage" (:744)
@@ -215,8 +286,7 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 					if(s.bc <= a->max_background_cover) s.bc += pc1;                               // :783-803
 				}
 			}
-			const double deg_best = pcrhost::planes_degeneracy(pcrhost::planes_of_word(best_assay.f.w)) + pcrhost::planes_degeneracy(pcrhost::planes_of_word(best_assay.r.w));
-			const double deg_trial = pcrhost::planes_degeneracy(pcrhost::planes_of_word(gp[g].f.w)) + pcrhost::planes_degeneracy(pcrhost::planes_of_word(gp[g].r.w));   // total_degeneracy, assay.h:536-539
+			const double deg_best = total_degeneracy(best_assay), deg_trial = total_degeneracy(gp[g]);
 			if(num_active_background > 0){
 				if(score_lt(best_score, s) && s.bc <= a->max_background_cover){                    // :815-816
 					if((rc = pcr_background_match(ctx, PCR_SET_BACKGROUND, &gp[g], 1, &ba, bits.data())) != PCR_OK) return rc;
@@ -230,15 +300,47 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 				if(update_best){ best_score = s; best_assay = gp[g]; }
 			}
 		}
+		return PCR_OK;
+		};
+		if(!ranked){ if((rc = walk()) != PCR_OK) return rc; }
+		else if(lrc == PCR_OK) lrc = walk();
 		lap(3);
+		size_t win = 0;                                                                         // trial ranks: the winning rank
+		if(ranked){
+			// reduce_best_assay (main.cpp:1421-1601), before the test below as the reference does (:926-932): rank 0's best is the
+			// starting best; in ascending rank order a record replaces it iff it scores higher or ties with a lower degeneracy
+			// (:1432-1480; the reference's root takes the ranks in arrival order, DESIGN.md section 5)
+			const float mine[3] = {best_score.tc, best_score.bc, best_score.ov};
+			std::vector<uint64_t> recs; std::vector<TrialBest> all;
+			if((rc = trial_gather_best(ctx, lrc, mine, best_assay, best_background, b_words, recs, all)) != PCR_OK) return rc;
+			for(size_t r = 1;r < all.size();++r){
+				const ScoreH sw = {all[win].tc, all[win].bc, all[win].ov}, sr = {all[r].tc, all[r].bc, all[r].ov};
+				if(score_lt(sw, sr) || (score_eq(sw, sr) && total_degeneracy(all[win].assay) > total_degeneracy(all[r].assay))) win = r;
+			}
+			if(ctx->debug_log){
+				for(size_t r = 0;r < all.size();++r) fprintf(stderr, "[pcramp] design iteration %u, rank %zu of %d: best %g %g %g, degeneracy %g%s\n", assay_iteration, r,
+					ranks->world, all[r].tc, all[r].bc, all[r].ov, total_degeneracy(all[r].assay), r == win ? " (the winner)" : "");
+			}
+			best_score = {all[win].tc, all[win].bc, all[win].ov};
+			best_assay = all[win].assay;
+			std::copy(all[win].background, all[win].background + b_words, best_background.begin());
+			lap(7);
+		}
 		if(best_score.tc <= 0.0f) break;                                                        // :926-930: nothing detects a target
+		auto apply = [&]() -> int {
 		// ---- the best assay: the targets it detects, its amplicons (main.cpp:898-922)
 		std::vector<uint64_t> target_match(t_words, 0);
-		rc = pcr_amplify(ctx, PCR_SET_TARGET, &best_assay, 1, &find_args, target_match.data(), nullptr, nullptr, nullptr);
+		rc = ranked ? PCR_OK : pcr_amplify(ctx, PCR_SET_TARGET, &best_assay, 1, &find_args, target_match.data(), nullptr, nullptr, nullptr);
 		if(!sharded && rc != PCR_OK) return rc;
 		std::vector<pcr_amplicon> amp;
-		std::vector<std::vector<uint8_t> > amp_codes_all;                                      // sharded: the inner stretches of `amp`
-		if(sharded){
+		std::vector<std::vector<uint8_t> > amp_codes_all;                                      // sharded, trial ranks: the inner stretches of `amp`
+		if(ranked){
+			// from the winning rank, whose word DB found them
+			lap(4);
+			if((rc = trial_share_winner(ctx, win, &best_assay, &find_args, a->use_multiplex != 0, t_words, target_match, amp, amp_codes_all)) != PCR_OK) return rc;
+			lap(7);
+		}
+		else if(sharded){
 			// the bits over all targets; then the amplicons over all targets, records with global sequence indices
 			lrc = rc;
 			lap(4);
@@ -277,7 +379,7 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 		// ---- the multiplex background grows by the assay's unique amplicons; the targets are split (main.cpp:989-1017)
 		if(a->use_multiplex){
 			std::vector<std::vector<uint8_t> > mine;
-			if(sharded) mine.swap(amp_codes_all);
+			if(sharded || ranked) mine.swap(amp_codes_all);
 			else for(const pcr_amplicon &r : amp){
 				if(r.sequence >= T.n || r.inner_start < 0 || r.inner_length < 0 || (uint64_t)r.inner_start + (uint64_t)r.inner_length > T.len[r.sequence]){ g_err = "pcr_design: amplicon outside its sequence"; return PCR_ERR_RANGE; }
 				const std::vector<uint8_t> &buf = T.packed[r.sequence];
@@ -338,11 +440,15 @@ int pcr_design(pcr_ctx *ctx, const pcr_design_args *a, const pcr_output *o, int 
 		for(uint64_t w = 0;w < b_words;++w) total_background[w] |= best_background[w];
 		D.pool.push_back(best_assay);
 		lap(6);
-		if(ctx->timing) fprintf(stderr, "[pcramp] design iteration %u ms: sample %.1f  word DBs %.1f  local search %.1f  gates %.1f  best assay %.1f  amplicon DB + splits %.1f  flags %.1f  exchanges %.1f\n",
-			assay_iteration, t_phase[0], t_phase[1], t_phase[2], t_phase[3], t_phase[4], t_phase[5], t_phase[6], t_phase[7]);
+		return PCR_OK;
+		};
+		if(!ranked){ if((rc = apply()) != PCR_OK) return rc; }
+		else lrc = apply();                                                                     // (lrc was PCR_OK: the reduction agreed)
+		if(ctx->timing) fprintf(stderr, "[pcramp] design iteration %u ms: sample %.1f  word DBs %.1f  local search %.1f  gates %.1f  best assay %.1f  amplicon DB + splits %.1f  flags %.1f  %s %.1f\n",
+			assay_iteration, t_phase[0], t_phase[1], t_phase[2], t_phase[3], t_phase[4], t_phase[5], t_phase[6], ranked ? "reduction" : "exchanges", t_phase[7]);
 		if(assay_iteration >= a->num_assay) break;
 	}
-	if(sharded){ if((rc = shard_agree(ctx, 0ull, lrc, "pcr_design")) != PCR_OK) return rc; }   // (the last iteration's splits and flags)
+	if(carry){ if((rc = shard_agree(ctx, 0ull, lrc, "pcr_design", ranks)) != PCR_OK) return rc; }   // (the last iteration's splits and flags)
 	{
 		struct Ft { const pcr_output *o; const uint8_t *act; const uint64_t *bg; };
 		Ft ft = {o, g_active.data(), B.n ? total_background.data() : nullptr};

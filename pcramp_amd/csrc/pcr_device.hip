@@ -761,6 +761,9 @@ struct pcr_ctx {
 	bool design_ready = false; DevBuf<uint64_t> sh_bits;   // (and the best assay's local + global bits)
 	std::vector<std::vector<uint8_t> > samp_packed; std::vector<uint64_t> samp_len;
 	void drop_shard(){ shard_comm = nullptr; shard_mode = 0; shard_bounds.clear(); design_ready = false; samp_packed.clear(); samp_len.clear(); }
+	// the reference's MPI mode (pcr_design_trial_ranks, pcr_trial_ranks.inc): every rank holds the whole sets, pcr_design samples
+	// this rank's trials and reduces the ranks' best assays over trial_comm; NULL = not attached
+	pcr_comm *trial_comm = nullptr;
 	size_t amp_cap = size_t(1) << 20;
 	uint32_t n_cu = 256;        // compute units of the device (hipDeviceProp)
 	DevBuf<uint64_t> fin_scratch;   // k_finalize_big's keys
@@ -1614,6 +1617,7 @@ static int load_sequences_impl(pcr_ctx *ctx, int which, const uint8_t *packed4, 
 	S.packed.assign(n, std::vector<uint8_t>());
 	S.len.assign(lengths, lengths + n);
 	if(which == PCR_SET_TARGET) ctx->drop_shard();                                  // a new target set is not the shard that was attached
+	if(which == PCR_SET_TARGET || which == PCR_SET_BACKGROUND) ctx->trial_comm = nullptr;   // nor are new sets the ones the ranks agreed on
 	S.weight.assign(n, 1.0f);
 	if(weights) S.weight.assign(weights, weights + n);
 	S.weight_dirty = true;
@@ -2946,6 +2950,7 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 
 #include "pcr_exchange.inc"
 #include "pcr_shard.inc"
+#include "pcr_trial_ranks.inc"
 #include "pcr_entry_sw_thermo.inc"
 #include "pcr_multiplex_screen.inc"
 #include "pcr_writers.inc"

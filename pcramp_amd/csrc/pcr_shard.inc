@@ -130,11 +130,11 @@ int sh_allgather_rec(pcr_ctx *ctx, pcr_comm *c, const uint64_t *d_rec, uint64_t 
 }
 
 // ---- agreement steps
-// On entry to a sharded entry point: every rank's status and fingerprint of the call.  Returns the same code on every rank:
-// a local failure anywhere, or PCR_ERR_ARG when the fingerprints differ.
-int shard_agree(pcr_ctx *ctx, uint64_t fingerprint, int local_rc, const char *what)
+// On entry to a sharded entry point: every rank's status and fingerprint of the call, over `c` (nullptr: the attached shard's
+// communicator).  Returns the same code on every rank: a local failure anywhere, or PCR_ERR_ARG when the fingerprints differ.
+int shard_agree(pcr_ctx *ctx, uint64_t fingerprint, int local_rc, const char *what, pcr_comm *c = nullptr)
 {
-	pcr_comm *c = ctx->shard_comm;
+	if(!c) c = ctx->shard_comm;
 	const uint64_t me[2] = {local_rc != PCR_OK ? sh_fail_bit(local_rc) : 0ull, fingerprint};
 	std::vector<uint64_t> all(2*(size_t)c->world);
 	const int rc = sh_allgather_host(ctx, c, me, sizeof(me), all.data());
@@ -360,6 +360,7 @@ int pcr_shard_targets(pcr_ctx *ctx, pcr_comm *comm, uint64_t first_seq, uint64_t
 {
 	if(!ctx){ g_err = "pcr_shard_targets: bad argument"; return PCR_ERR_ARG; }
 	if(!comm){ ctx->drop_shard(); return PCR_OK; }
+	if(ctx->trial_comm){ g_err = "pcr_shard_targets: trial ranks are attached (pcr_design_trial_ranks); the two modes do not combine"; return PCR_ERR_STATE; }
 	if(!comm->host_fn && comm->device != ctx->device){ g_err = "pcr_shard_targets: the communicator belongs to another device"; return PCR_ERR_ARG; }
 	ctx->drop_shard();
 	const SeqSet &S = ctx->sets[PCR_SET_TARGET];

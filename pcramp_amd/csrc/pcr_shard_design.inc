@@ -67,10 +67,12 @@ int pool_cover_pass(pcr_ctx *ctx, const std::vector<std::vector<uint8_t> > &amp,
 }
 
 // One status-and-size all-gather, then one all-gather of records padded to the largest: every rank's `words` u64 -> all of
-// them, rank order, in `out` (first[r] .. first[r + 1] for rank r).  Returns the same code on every rank.
-int sh_gather_var(pcr_ctx *ctx, int local_rc, const std::vector<uint64_t> &words, std::vector<uint64_t> &out, std::vector<size_t> &first)
+// them, rank order, in `out` (first[r] .. first[r + 1] for rank r), over `c` (nullptr: the attached shard's communicator).
+// Returns the same code on every rank.
+int sh_gather_var(pcr_ctx *ctx, int local_rc, const std::vector<uint64_t> &words, std::vector<uint64_t> &out, std::vector<size_t> &first,
+	pcr_comm *c = nullptr)
 {
-	pcr_comm *c = ctx->shard_comm;
+	if(!c) c = ctx->shard_comm;
 	const size_t W = (size_t)c->world;
 	const uint64_t me[2] = {local_rc != PCR_OK ? sh_fail_bit(local_rc) : 0ull, local_rc != PCR_OK ? 0ull : (uint64_t)words.size()};
 	std::vector<uint64_t> hdr(2*W);

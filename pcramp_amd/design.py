@@ -43,8 +43,17 @@ SWITCHES = {"--count": ("num_assay", int), "--trial": ("num_trial", int), "--see
 IGNORED_WITH_VALUE = {"-t", "-b", "-o", "--thread"}
 
 
-def options_from_argv(argv):
-    """The options a reference command line sets (argv[0] is the program name); unknown switches raise."""
+def trials_per_rank(num_trial, world):
+    """The trials of one rank when `world` ranks share --trial num_trial, as the reference's root divides them (main.cpp:65)."""
+    num_trial, world = int(num_trial), int(world)
+    if world < 1:
+        raise ValueError("design.trials_per_rank: world must be at least 1")
+    return max(1, -(-num_trial // world))
+
+
+def options_from_argv(argv, world=1):
+    """The options a reference command line sets (argv[0] is the program name); unknown switches raise.  world: the ranks of
+    the reference's MPI mode, whose num_trial is then that of one rank (trials_per_rank)."""
     o = dict(DEFAULTS)
     i = 1
     while i < len(argv):
@@ -61,6 +70,8 @@ def options_from_argv(argv):
         else:
             o[name] = typ(argv[i + 1])
             i += 2
+    if world != 1:
+        o["num_trial"] = trials_per_rank(o["num_trial"], world)
     return o
 
 
