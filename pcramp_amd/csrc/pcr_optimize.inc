@@ -156,7 +156,7 @@ __global__ void k_pair_moves_batch(const DevEntry *__restrict__ db, uint32_t n, 
 			for(uint32_t v = job.v_begin;v < job.v_end;++v){
 				const float var = identity(variants[v], ee.w, use_taq);
 				const float f = (side == 0) ? var : best, r = (side == 0) ? best : var;
-				if(__fsqrt_rn(__fmul_rn(f, r)) >= ident_thr)                         // pcr_assay.cpp:285-287
+				if(sqrtf(__fmul_rn(f, r)) >= ident_thr)                         // pcr_assay.cpp:285-287
 					atomicOr((unsigned long long *)&dst[(size_t)v*bit_words + (ee.seq >> 6)], bit);
 			}
 		}
@@ -180,7 +180,7 @@ __global__ void k_pair_moves_batch(const DevEntry *__restrict__ db, uint32_t n, 
 		for(uint32_t v = job.v_begin;v < job.v_end;++v){
 			const float var = identity(variants[v], ee.w, use_taq);
 			const float f = (side == 0) ? var : tk.best, r = (side == 0) ? tk.best : var;
-			if(__fsqrt_rn(__fmul_rn(f, r)) >= ident_thr) atomicOr((unsigned long long *)&dst[(size_t)v*bit_words + (ee.seq >> 6)], 1ull << (ee.seq & 63));
+			if(sqrtf(__fmul_rn(f, r)) >= ident_thr) atomicOr((unsigned long long *)&dst[(size_t)v*bit_words + (ee.seq >> 6)], 1ull << (ee.seq & 63));
 		}
 	}
 }
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(256) void k_pair_moves_lds(const DevEntry *__restri
 			for(uint32_t v = job.v_begin;v < job.v_end;++v){
 				const float var = identity(variants[v], ee.w, use_taq);
 				const float f = (side == 0) ? var : tk.best, r = (side == 0) ? tk.best : var;
-				if(__fsqrt_rn(__fmul_rn(f, r)) >= ident_thr) atomicOr((unsigned long long *)&dst[(size_t)v*bit_words + (ee.seq >> 6)], 1ull << (ee.seq & 63));
+				if(sqrtf(__fmul_rn(f, r)) >= ident_thr) atomicOr((unsigned long long *)&dst[(size_t)v*bit_words + (ee.seq >> 6)], 1ull << (ee.seq & 63));
 			}
 		}
 		__syncthreads();
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(256) void k_pair_moves_lds(const DevEntry *__restri
 				for(uint32_t v = job.v_begin;v < job.v_end;++v){
 					const float var = identity(variants[v], ew, use_taq);
 					const float f = (side == 0) ? var : best, r = (side == 0) ? best : var;
-					if(__fsqrt_rn(__fmul_rn(f, r)) >= ident_thr)                         // pcr_assay.cpp:285-287
+					if(sqrtf(__fmul_rn(f, r)) >= ident_thr)                         // pcr_assay.cpp:285-287
 						atomicOr((unsigned long long *)&dst[(size_t)v*bit_words + (seq >> 6)], bit);
 				}
 			}
@@ -412,7 +412,7 @@ __global__ __launch_bounds__(256) void k_pair_moves_tasks(const MoveTask *__rest
 		for(uint32_t v = job.v_begin + lane;v < job.v_end;v += 64){
 			const float var = identity(variants[v], ee.w, use_taq);
 			const float f = (side == 0) ? var : t.best, r = (side == 0) ? t.best : var;
-			if(__fsqrt_rn(__fmul_rn(f, r)) >= ident_thr)                             // pcr_assay.cpp:285-287
+			if(sqrtf(__fmul_rn(f, r)) >= ident_thr)                             // pcr_assay.cpp:285-287
 				atomicOr((unsigned long long *)&dst[(size_t)v*bit_words + (ee.seq >> 6)], bit);
 		}
 	}

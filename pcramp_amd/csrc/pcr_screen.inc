@@ -83,7 +83,9 @@ __device__ __forceinline__ bool nondegen(uint32_t v) { return v == 1 || v == 2 |
 
 __device__ __forceinline__ int taq_idx(uint32_t v) { return (v == 2) ? 0 : (v == 4) ? 1 : (v == 1) ? 2 : 3; } // word.cpp:233
 
-// update_identity for one (oligo, key) (optimize.cpp:209-261)
+// update_identity for one (oligo, key) (optimize.cpp:209-261).  The pairing kernels test sqrtf(__fmul_rn(f, r)) >= thr:
+// sqrtf is correctly rounded under the default flags, as the reference's sqrtf is; __fsqrt_rn is the bare v_sqrt_f32
+// (about 1 ulp) here and refuses a pair whose exact score equals the threshold (an 18-mer with one mismatch at 17/18).
 __device__ float identity(const OligoDev &o, const Planes &key, int use_taq)
 {
 	const uint32_t cnt = __popc((key.a & o.m.a) | (key.c & o.m.c) | (key.g & o.m.g) | (key.t & o.m.t));
@@ -167,7 +169,7 @@ __global__ void k_pair(const DevEntry *__restrict__ db, uint32_t n, const uint32
 					if(has_split(planes, base, amp_start, amp_len)) continue;
 					const float f = identity(F, (orient == 0) ? ei.w : ej.w, use_taq);
 					const float r = identity(R, (orient == 0) ? ej.w : ei.w, use_taq);
-					if(__fsqrt_rn(__fmul_rn(f, r)) >= ident_thr){                // pcr_assay.cpp:572-576
+					if(sqrtf(__fmul_rn(f, r)) >= ident_thr){                // pcr_assay.cpp:572-576
 						uint64_t *dst = (orient == 0) ? bits_fr : bits_rf;
 						atomicOr((unsigned long long *)&dst[(size_t)pair*bit_words + (ei.seq >> 6)], 1ull << (ei.seq & 63));
 					}
@@ -243,7 +245,7 @@ __global__ void k_pair_moves(const DevEntry *__restrict__ db, uint32_t n, uint32
 	for(uint32_t v = 0;v < n_variants;++v){
 		const float var = identity(variants[v], ee.w, use_taq);
 		const float f = (side == 0) ? var : best, r = (side == 0) ? best : var;
-		if(__fsqrt_rn(__fmul_rn(f, r)) >= ident_thr)                             // pcr_assay.cpp:285-287
+		if(sqrtf(__fmul_rn(f, r)) >= ident_thr)                             // pcr_assay.cpp:285-287
 			atomicOr((unsigned long long *)&dst[(size_t)v*bit_words + (ee.seq >> 6)], bit);
 	}
 }
@@ -330,7 +332,7 @@ __global__ __launch_bounds__(PMS_THREADS) void k_pair_moves_seq(const DevEntry *
 		for(uint32_t v = 0;v < n_variants;++v){
 			const float var = identity(variants[v], ee.w, use_taq);
 			const float f = (side == 0) ? var : best, r2 = (side == 0) ? best : var;
-			if(__fsqrt_rn(__fmul_rn(f, r2)) >= ident_thr)                        // pcr_assay.cpp:285-287
+			if(sqrtf(__fmul_rn(f, r2)) >= ident_thr)                        // pcr_assay.cpp:285-287
 				atomicOr((unsigned long long *)&dst[(size_t)v*bit_words + (seq >> 6)], bit);
 		}
 	}
@@ -485,7 +487,7 @@ __global__ __launch_bounds__(64*POST_WAVES) void k_post(const Hit *__restrict__ 
 					if(has_split(planes, base, amp_start, amp_len)) continue;
 					const float f = identity(F, (orient == 0) ? me.w : ej.w, use_taq);
 					const float r = identity(R, (orient == 0) ? ej.w : me.w, use_taq);
-					if(__fsqrt_rn(__fmul_rn(f, r)) >= ident_thr){                        // pcr_assay.cpp:572-576
+					if(sqrtf(__fmul_rn(f, r)) >= ident_thr){                        // pcr_assay.cpp:572-576
 						uint64_t *dst = (orient == 0) ? bits_fr : bits_rf;
 						atomicOr((unsigned long long *)&dst[(size_t)pair*bit_words + (seq >> 6)], 1ull << (seq & 63));
 					}
@@ -630,7 +632,7 @@ __global__ __launch_bounds__(64*WAVES) void k_post_big(const Hit *__restrict__ h
 						if(has_split(planes, base, amp_start, amp_len)) continue;
 						const float f = identity(F, (orient == 0) ? me.w : ej.w, use_taq);
 						const float r = identity(R, (orient == 0) ? ej.w : me.w, use_taq);
-						if(__fsqrt_rn(__fmul_rn(f, r)) >= ident_thr){                      // pcr_assay.cpp:572-576
+						if(sqrtf(__fmul_rn(f, r)) >= ident_thr){                      // pcr_assay.cpp:572-576
 							uint64_t *dst = (orient == 0) ? bits_fr : bits_rf;
 							atomicOr((unsigned long long *)&dst[(size_t)pair*bit_words + (seq >> 6)], 1ull << (seq & 63));
 						}

@@ -676,3 +676,67 @@ def test_make_degenerate(oracle, reference, case):
     assert changed >= 3
     if "max_dimer" in case:
         assert reduced >= 1
+
+
+# ------------------------------------------------------------------------------------ planted amplicon edges
+@pytest.mark.parametrize("k", range(__import__("amplicon_edges").N_SCENARIOS))
+def test_amplicon_edges(oracle, reference, k):
+    """tests/amplicon_edges.py's planted geometry (length window, overlap, dangling ends, EOS at both ends of the amplicon
+    and of the padded inner stretch, several partners, identity at the threshold): target_match, coverage,
+    collect_amplicons, move_coverage and background_match of the oracle equal the reference's."""
+    import amplicon_edges as AE
+    from testdata import move_variants
+    from pcramp_amd import words as W
+    sc = AE.scenarios(oracle)[k]
+    so, sr = _sessions(oracle, reference, sc.seqs, sc.weights, **sc.opts)
+    for s in (so, sr):
+        for i in sc.inactive:
+            s.set_active(i, False)
+    assert so.select(sc.pairs) == sr.select(sc.pairs)
+    for s in (so, sr):
+        for i, pos in sc.splits:
+            s.split(i, pos)
+    assert so.db_entries() == sr.db_entries()
+    o = sc.opts
+    fr, rf = AE.expected(sc)
+    # a primer off either end makes the reference's collect_unique_amplicons throw (a 3' hang: extract_amplicon_seq reads
+    # past the sequence; a 5' hang: AmpliconBounds refuses begin > end, begin being unsigned there); collect_amplicons is
+    # compared on the other sequences of the scenario (below)
+    hangs = [l.seq for l in sc.labels if "hang" in l.what]
+    for p, pair in enumerate(sc.pairs):
+        ob, ori = so.target_match(pair, orient=True)
+        assert (ob == sr.target_match(pair)).all(), p
+        assert np.array_equal((ori & 1) != 0, fr[p]) and np.array_equal((ori & 2) != 0, rf[p]), p
+        assert so.target_coverage(pair) == sr.target_coverage(pair), p
+        if not hangs:
+            assert so.collect_amplicons(pair, o["target_threshold"], o["amp_min"], o["amp_max"]) == \
+                sr.collect_amplicons(pair, o["target_threshold"], o["amp_min"], o["amp_max"]), p
+        for side in (0, 1):
+            var = []
+            for kind in ("trim5", "trim3", "grow5", "grow3"):
+                var += move_variants(W, pair[side], kind)[:2]
+            assert np.array_equal(so.move_coverage(pair, side, var), sr.move_coverage(pair, side, var)), (p, side)
+    if hangs:
+        keep = [i for i in range(len(sc.seqs)) if i not in hangs]
+        co, cr = _sessions(oracle, reference, [sc.seqs[i] for i in keep], **o)
+        assert co.select(sc.pairs) == cr.select(sc.pairs)
+        for s in (co, cr):
+            for i, pos in sc.splits:
+                s.split(keep.index(i), pos)
+        for p, pair in enumerate(sc.pairs):
+            assert co.collect_amplicons(pair, o["target_threshold"], o["amp_min"], o["amp_max"]) == \
+                cr.collect_amplicons(pair, o["target_threshold"], o["amp_min"], o["amp_max"]), p
+    # the same sequences as a background set, the oracle in the reference's index mode (emulate_index_bug=1)
+    bo, br = _sessions(oracle, reference, sc.seqs)
+    thr = np.float32(0.8) * np.float32(0.9)
+    assert bo.select(sc.pairs, threshold=thr, min_len_override=16) == br.select(sc.pairs, threshold=thr, min_len_override=16)
+    compared = {}
+    for pair in sc.pairs:
+        for w, amp in enumerate(((0, 2000), (o["amp_min"], o["amp_max"]))):
+            rb, _ = br.background_match(pair, amp_min=amp[0], amp_max=amp[1])
+            if rb is None:
+                continue                           # the reference's odd-count out-of-bounds case (background_match.cpp:122)
+            ob, _ = bo.background_match(pair, amp_min=amp[0], amp_max=amp[1], emulate_index_bug=1)
+            assert (ob == rb).all()
+            compared[w] = compared.get(w, 0) + 1
+    assert len(compared) == 2, compared                # every amplicon window compared on at least one pair
