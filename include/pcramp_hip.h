@@ -404,6 +404,36 @@ typedef struct {
 int64_t pcr_collect_amplicons(pcr_ctx *ctx, pcr_set which, const pcr_pair *pair, float threshold, int32_t amp_min, int32_t amp_max,
 	pcr_amplicon *out, uint64_t cap);
 
+/* ---- Cross-assay products of a primer pool */
+
+/* One product two oligos of a pool form on a sequence of the set (32 bytes). */
+typedef struct {
+	uint32_t plus_oligo, minus_oligo;   /* distinct-oligo ids (see oligo_id) in the plus- and the minus-strand role */
+	uint32_t sequence;
+	int32_t  begin, end;                /* as pcr_amplicon */
+	int32_t  inner_start, inner_length; /* as pcr_amplicon */
+	uint32_t intended;                  /* 1: some pool pair i has {id(F_i), id(R_i)} = {plus_oligo, minus_oligo} */
+} pcr_product;
+
+#define PCR_POOL_MAX_PAIRS 1024     /* 2 048 distinct oligos */
+
+/* Every amplicon any two oligos of a pool form over the word DB of the last pcr_select_words on `which`.
+ * The pool's 2*n_pool oligo words (F of pair i is slot 2i, R is slot 2i+1) get distinct ids in order of first
+ * appearance; oligo_id[2*n_pool] receives them.  For every ordered pair of distinct oligos (x, y), x = y included, the
+ * products are the amplicons PCR::collect_unique_amplicons / extract_amplicon_seq (pcr_assay.cpp:443-542,756-813) admit
+ * with x in the plus-strand role and y in the minus-strand role: both sites match at threshold^2, the plus site's sequence
+ * is active, the sites do not overlap, amp_min <= end - begin + 1 <= amp_max, and the inner stretch lies inside the
+ * sequence and holds no EOS -- what pcr_collect_amplicons reports for the pair (x, y) in orientation 0.  So for oligos a
+ * and b, pcr_collect_amplicons((a, b)) gives the products (a, b) as orientation 0 and (b, a) as orientation 1; for a = b
+ * it gives each product twice, this call once.  Records are unique by (plus_oligo, minus_oligo, sequence, begin, end) and
+ * sorted by that key.  Returns the number of products or a negative error; if it exceeds cap, the contents of out are
+ * unspecified (cap = 0: count only).  n_pool = 0 returns 0.  PCR_ERR_STATE without a word DB; PCR_ERR_ARG for
+ * PCR_SET_MULTIPLEX, null pointers or n_pool > PCR_POOL_MAX_PAIRS.  Changes nothing other calls read.  On a handle with
+ * a target shard attached, sequence indices are local to the rank's block and no collective is made (as
+ * pcr_collect_amplicons). */
+int64_t pcr_pool_products(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, uint32_t *oligo_id, pcr_product *out, uint64_t cap);
+
 /* ---- The multiplex compatibility filter of the trial loop (main.cpp:744-803), batched over the trial assays */
 
 typedef struct {

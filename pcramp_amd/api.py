@@ -60,6 +60,12 @@ class Amplicon(C.Structure):
                 ("inner_length", C.c_int32), ("orientation", C.c_uint32)]
 
 
+# pcr_product: one amplicon two oligos of a pool form (Screener.pool_products)
+PRODUCT_DTYPE = np.dtype([("plus_oligo", np.uint32), ("minus_oligo", np.uint32), ("sequence", np.uint32), ("begin", np.int32),
+                          ("end", np.int32), ("inner_start", np.int32), ("inner_length", np.int32), ("intended", np.uint32)])
+POOL_MAX_PAIRS = 1024                         # PCR_POOL_MAX_PAIRS
+
+
 class SamplerArgs(C.Structure):
     _fields_ = [("primer_min", C.c_int32), ("primer_max", C.c_int32), ("amp_min", C.c_int32), ("amp_max", C.c_int32),
                 ("max_degen", C.c_double)]
@@ -114,7 +120,7 @@ ABI_SYMBOLS = [
     "pcr_sw_align_words", "pcr_background_match", "pcr_multiplex_match",
     "pcr_thermo", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
-    "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons",
+    "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -199,6 +205,9 @@ def load_library():
                                     C.POINTER(ThermoArgs), C.c_void_p, C.c_void_p]
     L.pcr_collect_amplicons.restype = C.c_int64
     L.pcr_collect_amplicons.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64]
+    L.pcr_pool_products.restype = C.c_int64
+    L.pcr_pool_products.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_uint64]
     L.pcr_multiplex_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.pcr_multiplex_coverage.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_void_p]
     L.pcr_host_pool_overlaps.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -660,6 +669,29 @@ class Screener:
             if n <= cap:
                 return [dict(sequence=r.sequence, begin=r.begin, end=r.end, inner_start=r.inner_start,
                              inner_length=r.inner_length, orientation=r.orientation) for r in buf[:n]]
+            cap = int(n)
+
+    def pool_products(self, pool, threshold=1.0, amp_min=80, amp_max=200, which=TARGET, select=True, cap=1 << 16):
+        """Every amplicon any two oligos of the pool form (pcr_pool_products) -> (oligo_id uint32[2 * len(pool)],
+        records: PRODUCT_DTYPE array sorted by (plus_oligo, minus_oligo, sequence, begin, end)).
+
+        oligo_id[2i] / oligo_id[2i + 1] is the distinct-oligo id of F / R of pool pair i (ids in order of first
+        appearance).  A record is an amplicon with plus_oligo in the plus-strand role and minus_oligo in the minus-strand
+        role, as collect_amplicons reports it for that pair in orientation 0; `intended` marks the combinations that are
+        pool pairs.  select=True first runs select_words(pool, float32(threshold)**2, which=which): this REPLACES the
+        set's word DB.  select=False uses the DB as it stands (the one collect_amplicons and find_target_match read)."""
+        if select:
+            self.select_words(pool, float(np.float32(threshold) * np.float32(threshold)), which=which)
+        a = W.pairs_array(pool)
+        ids = np.zeros(max(2 * len(pool), 1), np.uint32)
+        while True:
+            out = np.zeros(max(cap, 1), PRODUCT_DTYPE)
+            n = self.L.pcr_pool_products(self.h, which, a.ctypes.data, len(pool), float(threshold), int(amp_min), int(amp_max),
+                                         ids.ctypes.data, out.ctypes.data, cap)
+            if n < 0:
+                raise PcrError(_err(self.L))
+            if n <= cap:
+                return ids[:2 * len(pool)].copy(), out[:n].copy()
             cap = int(n)
 
     def multiplex_load(self, seqs, min_oligo_length=18):

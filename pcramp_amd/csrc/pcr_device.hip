@@ -751,6 +751,8 @@ struct pcr_ctx {
 	DevBuf<pcr_amplicon> mx_amp;   // pcr_collect_amplicons records
 	DevBuf<OligoDev> opt_oligos; DevBuf<uint2> opt_jobs; DevBuf<float> opt_cov; DevBuf<uint32_t> opt_loc, opt_tasks;   // pcr_optimize_batch: base oligos + trial words, per-oligo variant ranges, coverages
 	DevBuf<Planes> mx_keys; uint32_t mx_n_keys = 0; DevBuf<uint32_t> mx_count;   // multiplex background: unique words of the accepted amplicons (pcr_multiplex.inc)
+	// pcr_pool_products (pcr_pool.inc): oligo table + intended bitmap, per-entry / per-item counts and offsets, items, records, sort keys
+	DevBuf<uint8_t> pool_in, pool_tmp; DevBuf<uint32_t> pool_cnt, pool_ord; DevBuf<uint64_t> pool_eoff, pool_ioff, pool_keys; DevBuf<uint2> pool_items; DevBuf<pcr_product> pool_rec;
 	// an attached target shard (pcr_shard_targets, pcr_shard.inc): PCR_SET_TARGET holds rows [shard_first, shard_first + n) of
 	// shard_n_total, and the local search combines target coverage over shard_comm; NULL = not sharded
 	pcr_comm *shard_comm = nullptr; uint64_t shard_first = 0, shard_n_total = 0; int shard_mode = 0;
@@ -1569,6 +1571,7 @@ void pcr_destroy(pcr_ctx *ctx)
 	if(ctx->sw_pin) (void)hipHostFree(ctx->sw_pin);
 	for(int k = 0;k < 2;++k){ if(ctx->sw_done[k]) (void)hipEventDestroy(ctx->sw_done[k]); }
 	ctx->oligos.release(); ctx->sw_jobs.release(); ctx->sw_out.release(); ctx->sw_q.release(); ctx->sw_qlen.release(); ctx->sw_t.release(); ctx->entry_codes.release(); ctx->entry_lens.release(); ctx->amp_recs.release(); ctx->amp_recs2.release(); ctx->amp_keys.release(); ctx->amp_pkeys.release(); ctx->amp_pair_start.release(); ctx->sort_tmp.release(); ctx->bg_pairs.release(); ctx->th_jobs.release(); ctx->th_out.release(); ctx->th_dg.release(); ctx->th_dbg.release(); ctx->split_where.release(); ctx->th_map.release(); ctx->th_bad.release(); ctx->mx_keys.release(); ctx->mx_count.release(); ctx->mx_amp.release(); ctx->opt_oligos.release(); ctx->opt_jobs.release(); ctx->opt_cov.release(); ctx->opt_loc.release(); ctx->opt_tasks.release();
+	ctx->pool_in.release(); ctx->pool_tmp.release(); ctx->pool_cnt.release(); ctx->pool_ord.release(); ctx->pool_eoff.release(); ctx->pool_ioff.release(); ctx->pool_keys.release(); ctx->pool_items.release(); ctx->pool_rec.release();
 	if(ctx->aux_stream){ (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
 	if(ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
 	delete ctx;
@@ -2953,4 +2956,5 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_trial_ranks.inc"
 #include "pcr_entry_sw_thermo.inc"
 #include "pcr_multiplex_screen.inc"
+#include "pcr_pool.inc"
 #include "pcr_writers.inc"
