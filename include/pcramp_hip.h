@@ -585,6 +585,10 @@ int64_t pcr_format_oligos(const pcr_pair *assay, const pcr_pair *pool, uint32_t 
  * opening of the assay array (main.cpp:460-462). */
 int64_t pcr_format_header(const pcr_output *o, int argc, const char *const *argv, uint32_t seed, char *out, uint64_t cap);
 
+/* The version, command line and seed lines of pcr_format_header alone (json = Options::JSON_OUTPUT): the reference writes and
+ * flushes them before it reads its FASTA files (main.cpp:125-163), so they are all its output file holds when the ingest throws. */
+int64_t pcr_format_preamble(int json, int argc, const char *const *argv, uint32_t seed, char *out, uint64_t cap);
+
 /* What every design iteration writes BEFORE the search (main.cpp:504-519): the rule and "# Attempting to detect N
  * remaining targets" (text) or the record opening with its id (JSON).  The reference writes it even if the iteration
  * then finds no assay. */

@@ -109,6 +109,21 @@ void summary(Out &o, const char *prefix, const uint64_t *len, uint32_t n, bool j
 	}
 }
 
+// version, command line and seed (main.cpp:131-163): the lines the reference writes before it reads its inputs
+void write_preamble(Out &o, bool json, int argc, const char *const *argv, uint32_t seed)
+{
+	if(!json){                                                   // main.cpp:132-147
+		o << "PCRamp version 0.3\n" << "Command line:";
+		for(int i = 0;i < argc;++i) o << ' ' << argv[i];
+		o << '\n' << "Random number seed = " << (unsigned)seed << '\n';
+	}
+	else{                                                        // main.cpp:148-160
+		o << "{\n\t\"program\":\"PCRamp\",\n" << "\t\"version\":\"0.3\",\n\t" << "\"command line\":\"" << argv[0];
+		for(int i = 1;i < argc;++i) o << ' ' << argv[i];
+		o << "\",\n\t\"seed\":" << (unsigned)seed << ',' << '\n';
+	}
+}
+
 inline bool bit(const uint64_t *w, uint32_t i) { return w && ((w[i >> 6] >> (i & 63)) & 1ull); }
 
 } // namespace
@@ -127,19 +142,18 @@ int64_t pcr_format_header(const pcr_output *f, int argc, const char *const *argv
 {
 	if(!f || argc < 1 || !argv){ g_err = "pcr_format_header: bad argument"; return PCR_ERR_ARG; }
 	Out o;
-	if(!f->json){                                                // main.cpp:132-147
-		o << "PCRamp version 0.3\n" << "Command line:";
-		for(int i = 0;i < argc;++i) o << ' ' << argv[i];
-		o << '\n' << "Random number seed = " << (unsigned)seed << '\n';
-	}
-	else{                                                        // main.cpp:148-160
-		o << "{\n\t\"program\":\"PCRamp\",\n" << "\t\"version\":\"0.3\",\n\t" << "\"command line\":\"" << argv[0];
-		for(int i = 1;i < argc;++i) o << ' ' << argv[i];
-		o << "\",\n\t\"seed\":" << (unsigned)seed << ',' << '\n';
-	}
+	write_preamble(o, f->json != 0, argc, argv, seed);
 	summary(o, "target sequence summary", f->target_lengths, f->n_target, f->json != 0);           // main.cpp:440
 	summary(o, "background sequence summary", f->background_lengths, f->n_background, f->json != 0);   // main.cpp:443
 	if(f->json) o << "\t\"assays\":[\n";                           // main.cpp:460-462
+	return emit(o, out, cap);
+}
+
+int64_t pcr_format_preamble(int json, int argc, const char *const *argv, uint32_t seed, char *out, uint64_t cap)
+{
+	if(argc < 1 || !argv){ g_err = "pcr_format_preamble: bad argument"; return PCR_ERR_ARG; }
+	Out o;
+	write_preamble(o, json != 0, argc, argv, seed);
 	return emit(o, out, cap);
 }
 
