@@ -2373,6 +2373,7 @@ int select_impl(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_p
 		const uint32_t cap = S.bucket_cap;
 		const uint64_t n_slots = (uint64_t)S.n*cap;
 		if(n_slots >= (uint64_t(1) << 32) || n_slots*(sizeof(Hit) + sizeof(DevEntry)) > (uint64_t(96) << 30)){
+			S.bucket_cap = 64;   // (the size that was refused must not stay: the next pass over this set, with other candidates, starts small and grows again)
 			g_err = "pcr_select_words: the per-sequence hit buckets would not fit (too many tied sites per sequence)"; return PCR_ERR_CAPACITY;
 		}
 		if((rc = ctx->hits.ensure(n_slots)) != PCR_OK) return rc;

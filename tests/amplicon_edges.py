@@ -13,6 +13,7 @@ A label is (pair index, orientation 'FR' / 'RF', built amplicon length, admitted
 the bits per pair and orientation; `expected_bounds(c)` the (sequence, begin, end) records of collect_amplicons.
 tests/test_amplicon_edges_host.py holds the oracle to these labels, so that no case drifts off its edge unnoticed.
 """
+import bisect
 import random
 from collections import namedtuple
 
@@ -49,6 +50,26 @@ def pair_score(f, r):
     return f32(np.sqrt(f32(f32(f) * f32(r))))
 
 
+def plant(lib, s, role, pos, o, ident, oligo):
+    """Write oligo text `o` (plus role) or its reverse complement (minus role) into the base list `s` at pos, cut where it runs
+    off the sequence -> the Site the reference sees there."""
+    L = len(s)
+    t = o if role == "P" else revcomp(o)
+    for j, c in enumerate(t):
+        if 0 <= pos + j < L:
+            s[pos + j] = c
+    w = lib.centered_word(o)
+    ws, we = lib.word_start(w), lib.word_stop(w)
+    loc = pos - ws if role == "P" else pos + we                            # WordMatch::loc (sequence.h:57-75)
+    if L % 2 and (loc + 31 > L - 1 if role == "P" else loc > L - 1):
+        # a site that only a trailing partial word holds, in a sequence of odd length: Sequence::pack's position
+        # counter has also stepped over the padding nibble of the last byte (sequence.cpp:198-263), so the
+        # reference places the site one base towards the 3' end (plus role: towards the 5' end)
+        loc += 1 if role == "M" else -1
+    geo = loc + ws if role == "P" else loc - we                            # the template_loc5 the reference sees
+    return Site(role, geo, len(o), f32(1.0) if ident is None else f32(ident), oligo, loc)
+
+
 class _Builder:
     """Sequences of one scenario: each holds one planted geometry (or a few sites for the partner cases)."""
 
@@ -71,21 +92,8 @@ class _Builder:
         placed = []
         for role, pos, ident in sites:
             o = (mutate or {}).get(role) or self.oligo(pair, orient, role)
-            t = o if role == "P" else revcomp(o)
-            for j, c in enumerate(t):
-                if 0 <= pos + j < L:
-                    s[pos + j] = c
             which = ("F" if role == "P" else "R") if orient == "FR" else ("R" if role == "P" else "F")
-            w = self.lib.centered_word(o)
-            ws, we = self.lib.word_start(w), self.lib.word_stop(w)
-            loc = pos - ws if role == "P" else pos + we                    # WordMatch::loc (sequence.h:57-75)
-            if L % 2 and (loc + 31 > L - 1 if role == "P" else loc > L - 1):
-                # a site that only a trailing partial word holds, in a sequence of odd length: Sequence::pack's position
-                # counter has also stepped over the padding nibble of the last byte (sequence.cpp:198-263), so the
-                # reference places the site one base towards the 3' end (plus role: towards the 5' end)
-                loc += 1 if role == "M" else -1
-            geo = loc + ws if role == "P" else loc - we                    # the template_loc5 the reference sees
-            placed.append(Site(role, geo, len(o), f32(1.0) if ident is None else f32(ident), (pair, which), loc))
+            placed.append(plant(self.lib, s, role, pos, o, ident, (pair, which)))
         for e in text_eos:
             s[e] = "-"
         i = len(self.seqs)
@@ -103,13 +111,11 @@ def _site_pairs(sites, L, eos, amp_min, amp_max, collect=False):
     """The reference's loop over the planted sites of one orientation, sorted by WordMatch::loc (a plus and a minus site at
     one loc always overlap, so their order does not matter) -> list of (plus site, minus site, begin, end)."""
     out = []
-    ordered = sorted(sites, key=lambda s: s.loc)
-    for a_i, p in enumerate(ordered):
-        if p.role != "P":
-            continue
-        for q in ordered[a_i:]:
-            if q.role != "M":
-                continue
+    plus = sorted((s for s in sites if s.role == "P"), key=lambda s: s.loc)
+    minus = sorted((s for s in sites if s.role == "M"), key=lambda s: s.loc)
+    m_locs = [s.loc for s in minus]
+    for p in plus:
+        for q in minus[bisect.bisect_left(m_locs, p.loc):]:
             p3, m5 = p.pos + p.n - 1, q.pos
             if p3 >= m5:
                 continue                                                   # overlap (:367-370)
@@ -165,16 +171,22 @@ def split_first_answer(label):
 
 def expected_bounds(sc, k):
     """-> sorted set of (sequence, begin, end) of PCR::extract_amplicon_seq for pair k over the planted sites (collect
-    threshold = the scenario's target threshold; every planted site matches at it).  A set: where Sequence::pack cuts
+    threshold = the scenario's target threshold; a planted site below its square is not matched).  A set: where Sequence::pack cuts
     two words at one position (the partial words at a 3' end) the reference lists the amplicon once per word."""
     o = sc.opts
     out = []
+    per_oligo = f32(o["target_threshold"]) * f32(o["target_threshold"])   # an oligo's sites are matched at threshold^2 (:775-776)
+
+    def matched(s):
+        """A site takes part when it matches (unsigned)(length * threshold^2) bases of its oligo.  (Without TaqMAMA the
+        identity is that count over the length; with it, every planted site of these scenarios matches.)"""
+        return bool(o["use_taq_mama"]) or round(float(s.ident) * s.n) >= int(f32(s.n) * per_oligo)
     for orient in ("FR", "RF"):
         plus_o, minus_o = ("F", "R") if orient == "FR" else ("R", "F")
         for i, sites in enumerate(sc.sites):
             if i in sc.inactive:
                 continue
-            mine = [s for s in sites if s.oligo[0] == k and
+            mine = [s for s in sites if s.oligo[0] == k and matched(s) and
                     ((s.role == "P" and s.oligo[1] == plus_o) or (s.role == "M" and s.oligo[1] == minus_o))]
             for p, q, b, e in _site_pairs(mine, len(sc.seqs[i]), sc.eos[i], o["amp_min"], o["amp_max"], collect=True):
                 out.append((i, b & 0xFFFFFFFF, e))                      # begin is unsigned there (a 5' hang wraps)

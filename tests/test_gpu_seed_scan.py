@@ -3,6 +3,7 @@ oracle: tile borders, many candidates, duplicated primers, IUPAC on either side,
 The word DB must be identical entry for entry.  Run on the GPU box with `-m gpu`."""
 import os
 import random
+import re
 
 import numpy as np
 import pytest
@@ -210,9 +211,14 @@ def test_iupac_primers_in_two_seed_groups(both, oracle):
     assert e3 == _oracle_entries(oracle, seqs, pairs, 1.0, 0.9)
 
 
-def test_dense_hits_low_complexity(both, oracle):
+LOW_COMPLEXITY_SLOTS = 8192     # the bucket size test_dense_hits_low_complexity ends with
+
+
+def test_dense_hits_low_complexity(both, oracle, capfd, monkeypatch):
     """Low-complexity targets: almost every position is a seed hit and very many windows tie at the maximum
-    (bucket growth, multi-seed codes, verification in every lane)."""
+    (bucket growth, multi-seed codes, verification in every lane).  The buckets end at LOW_COMPLEXITY_SLOTS slots (the
+    library's "pass done" debug line): one wave per sequence sorts them in LDS (k_finalize<1>); the larger forms are
+    pinned by tests/test_gpu_dense_buckets.py."""
     rng = random.Random(12)
     seqs = ["A" * 700 + rand_seq(rng, 300) + "AC" * 300, "ACGT" * 400, "A" * 40 + "C" + "A" * 500, rand_seq(rng, 1200)]
     txt = [("A" * 20, "T" * 20), ("AC" * 10, "GT" * 10), ("ACGT" * 5, "ACGT" * 5), ("A" * 19 + "C", "T" * 18)]
@@ -223,6 +229,16 @@ def test_dense_hits_low_complexity(both, oracle):
     assert e3 == e2
     assert e3 == _oracle_entries(oracle, seqs, pairs, 1.0, 0.9)
     assert len(e3) > 1000
+    monkeypatch.setenv("PCRAMP_DEBUG", "1")
+    d = api.Screener(0)
+    try:
+        capfd.readouterr()
+        assert _entries(d, seqs, pairs, thr) == e3
+        done = re.findall(r"pass done: (\d+)-slot buckets, largest fill (\d+)", capfd.readouterr().err)
+        print("pass done (slots, largest fill):", done)
+        assert len(done) == 1 and int(done[0][0]) == LOW_COMPLEXITY_SLOTS and int(done[0][1]) > LOW_COMPLEXITY_SLOTS // 2
+    finally:
+        d.close()
 
 
 def test_bench_shape_sample(both):

@@ -18,10 +18,10 @@ def dev():
     s.close()
 
 
-def test_sw_lanes_match_oracle(dev, oracle):
-    rng = random.Random(31)
+def _lanes(oracle, rng, n):
+    """n query / template word pairs: mutated copies with and without a gap, runs of one base, no match at all, unrelated."""
     qs, ts = [], []
-    for it in range(3000):
+    for it in range(n):
         qtxt = rand_seq(rng, rng.randint(1, 32), p_degen=0.05)
         mode = rng.random()
         if mode < 0.5:
@@ -45,6 +45,11 @@ def test_sw_lanes_match_oracle(dev, oracle):
         for _ in range(rng.randint(0, 32 - len(ttxt))):
             t = oracle.word_shift_right(t)
         qs.append(q); ts.append(t)
+    return qs, ts
+
+
+def test_sw_lanes_match_oracle(dev, oracle):
+    qs, ts = _lanes(oracle, random.Random(31), 3000)
     got = dev.sw_align_words(qs, ts)
     nz = 0
     for k in range(len(qs)):
@@ -55,6 +60,61 @@ def test_sw_lanes_match_oracle(dev, oracle):
             assert got[k][:7] == want.tup(), k
             nz += 1
     assert nz > 2000
+
+
+SW_DTYPE = np.dtype([("score", "<i2"), ("q_start", "<i2"), ("q_stop", "<i2"), ("t_start", "<i2"), ("t_stop", "<i2"),
+                     ("last1", "u1"), ("last2", "u1"), ("valid", "u1"), ("pad", "u1")])          # pcr_sw_result
+SW_CHUNK = 1 << 16                                                          # lanes per chunk of pcr_sw_align_words
+
+
+def test_sw_across_chunks(dev, oracle):
+    """pcr_sw_align_words beyond one chunk of 65 536 lanes: the two pinned slots are used in turn, a slot is copied out
+    before it is reused and the last two chunks after the loop.  Calls of 65 535 .. 200 000 lanes drawn (seeded) from
+    3 000 distinct lanes whose answers the oracle gives, so that a lane differs from the lanes at its place in the
+    neighbouring chunks: a result taken from the wrong slot, or a chunk overwritten before its copy-out, shows.  Then
+    three lanes and none on the same handle, into a poisoned array: nothing beyond the lanes asked for is written."""
+    import ctypes as C
+    assert C.sizeof(api.SwResult) == SW_DTYPE.itemsize
+    qs, ts = _lanes(oracle, random.Random(37), 3000)
+    want = np.zeros(len(qs), SW_DTYPE)
+    for k in range(len(qs)):
+        r = oracle.sw_align_words(qs[k], ts[k])
+        want[k] = (r.score, r.q_start, r.q_stop, r.t_start, r.t_stop, r.last1, r.last2, r.valid, 0)
+    assert np.count_nonzero(want["valid"]) > 2000
+    q0, t0 = np.array(qs, dtype=np.uint64).reshape(-1, 2), np.array(ts, dtype=np.uint64).reshape(-1, 2)
+    coords = ["score", "q_start", "q_stop", "t_start", "t_stop", "last1", "last2"]
+
+    def call(idx, out):
+        q, t = np.ascontiguousarray(q0[idx]), np.ascontiguousarray(t0[idx])
+        rc = dev.L.pcr_sw_align_words(dev.h, q.ctypes.data, t.ctypes.data, len(idx), out.ctypes.data)
+        assert rc == 0, api._err(dev.L)
+
+    def check(got, idx):
+        w = want[idx]
+        assert np.array_equal(got["score"], w["score"]) and np.array_equal(got["valid"], w["valid"])
+        v = w["valid"] != 0
+        for f in coords:
+            assert np.array_equal(got[f][v], w[f][v]), f
+
+    rng = np.random.default_rng(20261016)
+    for n in (65535, 65536, 65537, 131072, 131073, 200000):
+        idx = rng.integers(0, len(qs), n)
+        for step in (SW_CHUNK, 2 * SW_CHUNK):                               # the lanes one and two chunks apart differ
+            if n > step:
+                a, b = want[idx[:-step]], want[idx[step:]]
+                assert np.mean(a != b) > 0.9
+        got = np.zeros(n, SW_DTYPE)
+        call(idx, got)
+        check(got, idx)
+    poison = np.frombuffer(b"\xa5" * (64 * SW_DTYPE.itemsize), SW_DTYPE).copy()
+    idx = np.array([7, 1900, 42])
+    got = poison.copy()
+    call(idx, got)
+    check(got[:3], idx)
+    assert got[3:].tobytes() == poison[3:].tobytes()
+    got = poison.copy()
+    call(np.zeros(0, np.int64), got)
+    assert got.tobytes() == poison.tobytes()
 
 
 def test_sw_known_answers(dev, oracle):
