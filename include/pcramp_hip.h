@@ -327,8 +327,12 @@ int pcr_background_match(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uin
 	const pcr_background_args *args, uint64_t *bits);
 
 /* PCR::find_multiplex_background_match (background_match.cpp:168-295): F, (F), R, (R) of every
- * pair aligned against every whole sequence of the set (amplicon sequences, up to 32767 bases);
- * bit set when any single normalised score reaches the threshold. */
+ * pair aligned against every whole sequence of the set (amplicon sequences, up to 32766 bases: the
+ * reference's own limit -- SeqOverlap counts columns in a 16-bit integer up to and including the
+ * template length and never returns at 32767); bit set when any single normalised score reaches the
+ * threshold.  bits receives n_pairs x ceil(n / 64) words, bits at or past n zero; nothing is written
+ * for an empty set or zero pairs.  A set holding a longer template is refused with PCR_ERR_CAPACITY:
+ * bits is then all zero, and the handle stays usable. */
 int pcr_multiplex_match(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs,
 	float background_threshold, int use_taq_mama, uint64_t *bits);
 

@@ -340,7 +340,8 @@ static int multiplex_match_impl(pcr_ctx *ctx, int which, const pcr_pair *pairs, 
 	std::vector<uint64_t> code_off(S.n);
 	uint64_t tot = 0;
 	for(uint32_t s = 0;s < S.n;++s){
-		if(S.len[s] > 32767){ g_err = "pcr_multiplex_match: template longer than 32767 bases (SeqOverlap's int16 coordinate range)"; return PCR_ERR_CAPACITY; }
+		// SeqOverlap counts columns in SO_Score (int16) with `j <= max_target_len` (seq_overlap.cpp:383,427): at 32767 the reference never returns
+		if(S.len[s] > 32766){ g_err = "pcr_multiplex_match: template longer than 32766 bases, the reference's limit (SeqOverlap's int16 column counter cannot pass 32767)"; return PCR_ERR_CAPACITY; }
 		code_off[s] = tot; tot += S.len[s];
 	}
 	if(!S.have_codes){
@@ -348,7 +349,8 @@ static int multiplex_match_impl(pcr_ctx *ctx, int which, const pcr_pair *pairs, 
 		if((rc = S.d_code_off.ensure(S.n)) != PCR_OK) return rc;
 		HIP_TRY(hipMemcpyAsync(S.d_code_off.p, code_off.data(), S.n*sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
 		HIP_TRY(hipStreamSynchronize(ctx->stream));
-		hipLaunchKernelGGL(k_seq_codes, dim3(8, S.n), dim3(256), 0, ctx->stream, S.nib.p, S.d_blk_off.p, S.d_len.p, S.d_code_off.p, S.n, S.codes.p);
+		if((uint64_t)S.n*SEQ_CODE_SLICES >= (uint64_t(1) << 31)){ g_err = "pcr_multiplex_match: too many sequences in the set"; return PCR_ERR_CAPACITY; }
+		hipLaunchKernelGGL(k_seq_codes, dim3(S.n*SEQ_CODE_SLICES), dim3(256), 0, ctx->stream, S.nib.p, S.d_blk_off.p, S.d_len.p, S.d_code_off.p, S.n, S.codes.p);
 		HIP_TRY(hipGetLastError());
 		S.have_codes = true;
 	}

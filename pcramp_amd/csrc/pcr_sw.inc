@@ -197,14 +197,16 @@ __global__ void k_entry_codes(const DevEntry *__restrict__ db, uint32_t n, uint3
 	if(k == 0) lens[e] = (uint8_t)len;
 }
 
-// nibble store -> one code byte per base (templates of find_multiplex_background_match)
+// nibble store -> one code byte per base (templates of find_multiplex_background_match).  SEQ_CODE_SLICES workgroups per
+// sequence, all in the grid's x extent: the set grows with every accepted assay's amplicons and passes the 65 535 a y extent holds.
+constexpr uint32_t SEQ_CODE_SLICES = 8;
 __global__ void k_seq_codes(const uint32_t *__restrict__ nib, const uint64_t *__restrict__ blk_off, const uint64_t *__restrict__ len,
 	const uint64_t *__restrict__ code_off, uint32_t n_seq, uint8_t *__restrict__ codes)
 {
-	const uint32_t s = blockIdx.y;
+	const uint32_t s = blockIdx.x/SEQ_CODE_SLICES, slice = blockIdx.x % SEQ_CODE_SLICES;
 	if(s >= n_seq) return;
 	const uint64_t L = len[s];
-	for(uint64_t p = (uint64_t)blockIdx.x*blockDim.x + threadIdx.x;p < L;p += (uint64_t)gridDim.x*blockDim.x){
+	for(uint64_t p = (uint64_t)slice*blockDim.x + threadIdx.x;p < L;p += (uint64_t)SEQ_CODE_SLICES*blockDim.x){
 		const uint32_t w = nib[blk_off[s]*4 + (p >> 3)];
 		codes[code_off[s] + p] = (uint8_t)((w >> ((p & 7)*4)) & 0xF);
 	}

@@ -17,7 +17,9 @@ def _text(word):
     return W.text_from_codes(np.array([c for c in W.slots_from_word(word) if c], dtype=np.uint8))
 
 
-def _expected(oracle, ts, ams, pool, trials, thr_t, bg_thr, taq):
+def _expected(oracle, ts, ams, pool, trials, thr_t, bg_thr, taq, amp_min=80, amp_max=200):
+    """(compatible, multiplex_cover, pool_cover) per trial from the oracle's pieces.  ts: the target session (words selected),
+    ams: the session of the accepted amplicons, whose weights the multiplex cover sums (float32, in sequence order)."""
     comp, mcov, pcov = [], [], []
     for t in trials:
         ok = all(bool(oracle.multiplex_compatible(p, t)) for p in pool)
@@ -26,8 +28,8 @@ def _expected(oracle, ts, ams, pool, trials, thr_t, bg_thr, taq):
             mcov.append(0.0)
             pcov.append(0.0)
             continue
-        mcov.append(float(np.float32(ams.multiplex_match(t, bg_thr, taq).sum())) if ams.n else 0.0)   # weights 1
-        _, amps = ts.collect_amplicons(t, thr_t, 80, 200)
+        mcov.append(float(np.float32(ams.weighted_coverage(ams.multiplex_match(t, bg_thr, taq)))) if ams.n else 0.0)
+        _, amps = ts.collect_amplicons(t, thr_t, amp_min, amp_max)
         if not amps or not pool:
             pcov.append(0.0)
             continue
