@@ -240,10 +240,8 @@ __global__ __launch_bounds__(SCAN2_THREADS) void k_scan2(
 // Host side: lookup tables + bias planes for all orientation groups.
 struct Scan2Tables {
 	int nslot, klo;
-	uint32_t gw;             // counter words per group: 8 (256 orientations).  PCRAMP_SCAN2_GW=4 (A/B): five to eight words in ONE group make
-	                         // the kernel hold 114 - 120 VGPRs (4 waves per SIMD); two groups of four words hold 50 each (8 waves per SIMD) for one
-	                         // more pass over the positions -- measured at C3 (7 words): 0.548 against 0.524 ms per select_words, at 16 words
-	                         // 2.23 against 2.09: the scan is bound by its instructions, not by the waves it has to hide the LDS rows behind
+	uint32_t gw;             // counter words per group: 8 (256 orientations).  Groups of 4 words (50 VGPRs instead of 114 - 120, twice the waves, one
+	                         // more pass over the positions) measured slower: 0.548 against 0.524 ms per select_words at C3 (7 words), 2.23 against 2.09 at 16
 	uint32_t n_groups;       // groups of gw words
 	uint32_t last_words;     // words used by the last group (1..gw)
 	std::vector<uint32_t> tab, bias;
@@ -259,8 +257,7 @@ inline void build_scan2_tables(const std::vector<pcrhost::Candidate> &cand, cons
 	if((occ & ~0x1FFFFFF8u) == 0){ T.nslot = 26; T.klo = 3; }
 	else{ T.nslot = 32; T.klo = 0; }
 	const uint32_t n_words = (n_or + 31)/32;
-	static const int forced_gw = getenv("PCRAMP_SCAN2_GW") ? atoi(getenv("PCRAMP_SCAN2_GW")) : 0;   // A/B
-	T.gw = (forced_gw == 4) ? 4u : 8u;
+	T.gw = 8;
 	T.n_groups = (n_words + T.gw - 1)/T.gw;
 	T.last_words = n_words - (T.n_groups - 1)*T.gw;
 	T.tab.assign((size_t)T.n_groups*T.nslot*16*8, 0u);

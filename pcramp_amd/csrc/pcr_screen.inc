@@ -346,7 +346,8 @@ __global__ __launch_bounds__(PMS_THREADS) void k_pair_moves_seq(const DevEntry *
 // demand); block 0 publishes the pass's counters (overflow flag, fill) at kernel start, when every scan is
 // complete.  The has_split range error (sequence.cpp:306, unreachable with clamped amplicon ends) is noted in
 // counters[1] but, as with pcr_amplify_device, the asynchronous entry points do not report it.
-// waves per workgroup: a template parameter (r02: 16 waves 70.3 vs 68.2 us per pass at C2; 4 the same as 8; PCRAMP_POST_WAVES=16 for the A/B)
+// waves per workgroup: a template parameter (r02: 16 waves 70.3 vs 68.2 us per pass at C2; 4 the same as 8; r03: 4, 8 and 16
+// within the noise, profiles/dbg/r03_ab_post_waves.txt): the pass launches 8
 constexpr uint32_t POST_CAP = 64, POST_MASK_WORDS = 4;
 // (what the match and pair steps read of an entry: half a DevEntry -- 30 KB of LDS per workgroup instead of 42, four workgroups =
 // all 32 waves of a CU resident instead of three)

@@ -359,6 +359,62 @@ def test_three_forms_of_the_seed_pass_agree(oracle, thr_t):
             d.close()
 
 
+# (environment of the handle, optimize_5 / optimize_3, select threshold as target threshold x 0.9, the form the pass must report)
+FORM_CASES = [
+    ({}, 0, 1.0, "seed3"),
+    ({"PCRAMP_SEED3": 0}, 0, 1.0, "seed2"),
+    ({"PCRAMP_IRR_INDEX": 0}, 0, 1.0, "seed2"),
+    ({"PCRAMP_SEED": 1}, 0, 1.0, "seed1-dev"),
+    ({"PCRAMP_SEED": 1, "PCRAMP_SEED_TABLES": "host"}, 0, 1.0, "seed1-host"),
+    ({}, 1, 1.0, "seed1-host"),
+    ({"PCRAMP_SCAN": 2}, 0, 1.0, "bitsliced"),
+    ({"PCRAMP_SCAN": 1}, 0, 1.0, "popcount"),
+    ({}, 0, 0.8, "bitsliced"),              # 0.72, the background threshold of C3: no orientation has a seed structure
+]
+
+
+def test_the_pass_reports_the_form_that_ran(oracle, capfd):
+    """Which scan serves the seeded orientations of a pass is decided in one place (choose_scan_form) and reported in the
+    'scan plan' debug line: the default pass must stay with the third form, and every switch the other tests use to reach a
+    form must still reach it.  Then three fused passes on the default handle: the first stages through k_stage, the third
+    is lean exactly when the handle's staging mode says so, and every pass (replays after a bucket overflow included) keeps
+    the third form."""
+    import torch
+    rng = random.Random(4242)
+    seqs, pairs = _border_case(rng, oracle)
+    for env, opt, thr_t, want in FORM_CASES:
+        dev = _screener_env(PCRAMP_DEBUG=1, **env)
+        try:
+            dev.load_texts(seqs, [1.0] * len(seqs))
+            capfd.readouterr()
+            dev.select_words(pairs, float(np.float32(thr_t) * np.float32(0.9)), 18, opt, opt, count=False)
+            forms = re.findall(r"scan plan: form=([\w-]+),", capfd.readouterr().err)
+            print(env, opt, thr_t, "->", forms)
+            assert forms and set(forms) == {want}, (env, opt, thr_t)
+        finally:
+            dev.close()
+    dev = _screener_env(PCRAMP_DEBUG=1)
+    try:
+        dev.load_texts(seqs, [1.0] * len(seqs))
+        fused = pairs[:46]      # (an even number: with 15 sequences a pair's bitset is 8 bytes, and the fused tail wants 16-byte multiples)
+        o = torch.full((2, len(fused), int(dev.bitset_words())), -1, dtype=torch.int64, device="cuda:0")
+        capfd.readouterr()
+        for _ in range(3):
+            dev.screen_device(fused, float(np.float32(0.9)), o[0].data_ptr(), o[1].data_ptr(), 1.0, 1.0, 80, 200, False)
+        dev.synchronize()
+        torch.cuda.synchronize()
+        err = capfd.readouterr().err
+        staging = re.findall(r"staging: (lean|k_stage)", err)
+        print("staging of three fused passes:", staging, "handle:", dev.staging_mode())
+        # (the three enqueued passes come first; where one of them overflowed its 64-slot buckets, synchronize() replays it and
+        # the later ones synchronously, with lines of their own behind these)
+        forms = re.findall(r"scan plan: form=([\w-]+),", err)
+        assert len(forms) >= 3 and set(forms) == {"seed3"}
+        assert len(staging) == len(forms) and staging[0] == "k_stage" and staging[2] == dev.staging_mode()
+    finally:
+        dev.close()
+
+
 def _random_case(rng, oracle):
     """A small random screen: a few sequence families (some with IUPAC codes, some with EOS inside), primers cut from them
     (some mutated, some with IUPAC positions, some unrelated), a select threshold between 0.81 and 1."""
