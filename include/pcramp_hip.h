@@ -104,6 +104,32 @@ int pcr_select_words(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_
 	int optimize_5, int optimize_3, float threshold, uint32_t min_oligo_length,
 	uint64_t *n_entries_out);
 
+/* The all-sites fill of a set's word DB: EVERY binding site of each oligo, not the best per sequence.
+ * pcr_select_words keeps, per (oligo, sequence), only the words that attain the maximum match count (the threshold is a
+ * floor, select_words.cpp:100-117); a weaker site on a sequence that also holds a better site of the same oligo does not
+ * exist for the consumers of that DB.  This call fills the DB the way the reference fills its multiplex DB (pack, then
+ * match_words, main.cpp:989-1001): for every ACTIVE sequence of `which`, every entry Sequence::pack(min_oligo_length) emits
+ * -- regular windows on both strands, the centred partial words at the sequence ends and around EOS, under the handle's
+ * degeneracy / GC filters -- is kept when at least one oligo c of the batch (F and R of every pair; no 5'/3' shift
+ * candidates) has (c & word) >= unsigned(c.size()*threshold), the float product and truncation of select_words.cpp:83.
+ * The result REPLACES the set's word DB in the layout pcr_select_words leaves (entries unique, per sequence ordered by
+ * (loc, strand, kind, ord)), so pcr_get_entries, pcr_amplify, pcr_collect_amplicons, pcr_pool_products,
+ * pcr_background_match, pcr_move_coverage, ... read it as they read a selected DB.  n_entries_out as pcr_select_words.
+ *   - Synchronous; pending pcr_screen_device passes are drained first (their buffers are final when this call returns).
+ *   - Errors as pcr_select_words (PCR_ERR_ARG: unknown set, min_oligo_length outside [1,32] -- checked before the handle --,
+ *     NULL handle, NULL pairs with n_pairs > 0); PCR_SET_MULTIPLEX is refused with PCR_ERR_ARG.
+ *   - n_pairs == 0 or an empty set: an empty DB, PCR_OK.
+ *   - The per-sequence buckets grow and shrink on the ladder of pcr_select_words (64 ... 65 536 slots; a window that
+ *     several oligos match counts once per strand and launch group of 128 pairs).  More sites than that in one sequence,
+ *     or buckets that would not fit the device: PCR_ERR_CAPACITY, the set is left without a DB and its buckets start
+ *     at 64 slots again.
+ *   - On a handle with a target shard attached (pcr_shard_targets) the call works on this rank's block and makes no
+ *     collective, as pcr_collect_amplicons.
+ *   - The consumers floor at collect_threshold SQUARED (pcr_assay.cpp:31-32).  To give a consumer that will be called
+ *     with threshold t every site it could use, pass (float)t*(float)t here. */
+int pcr_select_sites(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs,
+	float threshold, uint32_t min_oligo_length, uint64_t *n_entries_out);
+
 /* Copy the current word DB to the host (parity tests; the reference's target_db). Returns the
  * number of entries (may exceed cap; only cap are written) or <0. */
 int64_t pcr_get_entries(pcr_ctx *ctx, pcr_set which, pcr_entry *out, uint64_t cap);

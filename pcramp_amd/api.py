@@ -113,7 +113,7 @@ _LIB = None
 # every symbol include/pcramp_hip.h declares
 ABI_SYMBOLS = [
     "pcr_last_error", "pcr_create", "pcr_destroy", "pcr_load_sequences", "pcr_set_active", "pcr_split", "pcr_split_many",
-    "pcr_select_words", "pcr_get_entries", "pcr_amplify", "pcr_amplify_device", "pcr_screen_device", "pcr_move_coverage", "pcr_coverage_from_bits",
+    "pcr_select_words", "pcr_select_sites", "pcr_get_entries", "pcr_amplify", "pcr_amplify_device", "pcr_screen_device", "pcr_move_coverage", "pcr_coverage_from_bits",
     "pcr_weighted_coverage", "pcr_num_sequences", "pcr_bitset_words", "pcr_profile_enable", "pcr_profile_read", "pcr_profile_read_kernel",
     "pcr_synchronize", "pcr_host_irregular_words", "pcr_host_window_valid", "pcr_host_candidates",
     "pcr_host_orientation_seeds", "pcr_host_move_trials",
@@ -159,6 +159,7 @@ def load_library():
     L.pcr_split.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64]
     L.pcr_select_words.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_float,
                                    C.c_uint32, C.POINTER(C.c_uint64)]
+    L.pcr_select_sites.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.c_uint64)]
     L.pcr_get_entries.restype = C.c_int64
     L.pcr_get_entries.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
     L.pcr_amplify.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(AmplifyArgs), C.c_void_p,
@@ -509,6 +510,17 @@ class Screener:
                                             threshold, min_oligo_length, C.byref(n) if count else None))
         return n.value if count else None
 
+    def select_sites(self, pairs, threshold, min_oligo_length=18, which=TARGET, count=True):
+        """The all-sites word DB (pcr_select_sites): every pack entry of every active sequence that some oligo of `pairs`
+        matches at or above unsigned(size * threshold) -- every binding site, where select_words keeps the best per
+        (oligo, sequence).  REPLACES the set's word DB; every reader of that DB then sees all sites.  A consumer called with
+        threshold t floors at t squared: pass float32(t)**2 here.  count=False skips the DB size and returns None."""
+        a = pairs if isinstance(pairs, np.ndarray) else W.pairs_array(pairs)
+        n = C.c_uint64(0)
+        self._check(self.L.pcr_select_sites(self.h, which, a.ctypes.data, a.shape[0], threshold, min_oligo_length,
+                                            C.byref(n) if count else None))
+        return n.value if count else None
+
     def entries(self, which=TARGET):
         n = self.L.pcr_get_entries(self.h, which, None, 0)
         if n < 0:
@@ -678,10 +690,21 @@ class Screener:
         oligo_id[2i] / oligo_id[2i + 1] is the distinct-oligo id of F / R of pool pair i (ids in order of first
         appearance).  A record is an amplicon with plus_oligo in the plus-strand role and minus_oligo in the minus-strand
         role, as collect_amplicons reports it for that pair in orientation 0; `intended` marks the combinations that are
-        pool pairs.  select=True first runs select_words(pool, float32(threshold)**2, which=which): this REPLACES the
-        set's word DB.  select=False uses the DB as it stands (the one collect_amplicons and find_target_match read)."""
-        if select:
-            self.select_words(pool, float(np.float32(threshold) * np.float32(threshold)), which=which)
+        pool pairs.  `select` chooses the sites the products are formed from:
+          True   first runs select_words(pool, float32(threshold)**2, which=which): per (oligo, sequence) only the sites
+                 with the highest match count -- a weaker site of an oligo on a sequence that also holds a better one is
+                 not seen;
+          "all"  first runs select_sites(pool, float32(threshold)**2, which=which): every site a product at this threshold
+                 can use (the multiplex check before ordering oligos wants this one);
+          False  uses the DB as it stands (the one collect_amplicons and find_target_match read).
+        True and "all" REPLACE the set's word DB."""
+        thr2 = float(np.float32(threshold) * np.float32(threshold))
+        if isinstance(select, str):
+            if select != "all":
+                raise ValueError("pool_products: select must be True, False or 'all'")
+            self.select_sites(pool, thr2, which=which)
+        elif select:
+            self.select_words(pool, thr2, which=which)
         a = W.pairs_array(pool)
         ids = np.zeros(max(2 * len(pool), 1), np.uint32)
         while True:

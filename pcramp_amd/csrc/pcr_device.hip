@@ -451,7 +451,8 @@ __device__ void materialise_entry(uint64_t k, const uint4 *__restrict__ planes, 
 	}
 }
 
-template<int WAVES>
+// ALL (pcr_select_sites): every hit is kept -- no arg-max filter, best[] is not read (it may be NULL).
+template<int WAVES, bool ALL = false>
 __global__ __launch_bounds__(64*WAVES) void k_finalize(const Hit *__restrict__ hits, const uint32_t *__restrict__ seq_count,
 	uint32_t cap, const uint32_t *__restrict__ best, uint32_t ncand, const uint4 *__restrict__ planes,
 	const uint64_t *__restrict__ blk_off, const IrrDev *__restrict__ irr, const uint32_t *__restrict__ irr_off,
@@ -474,7 +475,8 @@ __global__ __launch_bounds__(64*WAVES) void k_finalize(const Hit *__restrict__ h
 		uint64_t k = ~0ull;
 		if(i < n){
 			const Hit h = hits[(size_t)seq*cap + i];
-			if(((epoch << 8) | h.cnt) == best[(size_t)seq*ncand + h.cand]) k = h.key;
+			if constexpr (ALL) k = h.key;
+			else if(((epoch << 8) | h.cnt) == best[(size_t)seq*ncand + h.cand]) k = h.key;
 		}
 		fin_keys[i] = k;
 	}
@@ -527,6 +529,7 @@ __global__ __launch_bounds__(64*WAVES) void k_finalize(const Hit *__restrict__ h
 // 256-thread workgroup per touched sequence.  Slow path; exists so that such inputs are not refused.
 constexpr int FINBIG_THREADS = 256;
 constexpr uint32_t MAX_BUCKET_CAP_GLOBAL = 65536;
+template<bool ALL = false>
 __global__ __launch_bounds__(FINBIG_THREADS) void k_finalize_big(const Hit *__restrict__ hits, const uint32_t *__restrict__ seq_count,
 	uint32_t cap, const uint32_t *__restrict__ best, uint32_t ncand, const uint4 *__restrict__ planes,
 	const uint64_t *__restrict__ blk_off, const IrrDev *__restrict__ irr, const uint32_t *__restrict__ irr_off,
@@ -544,7 +547,8 @@ __global__ __launch_bounds__(FINBIG_THREADS) void k_finalize_big(const Hit *__re
 		uint64_t k = ~0ull;
 		if(i < n){
 			const Hit h = hits[(size_t)seq*cap + i];
-			if(((epoch << 8) | h.cnt) == best[(size_t)seq*ncand + h.cand]) k = h.key;
+			if constexpr (ALL) k = h.key;
+			else if(((epoch << 8) | h.cnt) == best[(size_t)seq*ncand + h.cand]) k = h.key;
 		}
 		fin_keys[i] = k;
 	}
@@ -1827,6 +1831,7 @@ int pcr_split(pcr_ctx *ctx, pcr_set which, uint32_t seq, uint64_t pos)
 } // extern "C"
 
 #include "pcr_select.inc"
+#include "pcr_select_sites.inc"
 
 extern "C" {
 

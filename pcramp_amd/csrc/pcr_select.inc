@@ -741,7 +741,8 @@ void launch_finalize(K kernel, dim3 grid, dim3 block, size_t lds, pcr_ctx *ctx, 
 		S.irr_off.p, S.db.p, S.d_seg_hi, sink.counters, sink.epoch, S.touched.p, extra...);
 }
 // k_touched, the k_finalize the bucket size asks for, then the counters to the host's mailbox: by k_publish, or -- fused pass --
-// by the k_match that follows.
+// by the k_match that follows.  ALL: the all-sites pass (pcr_select_sites.inc), whose finalize keeps every hit.
+template<bool ALL = false>
 int plain_tail(pcr_ctx *ctx, SeqSet &S, const HitSink &sink, bool async, FusedAmp *fa)
 {
 	int rc;
@@ -749,11 +750,11 @@ int plain_tail(pcr_ctx *ctx, SeqSet &S, const HitSink &sink, bool async, FusedAm
 	HIP_TRY(hipGetLastError());
 	S.touched_built = true;
 	uint32_t np2 = 1; while(np2 < sink.cap) np2 <<= 1;
-	if(np2 <= 1024) launch_finalize(k_finalize<FIN_WAVES>, dim3((S.n + FIN_WAVES - 1)/FIN_WAVES), dim3(64*FIN_WAVES), (size_t)FIN_WAVES*np2*sizeof(uint64_t), ctx, S, sink);
-	else if(np2 <= MAX_BUCKET_CAP) launch_finalize(k_finalize<1>, dim3(S.n), dim3(64), (size_t)np2*sizeof(uint64_t), ctx, S, sink);
+	if(np2 <= 1024) launch_finalize(k_finalize<FIN_WAVES, ALL>, dim3((S.n + FIN_WAVES - 1)/FIN_WAVES), dim3(64*FIN_WAVES), (size_t)FIN_WAVES*np2*sizeof(uint64_t), ctx, S, sink);
+	else if(np2 <= MAX_BUCKET_CAP) launch_finalize(k_finalize<1, ALL>, dim3(S.n), dim3(64), (size_t)np2*sizeof(uint64_t), ctx, S, sink);
 	else{
 		if((rc = ctx->fin_scratch.ensure((size_t)S.n*np2)) != PCR_OK) return rc;
-		launch_finalize(k_finalize_big, dim3(S.n), dim3(FINBIG_THREADS), 0, ctx, S, sink, ctx->fin_scratch.p);
+		launch_finalize(k_finalize_big<ALL>, dim3(S.n), dim3(FINBIG_THREADS), 0, ctx, S, sink, ctx->fin_scratch.p);
 	}
 	HIP_TRY(hipGetLastError());
 	// the only host synchronisation of the pass: overflow flag + DB size, through the mapped mailbox
