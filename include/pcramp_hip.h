@@ -464,6 +464,60 @@ typedef struct {
 int64_t pcr_pool_products(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
 	int32_t amp_min, int32_t amp_max, uint32_t *oligo_id, pcr_product *out, uint64_t cap);
 
+/* ---- Per-site duplex Tm: every binding site of a panel's oligos in the word DB, melted */
+
+/* One binding site of one oligo (48 bytes). */
+typedef struct {
+	uint32_t oligo;                     /* distinct-oligo id (see oligo_id) */
+	uint32_t sequence;
+	int32_t  loc5, loc3;                /* WordMatch::template_loc5 / template_loc3 (sequence.h:57-75) with the oligo's start() / stop() */
+	uint32_t strand;                    /* 1: the oligo in the plus-strand role (a product's begin side), 2: minus */
+	uint32_t matches;                   /* slots of the oligo the site's word matches: Word & Word of the entry the target is read from */
+	uint32_t n_expansions;              /* non-degenerate expansions of the oligo (Word::degeneracy()) */
+	uint32_t flags;                     /* PCR_SITE_* */
+	float    tm_max, tm_min;            /* highest / lowest heterodimer Tm over the expansions, degrees C */
+	float    dH, dS;                    /* NucCruc::delta_H / delta_S of the expansion that attains tm_max (the lowest-numbered one on a tie) */
+} pcr_site;
+
+#define PCR_SITE_NO_TM 1u               /* the site's template bases cannot be spelled in A, C, G, T: every float is 0 */
+#define PCR_SITE_MAX_EXPANSIONS 256     /* an oligo with more expansions is refused */
+
+/* Every binding site of every distinct oligo of a panel over the word DB of the last pcr_select_words or pcr_select_sites
+ * on `which`, with the duplex Tm of the oligo against the template strand it anneals to there.
+ *   Sites.  The panel's 2*n_pairs oligo words get distinct ids in order of first appearance, as in pcr_pool_products;
+ * oligo_id[2*n_pairs] receives them.  A site of oligo c is a (sequence, loc, strand) of the DB, strand 1 or 2, sequence
+ * active, at which some entry e has (e.w & c) >= unsigned(c.size() * threshold * threshold) -- the sites pcr_pool_products
+ * forms its products from.  loc5 / loc3 are template_loc5 / template_loc3 of that entry with c.start() / c.stop(): a
+ * product's begin is its plus site's loc5 and its end is its minus site's loc3, exactly (the entries' own loc is used as it
+ * is, including the + 1 that Sequence::pack gives the partial words at a sequence's tail).
+ *   Template bases.  They are read from the entry's word, not from the sequence.  T = slots c.start() - 1 .. c.stop() + 1
+ * clipped to 0 .. 31: the oligo's slots and one flanking slot on either side where the word has one (NucCruc turns a
+ * flanking base into a dangling end).  Where several entries share the site and match c, the one with the most occupied
+ * slots in T is read (on a tie the one whose slot masks (A, C, G, T) compare lowest); `matches` is that entry's count.
+ * Empty slots are dropped from both ends of T.  If a slot left is empty or holds more than one base, flags =
+ * PCR_SITE_NO_TM and tm_max = tm_min = dH = dS = 0.  Otherwise the target is the complement of those bases read from the
+ * highest slot to the lowest: the 5'->3' spelling of the strand the oligo anneals to.
+ *   What a caller must know about EOS splits.  No word of the DB has an empty slot inside: Word::push_back writes the next
+ * base over an EOS (word.cpp:32-41), so a word over a pcr_split joins the bases on either side of it.  The empty-slot half
+ * of the rule above is therefore never met on a DB this library builds, and PCR_SITE_NO_TM in practice means an ambiguity
+ * code.  A site straddling a split is reported as the weaker site its joined word is, with the Tm of a target that does
+ * not exist in the template as one molecule, and WITHOUT a flag: a caller that splits sequences and cares must compare
+ * loc5 .. loc3 with its own split positions.
+ *   Thermodynamics.  For each non-degenerate expansion q of c in the order of Word::begin() / next():
+ * NucCruc::approximate_tm_heterodimer with query q, that target, salt = args->salt and
+ * strand(args->primer_strand / c.degeneracy(), template_strand) by the two-concentration rule (nuc_cruc.h:818-838);
+ * template_strand = 0 is legal.  Only salt and primer_strand of args are read.
+ *   Records are unique and sorted by (oligo, sequence, loc5, strand).  Returns their number or a negative error; if it
+ * exceeds cap the contents of out are unspecified (cap = 0: count only, no thermodynamics is run).  n_pairs = 0 returns 0.
+ * PCR_ERR_ARG (checked before the handle): unknown set or PCR_SET_MULTIPLEX, null pointers, n_pairs > PCR_POOL_MAX_PAIRS,
+ * a negative concentration or a zero strand concentration of a duplex (primer_strand and template_strand both 0), salt
+ * outside [1e-6, 1], an oligo that is empty, has a hole between its ends or more than
+ * PCR_SITE_MAX_EXPANSIONS expansions; then a null handle.  PCR_ERR_STATE without a word DB; PCR_ERR_CAPACITY for 2^31 or
+ * more sites or (site, expansion) jobs.  Changes nothing other calls read.  On a handle with a target shard attached,
+ * sequence indices are local to the rank's block and no collective is made (as pcr_pool_products). */
+int64_t pcr_site_tm(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs, float threshold,
+	const pcr_thermo_args *args, float template_strand, uint32_t *oligo_id, pcr_site *out, uint64_t cap);
+
 /* ---- The multiplex compatibility filter of the trial loop (main.cpp:744-803), batched over the trial assays */
 
 typedef struct {

@@ -65,6 +65,13 @@ PRODUCT_DTYPE = np.dtype([("plus_oligo", np.uint32), ("minus_oligo", np.uint32),
                           ("end", np.int32), ("inner_start", np.int32), ("inner_length", np.int32), ("intended", np.uint32)])
 POOL_MAX_PAIRS = 1024                         # PCR_POOL_MAX_PAIRS
 
+# pcr_site: one binding site of one oligo with its duplex Tm (Screener.site_tm)
+SITE_DTYPE = np.dtype([("oligo", np.uint32), ("sequence", np.uint32), ("loc5", np.int32), ("loc3", np.int32),
+                       ("strand", np.uint32), ("matches", np.uint32), ("n_expansions", np.uint32), ("flags", np.uint32),
+                       ("tm_max", np.float32), ("tm_min", np.float32), ("dH", np.float32), ("dS", np.float32)])
+SITE_NO_TM = 1                                # PCR_SITE_NO_TM
+SITE_MAX_EXPANSIONS = 256                     # PCR_SITE_MAX_EXPANSIONS
+
 
 class SamplerArgs(C.Structure):
     _fields_ = [("primer_min", C.c_int32), ("primer_max", C.c_int32), ("amp_min", C.c_int32), ("amp_max", C.c_int32),
@@ -120,7 +127,7 @@ ABI_SYMBOLS = [
     "pcr_sw_align_words", "pcr_background_match", "pcr_multiplex_match",
     "pcr_thermo", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
-    "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products",
+    "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -209,6 +216,9 @@ def load_library():
     L.pcr_pool_products.restype = C.c_int64
     L.pcr_pool_products.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_uint64]
+    L.pcr_site_tm.restype = C.c_int64
+    L.pcr_site_tm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.POINTER(ThermoArgs), C.c_float, C.c_void_p,
+                              C.c_void_p, C.c_uint64]
     L.pcr_multiplex_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.pcr_multiplex_coverage.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_void_p]
     L.pcr_host_pool_overlaps.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -716,6 +726,61 @@ class Screener:
             if n <= cap:
                 return ids[:2 * len(pool)].copy(), out[:n].copy()
             cap = int(n)
+
+    def site_tm(self, panel, threshold=1.0, salt=0.05, primer_strand=9e-7, template_strand=0.0, which=TARGET, select=False,
+                cap=1 << 16):
+        """Every binding site of every oligo of the panel in the word DB, melted (pcr_site_tm) -> (oligo_id
+        uint32[2 * len(panel)], records: SITE_DTYPE array sorted by (oligo, sequence, loc5, strand)).
+
+        oligo_id is pool_products' numbering.  A record is one site of one oligo: where it is (loc5 / loc3: a product's
+        begin is its plus site's loc5, its end is its minus site's loc3), how many slots match, and the highest / lowest
+        heterodimer Tm of the oligo's expansions against the template strand they anneal to there, with dH / dS of the
+        highest; flags & SITE_NO_TM: the template bases hold an ambiguity code or an end of sequence and were not melted.
+        The strand concentration is NucCruc's two-strand rule of (primer_strand / degeneracy, template_strand).
+        `select` as for pool_products: True runs select_words first, "all" runs select_sites (both REPLACE the set's word
+        DB), False reads the DB as it stands."""
+        thr2 = float(np.float32(threshold) * np.float32(threshold))
+        if isinstance(select, str):
+            if select != "all":
+                raise ValueError("site_tm: select must be True, False or 'all'")
+            self.select_sites(panel, thr2, which=which)
+        elif select:
+            self.select_words(panel, thr2, which=which)
+        a = W.pairs_array(panel)
+        ids = np.zeros(max(2 * len(panel), 1), np.uint32)
+        args = self._targs(salt, primer_strand, 0.0, 0.0, 0.0, 0.0)
+        while True:
+            out = np.zeros(max(cap, 1), SITE_DTYPE)
+            n = self.L.pcr_site_tm(self.h, which, a.ctypes.data, len(panel), float(threshold), C.byref(args), float(template_strand),
+                                   ids.ctypes.data, out.ctypes.data, cap)
+            if n < 0:
+                raise PcrError(_err(self.L))
+            if n <= cap:
+                return ids[:2 * len(panel)].copy(), out[:n].copy()
+            cap = int(n)
+
+    @staticmethod
+    def product_tm(products, sites):
+        """tm_max of each product's plus site and of its minus site -> (float32[n], float32[n]): a join of pool_products'
+        records with site_tm's on (oligo, sequence, loc5, strand 1) and (oligo, sequence, loc3, strand 2).  Raises if a
+        product has no site record, which cannot happen when both calls saw the same DB, panel and threshold."""
+        def key(oligo, sequence, loc):
+            return np.stack([np.asarray(oligo, np.int64), np.asarray(sequence, np.int64), np.asarray(loc, np.int64)], axis=1)
+        out = []
+        for side, strand, site_loc, prod_loc in (("plus", 1, "loc5", "begin"), ("minus", 2, "loc3", "end")):
+            tab = sites[sites["strand"] == strand]
+            have = key(tab["oligo"], tab["sequence"], tab[site_loc])
+            want = key(products[side + "_oligo"], products["sequence"], products[prod_loc])
+            _, inv = np.unique(np.concatenate([have, want]), axis=0, return_inverse=True)
+            inv = inv.reshape(-1)
+            where = np.full(int(inv.max()) + 1 if inv.size else 1, -1, np.int64)
+            where[inv[:len(have)]] = np.arange(len(have))
+            at = where[inv[len(have):]]
+            if (at < 0).any():
+                raise PcrError("product_tm: %d products have no %s-site record (different DB, panel or threshold?)"
+                               % (int((at < 0).sum()), side))
+            out.append(tab["tm_max"][at].astype(np.float32))
+        return out[0], out[1]
 
     def multiplex_load(self, seqs, min_oligo_length=18):
         """The multiplex background keys (main.cpp:989-1001) from amplicon texts -> number of unique keys."""

@@ -27,6 +27,7 @@
 //   k_pair_moves, k_pair_moves_batch : the same sweep for the trial words of a local-search move (optimize_pcr.cpp; pcr_optimize.inc)
 //   k_sw, k_sw_words, k_bg_*, k_mx_* : SeqOverlap Smith-Waterman and the background / multiplex screens (pcr_sw.inc)
 //   thermo::k_thermo_wave  : NucCruc (pcr_thermo.inc)
+//   k_site_tm, k_site_reduce : the same engine over the binding sites of the word DB, jobs built on the device (pcr_site_tm.inc)
 // Host side in the same library: pcr_optimize.inc (optimize() batched over trial assays), pcr_sampler.inc, pcr_multiplex.inc,
 // pcr_multiplex_screen.inc, pcr_writers.inc; pcr_exchange.inc: the bitset all-gather over RCCL.
 #include <hip/hip_runtime.h>
@@ -757,6 +758,9 @@ struct pcr_ctx {
 	DevBuf<Planes> mx_keys; uint32_t mx_n_keys = 0; DevBuf<uint32_t> mx_count;   // multiplex background: unique words of the accepted amplicons (pcr_multiplex.inc)
 	// pcr_pool_products (pcr_pool.inc): oligo table + intended bitmap, per-entry / per-item counts and offsets, items, records, sort keys
 	DevBuf<uint8_t> pool_in, pool_tmp; DevBuf<uint32_t> pool_cnt, pool_ord; DevBuf<uint64_t> pool_eoff, pool_ioff, pool_keys; DevBuf<uint2> pool_items; DevBuf<pcr_product> pool_rec;
+	// pcr_site_tm (pcr_site_tm.inc): oligo tables, per-entry counts and offsets, items, per-item job offsets, per-job results, sort keys and order, records
+	DevBuf<uint8_t> site_in, site_tmp; DevBuf<uint32_t> site_cnt, site_ord, site_flag; DevBuf<uint64_t> site_eoff, site_joff, site_keys; DevBuf<uint2> site_items; DevBuf<float4> site_res; DevBuf<pcr_site> site_rec;
+	bool site_attr_set = false;
 	// an attached target shard (pcr_shard_targets, pcr_shard.inc): PCR_SET_TARGET holds rows [shard_first, shard_first + n) of
 	// shard_n_total, and the local search combines target coverage over shard_comm; NULL = not sharded
 	pcr_comm *shard_comm = nullptr; uint64_t shard_first = 0, shard_n_total = 0; int shard_mode = 0;
@@ -1576,6 +1580,7 @@ void pcr_destroy(pcr_ctx *ctx)
 	for(int k = 0;k < 2;++k){ if(ctx->sw_done[k]) (void)hipEventDestroy(ctx->sw_done[k]); }
 	ctx->oligos.release(); ctx->sw_jobs.release(); ctx->sw_out.release(); ctx->sw_q.release(); ctx->sw_qlen.release(); ctx->sw_t.release(); ctx->entry_codes.release(); ctx->entry_lens.release(); ctx->amp_recs.release(); ctx->amp_recs2.release(); ctx->amp_keys.release(); ctx->amp_pkeys.release(); ctx->amp_pair_start.release(); ctx->sort_tmp.release(); ctx->bg_pairs.release(); ctx->th_jobs.release(); ctx->th_out.release(); ctx->th_dg.release(); ctx->th_dbg.release(); ctx->split_where.release(); ctx->th_map.release(); ctx->th_bad.release(); ctx->mx_keys.release(); ctx->mx_count.release(); ctx->mx_amp.release(); ctx->opt_oligos.release(); ctx->opt_jobs.release(); ctx->opt_cov.release(); ctx->opt_loc.release(); ctx->opt_tasks.release();
 	ctx->pool_in.release(); ctx->pool_tmp.release(); ctx->pool_cnt.release(); ctx->pool_ord.release(); ctx->pool_eoff.release(); ctx->pool_ioff.release(); ctx->pool_keys.release(); ctx->pool_items.release(); ctx->pool_rec.release();
+	ctx->site_in.release(); ctx->site_tmp.release(); ctx->site_cnt.release(); ctx->site_ord.release(); ctx->site_flag.release(); ctx->site_eoff.release(); ctx->site_joff.release(); ctx->site_keys.release(); ctx->site_items.release(); ctx->site_res.release(); ctx->site_rec.release();
 	if(ctx->aux_stream){ (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
 	if(ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
 	delete ctx;
@@ -2155,4 +2160,5 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_entry_sw_thermo.inc"
 #include "pcr_multiplex_screen.inc"
 #include "pcr_pool.inc"
+#include "pcr_site_tm.inc"
 #include "pcr_writers.inc"
