@@ -9,7 +9,13 @@
  * Conventions: C linkage, opaque handle, plain pointers + sizes, caller-owned buffers, `int`
  * status (0 = ok, <0 = error; text via pcr_last_error(), thread-local).  No exceptions cross
  * the ABI.  A handle owns one GPU and one HIP stream and is not thread-safe (the reference's
- * equivalent rule: one NucCruc / SeqOverlap per OpenMP thread, main.cpp:533,702).
+ * equivalent rule: one NucCruc / SeqOverlap per OpenMP thread, main.cpp:533,702): it is used from
+ * one thread at a time.  The library runs one helper thread of its own per (device, stream) on which
+ * pcr_screen_device is used -- it stages and launches the passes the caller's thread has planned --
+ * shared by the handles created on that stream, started by their first such pass and joined when
+ * the last of them is destroyed.  It never calls back into the caller's code, and every entry point
+ * first waits for it to have launched the handle's queued passes (see pcr_screen_device;
+ * PCRAMP_LAUNCH_THREAD=0 at pcr_create: no helper thread, the caller's thread launches).
  * There is NO CPU fallback: every compute entry point fails if no gfx950 device is usable.
  */
 #ifndef PCRAMP_HIP_H
@@ -160,7 +166,16 @@ int pcr_amplify_device(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint3
  * before the pass has run: the device buffers are final only after pcr_synchronize() (or any other
  * entry point of the same handle) has returned PCR_OK -- that call inspects the counters of every
  * enqueued pass and, if a pass overflowed, replays it and the later ones with larger buckets into
- * the same buffers.  At most 6 passes are kept in flight. */
+ * the same buffers.  At most 6 passes are kept in flight.
+ * Threading: the call returns once the pass is QUEUED -- planned on the calling thread and handed to the
+ * stream's launcher thread, which writes its tables to the device and launches its kernels, in call order
+ * across all handles of the stream.  `pairs` and `args` are copied before the call returns; the two device
+ * buffers must stay valid until pcr_synchronize.  Stream order holds against later calls of this library
+ * only: synchronize (or call any other entry point of the handle) before enqueuing work of your own on
+ * the stream that reads the buffers.  An error met while launching (HIP, capacity) is returned by the
+ * NEXT call on the handle, with its text in that thread's pcr_last_error(); the handle's passes queued
+ * behind the failed one are dropped, not launched.  Passes that cannot be planned without device work (the
+ * first over a set, 5'/3' shift candidates, first-form tables, a tail that is not fused) run inline. */
 int pcr_screen_device(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs,
 	int optimize_5, int optimize_3, float select_threshold, uint32_t min_oligo_length,
 	const pcr_amplify_args *args, uint64_t *d_bits_fr, uint64_t *d_bits_rf);
@@ -213,6 +228,10 @@ int pcr_synchronize(pcr_ctx *ctx);
  * read-back round trip) and the pass has no staging launch; 0 = a staging kernel (k_stage) copies them out of mapped
  * host memory (PCRAMP_STAGE=kernel, no large BAR, or a failed probe). */
 int pcr_staging_mode(pcr_ctx *ctx);
+
+/* How many pcr_screen_device passes of this handle went through its stream's launcher thread (the others ran
+ * inline on the calling thread), and the largest number of them queued there at once.  Either pointer may be NULL. */
+int pcr_launcher_stats(pcr_ctx *ctx, uint64_t *passes_pipelined, uint32_t *max_queue_depth);
 
 /* ---- multi-GPU: the path's one exchange step.  Targets shard across ranks (one process per GPU,
  * contiguous blocks whose boundaries are multiples of 64 sequences, so every rank owns whole bitset words); the primer pairs are

@@ -129,7 +129,7 @@ ABI_SYMBOLS = [
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
-    "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode",
+    "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
     "pcr_shard_gather_bits", "pcr_shard_sampler_targets", "pcr_design_trial_ranks", "pcr_design_trial_world",
     "pcr_comm_unique_id", "pcr_comm_init_rank", "pcr_comm_world", "pcr_comm_rank", "pcr_exchange_bits", "pcr_comm_destroy", "pcr_comm_library",
@@ -186,6 +186,7 @@ def load_library():
     L.pcr_profile_read_kernel.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
     L.pcr_synchronize.argtypes = [C.c_void_p]
     L.pcr_staging_mode.argtypes = [C.c_void_p]
+    L.pcr_launcher_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.pcr_comm_unique_id.argtypes = [C.c_void_p]
     L.pcr_comm_init_rank.restype = C.c_void_p
     L.pcr_comm_init_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
@@ -969,6 +970,14 @@ class Screener:
     def staging_mode(self):
         """'lean' (the CPU stores the per-pass tables straight into device memory, no staging launch) or 'k_stage'."""
         return "lean" if self.L.pcr_staging_mode(self.h) else "k_stage"
+
+    def launcher_stats(self):
+        """(passes_pipelined, max_queue_depth): the screen_device passes this handle planned on the calling thread and handed
+        to its stream's launcher thread, and the most of them that were queued there at once.  (0, 0) with
+        PCRAMP_LAUNCH_THREAD=0 in the environment when the handle was created: every pass then runs inline."""
+        n, d = C.c_uint64(0), C.c_uint32(0)
+        self._check(self.L.pcr_launcher_stats(self.h, C.byref(n), C.byref(d)))
+        return int(n.value), int(d.value)
 
     def synchronize(self):
         self._check(self.L.pcr_synchronize(self.h))

@@ -49,9 +49,14 @@
 #include <condition_variable>
 #include <functional>
 #include <memory>
+#include <atomic>
+#include <cassert>
+#include <sched.h>
+#include <pthread.h>
 
 #include "../../include/pcramp_hip.h"
 #include "pcr_host.hpp"
+#include "pcr_launch_queue.hpp"
 
 using pcrhost::Planes;
 
@@ -705,6 +710,8 @@ struct HostPool {
 	}
 };
 
+namespace { struct PassJob; struct Launcher; }   // pcr_select.inc
+
 struct pcr_ctx {
 	int device = 0;
 	std::unique_ptr<HostPool> pool_;
@@ -725,9 +732,7 @@ struct pcr_ctx {
 	DevBuf<uint32_t> best, counters, mask, status;
 	int scan_version = 3;
 	bool force_seed1 = false;   // PCRAMP_SEED=1: the first form of the seed scan (A/B)
-	// second form of the seed scan: the pass's seed list, mask tables (reused between passes) and the per-oligo seed cache
-	std::vector<uint32_t> s2_seeds; std::vector<uint4> s2_masks; std::vector<uint8_t> s2_floors;
-	std::vector<uint32_t> s2_group_end, s2_group_offmask, s2_group_or, s2_group_nor;   // per group: end in the seed list, forward-seed slot offsets, first orientation, orientations spanned   // the seed list in groups of whole orientations, each within one launch's LDS budget
+	// second form of the seed scan: the per-oligo seed cache (the pass's lists live in its PassJob: PlanLists, pcr_select.inc)
 	struct S2Key { uint32_t a, c, g, t, floor_; bool operator==(const S2Key &o) const { return a == o.a && c == o.c && g == o.g && t == o.t && floor_ == o.floor_; } };
 	struct S2KeyHash { size_t operator()(const S2Key &k) const { uint64_t h = 0x9E3779B97F4A7C15ull; for(uint32_t v : {k.a, k.c, k.g, k.t, k.floor_}){ h ^= v; h *= 0x100000001B3ull; h ^= h >> 29; } return (size_t)h; } };
 	struct S2Entry { std::vector<uint32_t> seeds; /* code << 14 | off << 9 */ uint32_t off_mask; bool seedable; uint4 mask; /* the orientation's interleaved mask entry (k_seed2 / k_seed3) */
@@ -735,11 +740,10 @@ struct pcr_ctx {
 	std::unordered_map<S2Key, S2Entry, S2KeyHash> s2_cache;
 	std::vector<pcrhost::Seed> s2_tmp;
 	struct S3Launch { Seed3Slices W; uint32_t n_chunks, per_wg, slice_cap, n_irr_wg; };
-	std::vector<S3Launch> s3_launch;               // third form: per launch group, the workgroups' slices of the chunk list
-	std::vector<uint32_t> s3_prefix; bool no_seed3 = false, s3_attr_set = false;   // third form: the pass's chunk list; PCRAMP_SEED3=0: second form (A/B)
+	bool no_seed3 = false, s3_attr_set = false;   // PCRAMP_SEED3=0: second form (A/B)
 	bool s2_attr_set = false; uint32_t s2_dbg = 0; bool no_irr_index = false;   // PCRAMP_IRR_INDEX=0: the irregular words scanned in chunks by every wave (A/B)
 	// first form, tables built on the device (k_seed_tables): the pass's seed list, its own per-oligo cache (8-gram seeds), the tables
-	std::vector<uint32_t> s1_seeds; std::unordered_map<S2Key, S2Entry, S2KeyHash> s1_cache;
+	std::unordered_map<S2Key, S2Entry, S2KeyHash> s1_cache;
 	DevBuf<uint32_t> s1_image, s1_heads, s1_multi, s1_part;
 	bool host_seed_tables = false;   // PCRAMP_SEED_TABLES=host: build them on the host as for passes with shift candidates (A/B)
 	DevBuf<Hit> hits;
@@ -812,6 +816,12 @@ struct pcr_ctx {
 		pcr_amplify_args args; uint64_t *d_fr, *d_rf;
 	};
 	std::vector<Pending> pending;
+	// The default pcr_screen_device pass is planned on the caller's thread and staged and launched by the stream's launcher thread
+	// (pcr_select.inc: PassJob lists who owns what meanwhile).  launcher: attached by the first pipelined pass, shared by the handles
+	// of the stream; lq_client: this handle's jobs in its queue and the error of one that failed.
+	bool launch_thread = true;                    // PCRAMP_LAUNCH_THREAD=0: every pass runs inline on the caller's thread
+	Launcher *launcher = nullptr; pcrq::Client lq_client; uint64_t n_pipelined = 0;
+	std::mutex job_m; std::vector<PassJob *> job_free, job_all;   // recycled pass jobs (job_free under job_m: the launcher thread hands them back)
 	DevBuf<uint8_t> arena;
 	const uint4 *d_cand_fwd = nullptr, *d_cand_rc = nullptr; const uint32_t *d_cand_floor = nullptr;
 	const OligoDev *d_oligos = nullptr;
@@ -830,6 +840,9 @@ struct pcr_ctx {
 namespace {
 
 int drain(pcr_ctx *ctx);
+int flush_launcher(pcr_ctx *ctx);
+void detach_launcher(pcr_ctx *ctx);
+void free_jobs(pcr_ctx *ctx);
 
 // HIP events around the launches of a priced kernel (PCR_PROF_*), on the launch stream, while profiling is on.  The pair is
 // handed to the context when the scope ends (also on an error return), so no event is ever left behind.
@@ -854,7 +867,10 @@ struct ProfScope {
 constexpr int PCR_SET_SCRATCH = 3;
 inline bool set_ok(pcr_set which) { return (unsigned)which <= (unsigned)PCR_SET_MULTIPLEX; }
 #define CHECK_SET(which) do{ if(!set_ok(which)){ g_err = "unknown sequence set (PCR_SET_TARGET, PCR_SET_BACKGROUND or PCR_SET_MULTIPLEX)"; return PCR_ERR_ARG; } }while(0)
-#define DRAIN(ctx) do{ if(!(ctx)->pending.empty()){ const int drc_ = drain(ctx); if(drc_ != PCR_OK) return drc_; } }while(0)
+// First thing in every entry point that touches the handle's device state: wait for the launcher thread to have launched the
+// handle's queued passes (flush_launcher, which also brings back a failed pass's error), then look at their counters (drain).
+#define FLUSH(ctx) do{ if((ctx)->launcher){ const int frc_ = flush_launcher(ctx); if(frc_ != PCR_OK) return frc_; } }while(0)
+#define DRAIN(ctx) do{ FLUSH(ctx); if(!(ctx)->pending.empty()){ const int drc_ = drain(ctx); if(drc_ != PCR_OK) return drc_; } }while(0)
 
 struct HostTimer {
 	pcr_ctx *ctx; int slot; std::chrono::steady_clock::time_point t0;
@@ -1500,6 +1516,7 @@ pcr_ctx *pcr_create(int device, void *hip_stream, const pcr_params *params)
 	if(const char *v = getenv("PCRAMP_S2DBG")) ctx->s2_dbg = (uint32_t)atoi(v);
 	if(const char *v = getenv("PCRAMP_IRR_INDEX")) ctx->no_irr_index = v[0] == '0';
 	if(const char *v = getenv("PCRAMP_SEED3")) ctx->no_seed3 = v[0] == '0';
+	if(const char *v = getenv("PCRAMP_LAUNCH_THREAD")) ctx->launch_thread = v[0] != '0';   // A/B, and for callers that want no helper thread
 	if(const char *v = getenv("PCRAMP_SCAN")){ if(v[0] == '1') ctx->scan_version = 1; else if(v[0] == '2') ctx->scan_version = 2; }   // A/B: 1 = popcount scan, 2 = bit-sliced only
 	{
 		// direct staging: fine-grained device memory the CPU can store into (large BAR) and whose stores a later launch sees.
@@ -1556,10 +1573,16 @@ void pcr_destroy(pcr_ctx *ctx)
 {
 	if(!ctx) return;
 	(void)hipSetDevice(ctx->device);
+	(void)flush_launcher(ctx);                    // queued passes are launched (or dropped after a failed one) before anything is freed
+	detach_launcher(ctx);                         // the stream's last handle stops and joins the launcher thread
 	(void)hipStreamSynchronize(ctx->stream);
 	ctx->pending.clear();
+	free_jobs(ctx);
 	if(ctx->timing && ctx->n_timed){
 		const double n = (double)ctx->n_timed;
+		fprintf(stderr, "[pcramp] host us/pass by stage: A (plan, caller's thread) %.1f  B (stage + launch, %s) %.1f  (%llu of %llu passes pipelined, queue depth <= %u)\n",
+			ctx->t_host[0]/n, ctx->n_pipelined ? "launcher thread" : "caller's thread", (ctx->t_host[1] + ctx->t_host[2])/n,
+			(unsigned long long)ctx->n_pipelined, (unsigned long long)ctx->n_timed, ctx->lq_client.max_depth);
 		fprintf(stderr, "[pcramp] host us/pass: plan %.1f  stage %.1f  launch %.1f  wait %.1f | amplify prep %.1f  launch %.1f  (%llu passes)\n",
 			ctx->t_host[0]/n, ctx->t_host[1]/n, ctx->t_host[2]/n, ctx->t_host[3]/n, ctx->t_host[4]/n, ctx->t_host[5]/n, (unsigned long long)ctx->n_timed);
 	}
@@ -1590,6 +1613,14 @@ uint32_t pcr_num_sequences(pcr_ctx *ctx, pcr_set which) { return (ctx && set_ok(
 uint64_t pcr_bitset_words(pcr_ctx *ctx, pcr_set which) { return (ctx && set_ok(which)) ? (ctx->sets[which].n + 63)/64 : 0; }
 
 int pcr_staging_mode(pcr_ctx *ctx) { return (ctx && ctx->direct_ok) ? 1 : 0; }
+
+int pcr_launcher_stats(pcr_ctx *ctx, uint64_t *passes_pipelined, uint32_t *max_queue_depth)
+{
+	if(!ctx){ g_err = "null ctx"; return PCR_ERR_ARG; }
+	if(passes_pipelined) *passes_pipelined = ctx->n_pipelined;
+	if(max_queue_depth) *max_queue_depth = ctx->lq_client.max_depth;
+	return PCR_OK;
+}
 
 int pcr_synchronize(pcr_ctx *ctx)
 {
@@ -1855,18 +1886,7 @@ int pcr_screen_device(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32
 	if(!set_ok(which)){ g_err = "pcr_screen_device: unknown sequence set"; return PCR_ERR_ARG; }
 	if(!ctx || !args || (n_pairs && (!pairs || !d_bits_fr || !d_bits_rf))){ g_err = "pcr_screen_device: bad argument"; return PCR_ERR_ARG; }
 	if(ctx->pending.size() + 2 >= pcr_ctx::MAIL_RING) DRAIN(ctx);     // the mailbox ring bounds how far the host may run ahead
-	const uint32_t seq0 = ctx->mail_seq;
-	FusedAmp fa; fa.pairs = pairs; fa.n_pairs = n_pairs; fa.a = args; fa.d_fr = d_bits_fr; fa.d_rf = d_bits_rf;
-	int rc = select_impl(ctx, which, pairs, n_pairs, optimize_5, optimize_3, select_threshold, min_oligo_length, nullptr, true, &fa);
-	if(rc != PCR_OK) return rc;
-	if(!fa.posted && (rc = amplify_launch(ctx, ctx->sets[which], pairs, n_pairs, args, d_bits_fr, d_bits_rf, &fa)) != PCR_OK) return rc;
-	if(ctx->mail_seq != seq0){                                        // a pass was enqueued (not the empty-input shortcut)
-		pcr_ctx::Pending p;
-		p.seq = ctx->mail_seq; p.which = (int)which; p.pairs.assign(pairs, pairs + n_pairs); p.opt5 = optimize_5; p.opt3 = optimize_3;
-		p.thr = select_threshold; p.min_len = min_oligo_length; p.args = *args; p.d_fr = d_bits_fr; p.d_rf = d_bits_rf;
-		ctx->pending.push_back(p);
-	}
-	return PCR_OK;
+	return screen_pass(ctx, which, pairs, n_pairs, optimize_5, optimize_3, select_threshold, min_oligo_length, args, d_bits_fr, d_bits_rf);
 }
 
 int64_t pcr_get_entries(pcr_ctx *ctx, pcr_set which, pcr_entry *out, uint64_t cap)
@@ -2022,6 +2042,7 @@ float pcr_weighted_coverage(const uint64_t *bits, const float *weights, uint64_t
 int pcr_profile_enable(pcr_ctx *ctx, int on)
 {
 	if(!ctx){ g_err = "null ctx"; return PCR_ERR_ARG; }
+	FLUSH(ctx);                                   // (the launcher thread records the scan events)
 	ctx->prof = (on != 0);
 	ctx->prof_stride = (on > 1) ? (uint32_t)on : 1u; ctx->prof_pass = 0;
 	return PCR_OK;
@@ -2030,6 +2051,7 @@ int pcr_profile_enable(pcr_ctx *ctx, int on)
 int pcr_profile_read(pcr_ctx *ctx, double *scan_ms, uint64_t *scan_launches, int reset)
 {
 	if(!ctx){ g_err = "null ctx"; return PCR_ERR_ARG; }
+	FLUSH(ctx);
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
 	for(auto &pr : ctx->prof_events){
 		float ms = 0.0f;
@@ -2048,6 +2070,7 @@ int pcr_profile_read_kernel(pcr_ctx *ctx, int kernel, double *ms, uint64_t *laun
 {
 	if(!ctx || kernel < 0 || kernel >= PCR_PROF_KERNELS){ g_err = "pcr_profile_read_kernel: bad argument"; return PCR_ERR_ARG; }
 	if(kernel == PCR_PROF_SCAN) return pcr_profile_read(ctx, ms, launches, reset);
+	FLUSH(ctx);
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
 	for(auto &pr : ctx->prof_events_k[kernel]){
 		float t = 0.0f;

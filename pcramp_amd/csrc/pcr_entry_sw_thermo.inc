@@ -105,6 +105,7 @@ int pcr_sw_align_words(pcr_ctx *ctx, const pcr_word128 *queries, const pcr_word1
 {
 	if(!ctx || (n && (!queries || !templates || !out))){ g_err = "pcr_sw_align_words: bad argument"; return PCR_ERR_ARG; }
 	if(n == 0) return PCR_OK;
+	FLUSH(ctx);
 	HIP_TRY(hipSetDevice(ctx->device));
 	static_assert(sizeof(SwOut) == sizeof(pcr_sw_result), "result layout");
 	// The words go to the device as they are (the kernel reads the code strings out of them) through two pinned,
@@ -703,6 +704,7 @@ int pcr_thermo(pcr_ctx *ctx, const pcr_word128 *oligos, uint32_t n, int check_ho
 	pcr_thermo_result *out)
 {
 	if(!ctx || !args || (n && (!oligos || !out))){ g_err = "pcr_thermo: bad argument"; return PCR_ERR_ARG; }
+	FLUSH(ctx);
 	HIP_TRY(hipSetDevice(ctx->device));
 	std::vector<thermo::Job> &jobs = ctx->th_host_jobs;                          // (the handle's: a fresh 1.4 MB vector per call of 20 000 oligos is page faults)
 	jobs.clear();
@@ -744,6 +746,7 @@ int pcr_thermo(pcr_ctx *ctx, const pcr_word128 *oligos, uint32_t n, int check_ho
 int pcr_dimer(pcr_ctx *ctx, const pcr_pair *pairs, uint32_t n, const pcr_thermo_args *args, float *max_tm)
 {
 	if(!ctx || !args || (n && (!pairs || !max_tm))){ g_err = "pcr_dimer: bad argument"; return PCR_ERR_ARG; }
+	FLUSH(ctx);
 	HIP_TRY(hipSetDevice(ctx->device));
 	std::vector<thermo::Job> jobs;
 	jobs.reserve(n);
@@ -771,6 +774,7 @@ int pcr_dimer(pcr_ctx *ctx, const pcr_pair *pairs, uint32_t n, const pcr_thermo_
 int pcr_multiplex_compatible(pcr_ctx *ctx, const pcr_pair *a, const pcr_pair *b, uint32_t n, const pcr_thermo_args *args, uint8_t *ok)
 {
 	if(!ctx || !args || (n && (!a || !b || !ok))){ g_err = "pcr_multiplex_compatible: bad argument"; return PCR_ERR_ARG; }
+	FLUSH(ctx);
 	HIP_TRY(hipSetDevice(ctx->device));
 	std::vector<thermo::Job> jobs;
 	std::vector<uint32_t> first(n + 1, 0);

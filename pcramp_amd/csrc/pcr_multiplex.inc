@@ -130,6 +130,7 @@ int pcr_multiplex_load(pcr_ctx *ctx, const uint8_t *packed4, const uint64_t *byt
 	if(!ctx || (n && (!packed4 || !byte_offsets || !lengths)) || min_oligo_length == 0 || min_oligo_length > 32){
 		g_err = "pcr_multiplex_load: bad argument"; return PCR_ERR_ARG;
 	}
+	FLUSH(ctx);
 	HIP_TRY(hipSetDevice(ctx->device));
 	pcrhost::PackFilter filt;
 	filt.max_degen = ctx->params.pack_max_degen;
@@ -177,6 +178,7 @@ int pcr_multiplex_coverage(pcr_ctx *ctx, const pcr_pair *base, int side, const p
 	float background_threshold, int use_taq_mama, float *coverage)
 {
 	if(!ctx || !base || (side != 0 && side != 1) || (n_variants && (!variants || !coverage))){ g_err = "pcr_multiplex_coverage: bad argument"; return PCR_ERR_ARG; }
+	FLUSH(ctx);
 	HIP_TRY(hipSetDevice(ctx->device));
 	for(uint32_t v = 0;v < n_variants;++v) coverage[v] = 0.0f;
 	if(ctx->mx_n_keys == 0 || n_variants == 0) return PCR_OK;                    // pcr_assay.cpp:75-77, :306-308

@@ -263,6 +263,7 @@ int pcr_random_assays(pcr_ctx *ctx, pcr_set which, uint32_t *seed, uint32_t n_tr
 		g_err = "pcr_random_assays: bad argument"; return PCR_ERR_ARG;
 	}
 	if(!sampler_args_ok(o)) return PCR_ERR_ARG;
+	FLUSH(ctx);
 	HIP_TRY(hipSetDevice(ctx->device));
 	const SeqSet &S = ctx->sets[which];
 	const SampView v = {S.packed.data(), S.len.data(), S.active.data(), S.n};

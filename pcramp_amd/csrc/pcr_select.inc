@@ -1,5 +1,21 @@
 namespace {
 
+// The lists a pass's planners make and its launches read (plan_seed2, plan_seed3_slices, plan_seed1).  They belong to the pass
+// (PassJob), not to the handle: the caller's thread may plan the next pass while the launcher thread still reads this one's.
+struct PlanLists {
+	// second form of the seed scan: the seed list in groups of whole orientations, each within one launch's LDS budget; mask entries, floors
+	std::vector<uint32_t> s2_seeds; std::vector<uint4> s2_masks; std::vector<uint8_t> s2_floors;
+	std::vector<uint32_t> s2_group_end, s2_group_offmask, s2_group_or, s2_group_nor;   // per group: end in the seed list, forward-seed slot offsets, first orientation, orientations spanned
+	std::vector<pcr_ctx::S3Launch> s3_launch;      // third form: per launch group, the workgroups' slices of the chunk list
+	std::vector<uint32_t> s3_prefix;               // third form: the pass's chunk list
+	std::vector<uint32_t> s1_seeds;                // first form, tables built on the device: the pass's seed list
+	void clear()
+	{
+		s2_seeds.clear(); s2_masks.clear(); s2_floors.clear(); s2_group_end.clear(); s2_group_offmask.clear(); s2_group_or.clear(); s2_group_nor.clear();
+		s3_launch.clear(); s3_prefix.clear(); s1_seeds.clear();
+	}
+};
+
 inline uint32_t spread16(uint32_t v)               // bit i of the low half -> bit 2i
 {
 	v &= 0xFFFFu;
@@ -14,20 +30,20 @@ inline uint32_t spread16(uint32_t v)               // bit i of the low half -> b
 // batch of 1 000 trial assays (pcramp.h:32) is 4 000 orientations = 16+ groups (r02 sent it to the first form with host-built
 // tables: 21 ms per select_words on a C5 shard).  false: an orientation whose seeds alone exceed one launch.
 constexpr uint32_t S2_MAX_GROUPS = 4096;
-// S3 (optional): the set whose position index the third form will read -- the chunk list of every launch group (ctx->s3_prefix: the
+// S3 (optional): the set whose position index the third form will read -- the chunk list of every launch group (L.s3_prefix: the
 // running number of 64-entry chunks of the group's seeds' runs, its total behind it) is made alongside, from chunk counts cached
 // beside each oligo's seeds for the set last used.
-bool plan_seed2(pcr_ctx *ctx, const std::vector<pcrhost::Candidate> &cand, std::vector<uint32_t> &or_seed, std::vector<uint32_t> &or_plain, uint32_t &irr_off_mask,
+bool plan_seed2(pcr_ctx *ctx, PlanLists &L, const std::vector<pcrhost::Candidate> &cand, std::vector<uint32_t> &or_seed, std::vector<uint32_t> &or_plain, uint32_t &irr_off_mask,
 	const SeqSet *S3 = nullptr)
 {
-	std::vector<uint32_t> &pf = ctx->s3_prefix;
+	std::vector<uint32_t> &pf = L.s3_prefix;
 	pf.clear();
 	uint32_t pf_run = 0;
 	const uint32_t n_or = 2*(uint32_t)cand.size();
-	std::vector<uint32_t> &out = ctx->s2_seeds;
-	out.clear(); ctx->s2_group_end.clear(); ctx->s2_group_offmask.clear(); ctx->s2_group_or.clear(); ctx->s2_group_nor.clear();
+	std::vector<uint32_t> &out = L.s2_seeds;
+	out.clear(); L.s2_group_end.clear(); L.s2_group_offmask.clear(); L.s2_group_or.clear(); L.s2_group_nor.clear();
 	irr_off_mask = 0;
-	ctx->s2_masks.resize(n_or);
+	L.s2_masks.resize(n_or);
 	if(ctx->s2_cache.size() > 16384) ctx->s2_cache.clear();
 	size_t group_begin = 0; uint32_t group_mask = 0, group_or0 = 0, group_last = 0;
 	// the tables of a launch must fit one CU's LDS; the third form keeps only the masks and a slice of the lists there: more orientations
@@ -55,13 +71,13 @@ bool plan_seed2(pcr_ctx *ctx, const std::vector<pcrhost::Candidate> &cand, std::
 			it = ctx->s2_cache.emplace(key, std::move(e)).first;
 		}
 		pcr_ctx::S2Entry &e = it->second;
-		ctx->s2_masks[o] = e.mask;
+		L.s2_masks[o] = e.mask;
 		if(!e.seedable){ or_plain.push_back(o); continue; }
 		or_seed.push_back(o);
 		// the group spans orientations [group_or0, o]: unseedable ones in between only take an (unused) id
 		if(!fits(out.size() - group_begin + e.seeds.size(), o - group_or0 + 1)){   // close the group, open the next at this orientation
-			if(!fits(e.seeds.size(), 1) || ctx->s2_group_end.size() + 1 >= S2_MAX_GROUPS) return false;
-			ctx->s2_group_end.push_back((uint32_t)out.size()); ctx->s2_group_offmask.push_back(group_mask); ctx->s2_group_or.push_back(group_or0); ctx->s2_group_nor.push_back(group_last - group_or0 + 1);
+			if(!fits(e.seeds.size(), 1) || L.s2_group_end.size() + 1 >= S2_MAX_GROUPS) return false;
+			L.s2_group_end.push_back((uint32_t)out.size()); L.s2_group_offmask.push_back(group_mask); L.s2_group_or.push_back(group_or0); L.s2_group_nor.push_back(group_last - group_or0 + 1);
 			group_begin = out.size(); group_mask = 0; group_or0 = o;
 			if(S3){ pf.push_back(pf_run); pf_run = 0; }                                // the group's total; the next one starts at 0
 		}
@@ -83,8 +99,8 @@ bool plan_seed2(pcr_ctx *ctx, const std::vector<pcrhost::Candidate> &cand, std::
 		}
 		if(!(o & 1u)){ irr_off_mask |= e.off_mask; group_mask |= e.off_mask; }   // slot offsets at which forward seeds sit (irregular-word scan)
 	}
-	ctx->s2_group_end.push_back((uint32_t)out.size()); ctx->s2_group_offmask.push_back(group_mask); ctx->s2_group_or.push_back(group_or0);
-	ctx->s2_group_nor.push_back(or_seed.empty() ? 0u : group_last - group_or0 + 1);
+	L.s2_group_end.push_back((uint32_t)out.size()); L.s2_group_offmask.push_back(group_mask); L.s2_group_or.push_back(group_or0);
+	L.s2_group_nor.push_back(or_seed.empty() ? 0u : group_last - group_or0 + 1);
 	if(S3) pf.push_back(pf_run);
 	return true;
 }
@@ -96,17 +112,17 @@ constexpr size_t S3_LDS_BUDGET = 120*1024;
 // 1024-thread workgroups, two per CU (512 threads x 4 per CU: within the spread of the repeated default, profiles/dbg/r03_ab_s3_grid.txt)
 constexpr uint32_t S3_WG_THREADS = 1024;
 uint32_t seed3_grid(const pcr_ctx *ctx) { return std::min<uint32_t>(2*ctx->n_cu, S3_MAX_WG); }
-bool plan_seed3_slices(pcr_ctx *ctx, bool with_irr)
+bool plan_seed3_slices(pcr_ctx *ctx, PlanLists &PL, bool with_irr)
 {
 	const uint32_t G_all = seed3_grid(ctx), seeds_per_turn = 16u*(S3_WG_THREADS/64);
-	ctx->s3_launch.resize(ctx->s2_group_end.size());
+	PL.s3_launch.resize(PL.s2_group_end.size());
 	size_t g_begin = 0, g_prefix = 0;
-	for(size_t g = 0;g < ctx->s2_group_end.size();++g){
-		const uint32_t ns = ctx->s2_group_end[g] - (uint32_t)g_begin;
-		g_begin = ctx->s2_group_end[g];
-		const uint32_t *P = ctx->s3_prefix.data() + g_prefix;                  // the group's chunk list, [ns + 1]
+	for(size_t g = 0;g < PL.s2_group_end.size();++g){
+		const uint32_t ns = PL.s2_group_end[g] - (uint32_t)g_begin;
+		g_begin = PL.s2_group_end[g];
+		const uint32_t *P = PL.s3_prefix.data() + g_prefix;                  // the group's chunk list, [ns + 1]
 		g_prefix += (size_t)ns + 1;
-		pcr_ctx::S3Launch &L = ctx->s3_launch[g];
+		pcr_ctx::S3Launch &L = PL.s3_launch[g];
 		// the launch's first workgroups look the irregular words up (16 seeds per wave turn) and leave the chunks to the others: the two
 		// chains of dependent loads then run side by side; at most a quarter of the launch
 		L.n_irr_wg = with_irr ? std::min<uint32_t>((ns + seeds_per_turn - 1u)/seeds_per_turn, G_all/4u) : 0u;
@@ -121,7 +137,7 @@ bool plan_seed3_slices(pcr_ctx *ctx, bool with_irr)
 		}
 		for(uint32_t w = G + 1;w <= S3_MAX_WG;++w) L.W.start[w] = at;
 		for(uint32_t w = 0;w < G;++w) L.slice_cap = std::max(L.slice_cap, std::min(L.W.start[w + 1] + 2u, ns + 1u) - L.W.start[w]);
-		if(17*(size_t)ctx->s2_group_nor[g] + 8*(size_t)L.slice_cap + 64 > S3_LDS_BUDGET) return false;
+		if(17*(size_t)PL.s2_group_nor[g] + 8*(size_t)L.slice_cap + 64 > S3_LDS_BUDGET) return false;
 	}
 	return true;
 }
@@ -129,10 +145,10 @@ bool plan_seed3_slices(pcr_ctx *ctx, bool with_irr)
 // The seeds of a pass for the first form with device-built tables: per orientation from the cache (8-gram seeds), listed as
 // code | slot offset << 16 | orientation << 21.  When the lists exceed S1_MAX_SEEDS (low thresholds: hundreds of codes per
 // orientation) the orientations with the longest lists go to the bit-sliced scan.
-void plan_seed1(pcr_ctx *ctx, const std::vector<pcrhost::Candidate> &cand, std::vector<uint32_t> &or_seed, std::vector<uint32_t> &or_plain, uint32_t &irr_off_mask)
+void plan_seed1(pcr_ctx *ctx, PlanLists &L, const std::vector<pcrhost::Candidate> &cand, std::vector<uint32_t> &or_seed, std::vector<uint32_t> &or_plain, uint32_t &irr_off_mask)
 {
 	const uint32_t n_or = 2*(uint32_t)cand.size();
-	std::vector<uint32_t> &out = ctx->s1_seeds;
+	std::vector<uint32_t> &out = L.s1_seeds;
 	out.clear();
 	irr_off_mask = 0;
 	if(ctx->s1_cache.size() > 16384) ctx->s1_cache.clear();
@@ -351,6 +367,12 @@ struct ScanPlan {
 	bool need_plain = false, need_seedset = false;    // bit-sliced tables: unseedable orientations (all tiles) / seedable ones (IUPAC tiles)
 	size_t n_seeds = 0;                               // of the form that planned the pass (debug line)
 	uint32_t n_live = 0, min_len = 0;                 // irregular words whose size counter reaches min_oligo_length; that length
+	void reset()                                      // (the vectors keep their storage: a recycled PassJob allocates nothing)
+	{
+		form = ScanForm::BitSliced; or_seed.clear(); or_plain.clear(); irr_off_mask = 0;
+		H.seeds.clear(); H.inheritors.clear(); H.n_inherited = 0; H.image.clear(); H.heads.clear(); H.multi.clear();
+		s3_with_irr = need_plain = need_seedset = false; n_seeds = 0; n_live = min_len = 0;
+	}
 };
 
 inline uint32_t live_irregular(const SeqSet &S, uint32_t min_oligo_length)
@@ -373,8 +395,8 @@ int irr_index_usable(pcr_ctx *ctx, SeqSet &S, bool &usable)
 
 // Scan plan.  version 3 (default): orientations that can be seeded go through the pigeonhole seed scan; the others, and every
 // tile holding IUPAC target codes, through the bit-sliced counter.  version 2: bit-sliced counter for everything.  version 1:
-// one popcount per (window, orientation).  The planners fill ctx->s2_* / s3_* / s1_seeds, which the launches read.
-int choose_scan_form(pcr_ctx *ctx, SeqSet &S, const std::vector<pcrhost::Candidate> &cand, int optimize_5, int optimize_3, uint32_t min_oligo_length, ScanPlan &P)
+// one popcount per (window, orientation).  The planners fill the pass's lists (PlanLists L), which the launches read.
+int choose_scan_form(pcr_ctx *ctx, SeqSet &S, const std::vector<pcrhost::Candidate> &cand, int optimize_5, int optimize_3, uint32_t min_oligo_length, ScanPlan &P, PlanLists &L)
 {
 	const uint32_t n_or = 2*(uint32_t)cand.size();
 	std::vector<uint32_t> &or_seed = P.or_seed, &or_plain = P.or_plain;
@@ -392,7 +414,7 @@ int choose_scan_form(pcr_ctx *ctx, SeqSet &S, const std::vector<pcrhost::Candida
 		bool worth = true;
 		if(!S.pix_valid){
 			std::vector<uint32_t> os, op; uint32_t om = 0;
-			worth = plan_seed2(ctx, cand, os, op, om, nullptr) && op.empty() && !os.empty();
+			worth = plan_seed2(ctx, L, cand, os, op, om, nullptr) && op.empty() && !os.empty();
 		}
 		if(worth){
 			if((rc = ensure_pos_index(ctx, S)) != PCR_OK) return rc;
@@ -403,11 +425,11 @@ int choose_scan_form(pcr_ctx *ctx, SeqSet &S, const std::vector<pcrhost::Candida
 	}
 	bool use_seed2 = false;
 	if(seed2_ok){
-		use_seed2 = plan_seed2(ctx, cand, or_seed, or_plain, P.irr_off_mask, want_seed3 ? &S : nullptr);
-		if(want_seed3 && !(use_seed2 && or_plain.empty() && !or_seed.empty() && plan_seed3_slices(ctx, P.s3_with_irr))){
+		use_seed2 = plan_seed2(ctx, L, cand, or_seed, or_plain, P.irr_off_mask, want_seed3 ? &S : nullptr);
+		if(want_seed3 && !(use_seed2 && or_plain.empty() && !or_seed.empty() && plan_seed3_slices(ctx, L, P.s3_with_irr))){
 			// the third form will not take the pass (an unseeded candidate, or its lists do not fit): plan within the second form's limits
 			or_seed.clear(); or_plain.clear();
-			use_seed2 = plan_seed2(ctx, cand, or_seed, or_plain, P.irr_off_mask, nullptr);
+			use_seed2 = plan_seed2(ctx, L, cand, or_seed, or_plain, P.irr_off_mask, nullptr);
 		}
 		// an orientation without a 9-gram structure (low thresholds: k = 4 mismatching slots and more) may still have an 8-gram
 		// one: let the first form plan the pass where it can (it hands fewer orientations to the bit-sliced scan); a batch beyond
@@ -418,11 +440,11 @@ int choose_scan_form(pcr_ctx *ctx, SeqSet &S, const std::vector<pcrhost::Candida
 	// ... and the third form -- the targets' positions indexed by their 9-grams, the seeds looked up (pcr_scan_seed3.inc) -- where every
 	// candidate is seeded (and the irregular words can come in through their index too: want_seed3, decided before the planning)
 	const bool use_seed3 = use_seed2 && want_seed3 && or_plain.empty() && !or_seed.empty()
-		&& ctx->s3_prefix.size() == ctx->s2_seeds.size() + ctx->s2_group_end.size();
-	if(use_seed2){ P.form = use_seed3 ? ScanForm::Seed3 : ScanForm::Seed2; P.n_seeds = ctx->s2_seeds.size(); }
+		&& L.s3_prefix.size() == L.s2_seeds.size() + L.s2_group_end.size();
+	if(use_seed2){ P.form = use_seed3 ? ScanForm::Seed3 : ScanForm::Seed2; P.n_seeds = L.s2_seeds.size(); }
 	else if(no_shifts && !ctx->host_seed_tables && n_or <= S1_MAX_OR){      // first form, tables built by k_seed_tables
-		plan_seed1(ctx, cand, or_seed, or_plain, P.irr_off_mask);
-		P.form = ScanForm::Seed1Dev; P.n_seeds = ctx->s1_seeds.size();
+		plan_seed1(ctx, L, cand, or_seed, or_plain, P.irr_off_mask);
+		P.form = ScanForm::Seed1Dev; P.n_seeds = L.s1_seeds.size();
 	}
 	else if(ctx->scan_version == 3 && n_or <= 65535){
 		const int prc = plan_seed_host(ctx, cand, P.H, or_seed, or_plain, P.irr_off_mask);
@@ -440,6 +462,38 @@ int choose_scan_form(pcr_ctx *ctx, SeqSet &S, const std::vector<pcrhost::Candida
 	P.need_seedset = !or_seed.empty() && S.n_degen_tiles > 0;
 	return PCR_OK;
 }
+
+// One pass, self-contained: the call's arguments, everything its planning made, and what the device stage needs to run it.
+// The caller's thread fills it (plan_pass: stage A), the thread that runs run_pass reads it (stage B): the same thread for an
+// inline pass, the stream's launcher thread for a pipelined one.  Recycled through a free list per handle.
+//
+// WHO OWNS WHAT while a handle has jobs in its stream's launch queue
+//   caller thread (stage A): argument checks; build_candidates; the planning half of choose_scan_form with the per-oligo caches
+//     (s2_cache, s1_cache, s2_tmp, seed_count/own/fill); plan_seed3_slices; prepare_tables (candidate planes, floors, build_oligos);
+//     pending[]; mail_seq (a pipelined pass's sequence number is reserved at enqueue: the passes of a handle are strictly FIFO);
+//     the job free list (under job_m).
+//   launcher thread (stage B): the Stager rings with their wait_published spin; the sizing of S.ctrl / hits / S.db / best / S.touched;
+//     the lean decision and the epoch; every launch; S.ctrl_clean, touched_from_seg, touched_built, d_seg_hi and the have_db markers
+//     (have_db, n_entries, n_touched, db_cap, n_slots); d_cand_*; the profiling events; t_host[1], t_host[2].
+//   set state that stage A READS (pix_*, pix_count_h, irx_valid, irr_size_count, irr_n_multi, n_irr, n_degen_tiles, n, bucket_cap)
+//     is written only while the queue holds no job of the handle: every writer sits behind DRAIN / flush_launcher.
+struct PassJob {
+	// the call
+	pcr_ctx *ctx = nullptr; int which = 0, opt5 = 0, opt3 = 0; float thr = 0.0f; uint32_t min_len = 0; bool async = false;
+	pcr_amplify_args args = {}; FusedAmp fa = {}; bool has_fa = false;
+	uint32_t seq = 0;                                 // the pass's reserved mailbox sequence number; 0: the tail takes the next one (inline passes)
+	bool begun = false, ctrl_was_clean = false;       // inline passes: begin_pass() ran before the planning, as it always has
+	// the plan
+	std::vector<pcrhost::Candidate> cand; ScanPlan P; PlanLists L;
+	std::vector<uint4> hf, hr; std::vector<uint32_t> hfl;   // candidate planes and floors as the device reads them
+	std::vector<OligoDev> ol;                         // fused pass: the amplicon screen's oligo table
+	bool fuse = false; size_t bits_bytes = 0;         // fuse: the screen rides in the pass; bytes of each of its two result bitsets
+	void reset()
+	{
+		seq = 0; begun = ctrl_was_clean = false; has_fa = false; fa = FusedAmp(); async = false;
+		cand.clear(); P.reset(); L.clear(); hf.clear(); hr.clear(); hfl.clear(); ol.clear(); fuse = false; bits_bytes = 0;
+	}
+};
 
 // What the launches of a pass read on the device (stage_tables).
 struct Scan2Staged { Scan2Tables T; const uint32_t *d_tab = nullptr, *d_bias = nullptr, *d_map = nullptr; };
@@ -461,44 +515,58 @@ void stage_scan2(Stager &st, const std::vector<uint32_t> &orients, Scan2Staged &
 	B.d_map = st.put(m.data(), m.size());
 }
 
-int stage_tables(pcr_ctx *ctx, SeqSet &S, const std::vector<pcrhost::Candidate> &cand, const ScanPlan &P, FusedAmp *fa, bool async, bool ctrl_was_clean,
-	HostTimer &timer, StagedTables &T)
+// Stage A's last step: the host tables that depend on nothing but the call -- candidate planes and floors in device layout, the
+// second form's floor bytes, and for a fused pass the amplicon screen's oligo table.  (S is only asked for its size.)
+void prepare_tables(const SeqSet &S, PassJob &J, FusedAmp *fa)
 {
+	const std::vector<pcrhost::Candidate> &cand = J.cand;
+	const uint32_t ncand = (uint32_t)cand.size(), n_or = 2*ncand;
+	J.hf.resize(ncand); J.hr.resize(ncand); J.hfl.resize(ncand);
+	for(uint32_t c = 0;c < ncand;++c){
+		J.hf[c] = make_uint4(cand[c].fwd.a, cand[c].fwd.c, cand[c].fwd.g, cand[c].fwd.t);
+		J.hr[c] = make_uint4(cand[c].rc.a, cand[c].rc.c, cand[c].rc.g, cand[c].rc.t);
+		J.hfl[c] = cand[c].floor_;
+	}
+	if(is_seed2(J.P.form)){
+		// (the mask entries come out of the per-oligo cache: plan_seed2)
+		std::vector<uint8_t> &floors2 = J.L.s2_floors;
+		floors2.assign(((size_t)n_or + 15) & ~size_t(15), 0);
+		for(uint32_t o = 0;o < n_or;++o) floors2[o] = (uint8_t)std::min<uint32_t>(cand[o >> 1].floor_, 255u);
+	}
+	// fused pass: the amplicon screen's oligo table travels with the scan tables, its result bitsets are
+	// cleared by the same launch
+	J.fuse = false; J.bits_bytes = 0; J.ol.clear();
+	if(fa && fa->n_pairs){
+		J.bits_bytes = (size_t)fa->n_pairs*((S.n + 63)/64)*sizeof(uint64_t);
+		J.fuse = ((uintptr_t)fa->d_fr % 16 == 0) && ((uintptr_t)fa->d_rf % 16 == 0) && (J.bits_bytes % 16 == 0);
+		if(J.fuse) build_oligos(fa->pairs, fa->n_pairs, fa->a, J.ol);
+	}
+}
+
+// Stage B's first step: the pass's tables to the device (a ring slot, k_stage or the lean form's direct write).
+int stage_tables(pcr_ctx *ctx, SeqSet &S, const PassJob &J, FusedAmp *fa, bool async, bool ctrl_was_clean, StagedTables &T)
+{
+	const std::vector<pcrhost::Candidate> &cand = J.cand;
+	const ScanPlan &P = J.P; const PlanLists &L = J.L;
 	const uint32_t ncand = (uint32_t)cand.size(), n_or = 2*ncand;
 	const bool seed2 = is_seed2(P.form), seed3 = P.form == ScanForm::Seed3;
 	const bool build_tables = P.form == ScanForm::Seed1Dev;
 	const HostSeedPlan &H = P.H;
 	int rc;
-	std::vector<uint4> hf(ncand), hr(ncand); std::vector<uint32_t> hfl(ncand);
-	for(uint32_t c = 0;c < ncand;++c){
-		hf[c] = make_uint4(cand[c].fwd.a, cand[c].fwd.c, cand[c].fwd.g, cand[c].fwd.t);
-		hr[c] = make_uint4(cand[c].rc.a, cand[c].rc.c, cand[c].rc.g, cand[c].rc.t);
-		hfl[c] = cand[c].floor_;
-	}
 	if(P.need_plain) build_scan2_tables(cand, P.or_plain, T.plain.T);
 	if(P.need_seedset) build_scan2_tables(cand, P.or_seed, T.seedset.T);
 	size_t bytes = ncand*(2*sizeof(uint4) + sizeof(uint32_t)) + 1024;
 	bytes += (T.plain.T.tab.size() + T.plain.T.bias.size() + P.or_plain.size() + 256)*sizeof(uint32_t);
 	bytes += (T.seedset.T.tab.size() + T.seedset.T.bias.size() + P.or_seed.size() + 256)*sizeof(uint32_t);
 	bytes += (H.image.size() + H.heads.size() + H.multi.size() + 64)*sizeof(uint32_t);
-	std::vector<uint4> &masks2 = ctx->s2_masks; std::vector<uint8_t> &floors2 = ctx->s2_floors;
 	if(seed2){
-		// (the mask entries come out of the per-oligo cache: plan_seed2)
-		floors2.assign(((size_t)n_or + 15) & ~size_t(15), 0);
-		for(uint32_t o = 0;o < n_or;++o) floors2[o] = (uint8_t)std::min<uint32_t>(cand[o >> 1].floor_, 255u);
-		bytes += masks2.size()*sizeof(uint4) + floors2.size() + ctx->s2_seeds.size()*sizeof(uint32_t) + 512;
-		if(seed3) bytes += ctx->s3_prefix.size()*sizeof(uint32_t) + 64;
+		bytes += L.s2_masks.size()*sizeof(uint4) + L.s2_floors.size() + L.s2_seeds.size()*sizeof(uint32_t) + 512;
+		if(seed3) bytes += L.s3_prefix.size()*sizeof(uint32_t) + 64;
 	}
-	if(build_tables) bytes += ctx->s1_seeds.size()*sizeof(uint32_t) + 256;
-	// fused pass: the amplicon screen's oligo table travels with the scan tables, its result bitsets are
-	// cleared by the same launch
-	std::vector<OligoDev> ol;
-	if(fa && fa->n_pairs){
-		T.bits_bytes = (size_t)fa->n_pairs*((S.n + 63)/64)*sizeof(uint64_t);
-		T.fuse = ((uintptr_t)fa->d_fr % 16 == 0) && ((uintptr_t)fa->d_rf % 16 == 0) && (T.bits_bytes % 16 == 0);
-		if(T.fuse){ build_oligos(fa->pairs, fa->n_pairs, fa->a, ol); bytes += ol.size()*sizeof(OligoDev) + 64; }
-	}
-	timer.next(1);
+	if(build_tables) bytes += L.s1_seeds.size()*sizeof(uint32_t) + 256;
+	T.bits_bytes = J.bits_bytes; T.fuse = J.fuse;
+	if(T.fuse) bytes += J.ol.size()*sizeof(OligoDev) + 64;
+	const uint32_t guard_seq = J.seq ? J.seq : ctx->mail_seq + 1;   // the sequence number the pass's tail will publish
 	// the pass's control block (counters | per-sequence fills | segment ends)
 	const uint64_t gen = S.ctrl.generation;
 	if((rc = S.ctrl.ensure(8 + 2*(size_t)S.n + 4)) != PCR_OK) return rc;
@@ -507,9 +575,9 @@ int stage_tables(pcr_ctx *ctx, SeqSet &S, const std::vector<pcrhost::Candidate> 
 	if(ctx->debug_log) fprintf(stderr, "[pcramp] staging: %s\n", T.lean ? "lean (tables written into device memory, no staging launch)" : "k_stage");
 	Stager st(ctx);
 	if((rc = T.lean ? st.begin_direct(bytes) : st.begin(bytes)) != PCR_OK) return rc;
-	ctx->d_cand_fwd = st.put(hf.data(), ncand);
-	ctx->d_cand_rc = st.put(hr.data(), ncand);
-	ctx->d_cand_floor = st.put(hfl.data(), ncand);
+	ctx->d_cand_fwd = st.put(J.hf.data(), ncand);
+	ctx->d_cand_rc = st.put(J.hr.data(), ncand);
+	ctx->d_cand_floor = st.put(J.hfl.data(), ncand);
 	if(P.need_plain) stage_scan2(st, P.or_plain, T.plain);
 	if(P.need_seedset) stage_scan2(st, P.or_seed, T.seedset);
 	if(!H.image.empty()){
@@ -519,35 +587,35 @@ int stage_tables(pcr_ctx *ctx, SeqSet &S, const std::vector<pcrhost::Candidate> 
 	}
 	const uint32_t *d_s1_seeds = nullptr;
 	if(build_tables){
-		d_s1_seeds = st.put(ctx->s1_seeds.data(), ctx->s1_seeds.size());
+		d_s1_seeds = st.put(L.s1_seeds.data(), L.s1_seeds.size());
 		if((rc = ctx->s1_image.ensure(SEED_IMAGE_WORDS)) != PCR_OK) return rc;
 		if((rc = ctx->s1_heads.ensure(2*(size_t)S1_MAX_SEEDS)) != PCR_OK) return rc;   // two words per distinct code
 		if((rc = ctx->s1_multi.ensure(S1_MAX_SEEDS)) != PCR_OK) return rc;
 		T.ST.image = ctx->s1_image.p; T.ST.heads = ctx->s1_heads.p; T.ST.multi = ctx->s1_multi.p; T.ST.flat = 1;
 	}
 	if(seed2){
-		T.ST2.seeds = st.put(ctx->s2_seeds.data(), ctx->s2_seeds.size());
-		T.ST2.masks = st.put(masks2.data(), masks2.size());
-		T.ST2.floors = st.put(floors2.data(), floors2.size());
-		T.ST2.n_seeds = (uint32_t)ctx->s2_seeds.size(); T.ST2.n_or = n_or;
-		if(seed3) T.d_s3_prefix = st.put(ctx->s3_prefix.data(), ctx->s3_prefix.size());
+		T.ST2.seeds = st.put(L.s2_seeds.data(), L.s2_seeds.size());
+		T.ST2.masks = st.put(L.s2_masks.data(), L.s2_masks.size());
+		T.ST2.floors = st.put(L.s2_floors.data(), L.s2_floors.size());
+		T.ST2.n_seeds = (uint32_t)L.s2_seeds.size(); T.ST2.n_or = n_or;
+		if(seed3) T.d_s3_prefix = st.put(L.s3_prefix.data(), L.s3_prefix.size());
 	}
 	// the staging launch also clears the control block and the result bitsets -- unless the pass is lean: then the tables
 	// are already in device memory, the control block was left clean by the previous pass's tail and the first scan launch
 	// clears the bitsets
 	const size_t ctrl_bytes = (8 + 2*(size_t)S.n)*sizeof(uint32_t);
 	if(T.fuse){
-		fa->d_oligos = st.put(ol.data(), ol.size());
+		fa->d_oligos = st.put(J.ol.data(), J.ol.size());
 		fa->staged = true;
-		if(T.lean) st.seal(ctx->mail_seq + 1);
-		else if((rc = st.ship(S.ctrl.p, ctrl_bytes, fa->d_fr, T.bits_bytes, fa->d_rf, T.bits_bytes, ctx->mail_seq + 1)) != PCR_OK) return rc;
+		if(T.lean) st.seal(guard_seq);
+		else if((rc = st.ship(S.ctrl.p, ctrl_bytes, fa->d_fr, T.bits_bytes, fa->d_rf, T.bits_bytes, guard_seq)) != PCR_OK) return rc;
 	}
-	else if((rc = st.ship(S.ctrl.p, ctrl_bytes, nullptr, 0, nullptr, 0, ctx->mail_seq + 1)) != PCR_OK) return rc;
+	else if((rc = st.ship(S.ctrl.p, ctrl_bytes, nullptr, 0, nullptr, 0, guard_seq)) != PCR_OK) return rc;
 	if(build_tables){
 		if((rc = ctx->s1_part.ensure(2*S1_GROUPS)) != PCR_OK) return rc;
-		hipLaunchKernelGGL(k_seed_tables<false>, dim3(S1_GROUPS), dim3(S1_BUILD_THREADS), 0, ctx->stream, d_s1_seeds, (uint32_t)ctx->s1_seeds.size(),
+		hipLaunchKernelGGL(k_seed_tables<false>, dim3(S1_GROUPS), dim3(S1_BUILD_THREADS), 0, ctx->stream, d_s1_seeds, (uint32_t)L.s1_seeds.size(),
 			ctx->s1_part.p, ctx->s1_image.p, ctx->s1_heads.p, ctx->s1_multi.p);
-		hipLaunchKernelGGL(k_seed_tables<true>, dim3(S1_GROUPS), dim3(S1_BUILD_THREADS), 0, ctx->stream, d_s1_seeds, (uint32_t)ctx->s1_seeds.size(),
+		hipLaunchKernelGGL(k_seed_tables<true>, dim3(S1_GROUPS), dim3(S1_BUILD_THREADS), 0, ctx->stream, d_s1_seeds, (uint32_t)L.s1_seeds.size(),
 			ctx->s1_part.p, ctx->s1_image.p, ctx->s1_heads.p, ctx->s1_multi.p);
 		HIP_TRY(hipGetLastError());
 	}
@@ -616,7 +684,7 @@ int launch_seed3_group(pcr_ctx *ctx, SeqSet &S, const Seed2Tables &Tg, const uin
 
 // Second and third form: one launch per seed group (plan_seed2).  The second form runs persistent workgroups of 16 waves, one per
 // CU (the tables they build take most of its LDS); the irregular words are taken by the same waves once their tiles are done.
-int launch_seed_groups(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const StagedTables &T, const FusedAmp *fa, const HitSink &sink)
+int launch_seed_groups(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const PlanLists &L, const StagedTables &T, const FusedAmp *fa, const HitSink &sink)
 {
 	const bool seed3 = P.form == ScanForm::Seed3;
 	const uint32_t tiles_per_wg = S2_WAVES*2;
@@ -631,21 +699,21 @@ int launch_seed_groups(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const StagedT
 	bool irr_by_index = P.s3_with_irr;                    // third form: decided with the form, the index is there and usable
 	if(!seed3){
 		irr_by_index = P.or_plain.empty() && P.n_live > 0 && !ctx->no_irr_index;
-		for(size_t g = 0, b = 0;g < ctx->s2_group_end.size();++g){ if((size_t)ctx->s2_group_end[g] - b > (size_t)sgrid.x*S2_THREADS) irr_by_index = false; b = ctx->s2_group_end[g]; }   // (a thread looks up at most one seed)
+		for(size_t g = 0, b = 0;g < L.s2_group_end.size();++g){ if((size_t)L.s2_group_end[g] - b > (size_t)sgrid.x*S2_THREADS) irr_by_index = false; b = L.s2_group_end[g]; }   // (a thread looks up at most one seed)
 		if(irr_by_index && (rc = irr_index_usable(ctx, S, irr_by_index)) != PCR_OK) return rc;
 	}
 	uint32_t g_begin = 0, g_prefix = 0;
 	bool first_launch = true;
-	for(size_t g = 0;g < ctx->s2_group_end.size();++g){
+	for(size_t g = 0;g < L.s2_group_end.size();++g){
 		Seed2Tables Tg = T.ST2;
-		const uint32_t or0 = ctx->s2_group_or[g], g_or = ctx->s2_group_nor[g];
-		Tg.seeds = T.ST2.seeds + g_begin; Tg.n_seeds = ctx->s2_group_end[g] - g_begin;
+		const uint32_t or0 = L.s2_group_or[g], g_or = L.s2_group_nor[g];
+		Tg.seeds = T.ST2.seeds + g_begin; Tg.n_seeds = L.s2_group_end[g] - g_begin;
 		Tg.masks = T.ST2.masks + (size_t)or0; Tg.floors = T.ST2.floors + or0; Tg.n_or = g_or; Tg.or_base = or0;
-		g_begin = ctx->s2_group_end[g];
+		g_begin = L.s2_group_end[g];
 		if(Tg.n_seeds == 0){ g_prefix += 1u; continue; }
 		const size_t dyn = (size_t)g_or*sizeof(uint4) + (((size_t)g_or + 15) & ~size_t(15)) + 8*((size_t)Tg.n_seeds + 64) + 16;   // masks | floors | chain | head (each with 64 dummy slots)
 		IrrArgs2 IA; IA.scan = S.irr_scan.p; IA.irr = S.irr.p; IA.n_live = P.n_live;
-		IA.off_mask = ctx->s2_group_offmask[g];
+		IA.off_mask = L.s2_group_offmask[g];
 		IA.exhaustive = first_launch ? 1u : 0u;                             // words holding IUPAC slots meet every candidate once, in the first launch
 		IA.ix_first = IA.ix_last = IA.ix_words = nullptr; IA.min_cws = std::min<uint32_t>(P.min_len, 255u);
 		if(!P.or_plain.empty()){                                            // unseeded candidates in the pass: every irregular word meets every candidate, once
@@ -656,13 +724,13 @@ int launch_seed_groups(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const StagedT
 			IA.ix_first = S.irx_first.p; IA.ix_last = S.irx_last.p; IA.ix_words = S.irx_words.p; IA.n_live = 0;
 		}
 		if(ctx->debug_log) fprintf(stderr, "[pcramp] k_seed2: %u workgroups, %u seeds of orientations %u..%u (group %zu of %zu), %zu + %zu B of LDS\n", sgrid.x, Tg.n_seeds,
-			or0, or0 + g_or - 1, g + 1, ctx->s2_group_end.size(), sizeof(S2Shared), dyn);
+			or0, or0 + g_or - 1, g + 1, L.s2_group_end.size(), sizeof(S2Shared), dyn);
 		S2Clear Z = { nullptr, 0u, nullptr, 0u, nullptr };
 		if(T.lean && first_launch){                                          // the first launch of a lean pass clears the result bitsets
 			Z.z0 = (uint4 *)fa->d_fr; Z.z1 = (uint4 *)fa->d_rf; Z.n0 = Z.n1 = (uint32_t)(T.bits_bytes/16); Z.ctrl = sink.counters;
 		}
 		if(seed3){
-			if((rc = launch_seed3_group(ctx, S, Tg, T.d_s3_prefix + g_prefix, ctx->s3_launch[g], IA, sink, Z)) != PCR_OK) return rc;
+			if((rc = launch_seed3_group(ctx, S, Tg, T.d_s3_prefix + g_prefix, L.s3_launch[g], IA, sink, Z)) != PCR_OK) return rc;
 			g_prefix += Tg.n_seeds + 1u;
 		}
 		else hipLaunchKernelGGL(k_seed2_of_ctx, sgrid, sblock, dyn, ctx->stream, S.tb_d(), S.valid_d(), S.tile_desc.p, S.n_tiles, Tg, S.d_active.p, ctx->d_cand_fwd, ctx->d_cand_floor,
@@ -685,7 +753,7 @@ int launch_irregular(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const HitSink &
 
 // All scan launches of one attempt: bit-sliced counter for the unseeded orientations, the plan's form for the seeded ones, the
 // bit-sliced counter again for those in the IUPAC tiles, then the irregular words where no seed scan took them along.
-int launch_scans(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const StagedTables &T, const FusedAmp *fa, const HitSink &sink)
+int launch_scans(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const PlanLists &L, const StagedTables &T, const FusedAmp *fa, const HitSink &sink)
 {
 	int rc = PCR_OK;
 	const uint32_t ncand = sink.ncand;
@@ -695,7 +763,7 @@ int launch_scans(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const StagedTables 
 		if(P.need_plain && (rc = launch_scan2(ctx, S, T.plain.T, ncand, sink, T.plain.d_tab, T.plain.d_bias, nullptr, S.n_tiles, T.plain.d_map)) != PCR_OK) return rc;
 		if(P.form == ScanForm::Popcount) rc = launch_popcount(ctx, S, sink);
 		else if(is_seed1(P.form)) rc = launch_seed1(ctx, S, P, T, sink);
-		else if(is_seed2(P.form)) rc = launch_seed_groups(ctx, S, P, T, fa, sink);
+		else if(is_seed2(P.form)) rc = launch_seed_groups(ctx, S, P, L, T, fa, sink);
 		if(rc != PCR_OK) return rc;
 		if(P.need_seedset && (rc = launch_scan2(ctx, S, T.seedset.T, ncand, sink, T.seedset.d_tab, T.seedset.d_bias, S.degen_tiles.p, S.n_degen_tiles,
 			T.seedset.d_map)) != PCR_OK) return rc;
@@ -711,23 +779,24 @@ int launch_scans(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const StagedTables 
 // The whole tail -- DB finalisation and the amplicon screen -- in one launch: k_post (64-slot buckets, WAVES sequences per
 // workgroup) or k_post_big (128 / 256 slots).
 template<class K>
-void launch_post(K kernel, uint32_t waves, pcr_ctx *ctx, SeqSet &S, const HitSink &sink, const FusedAmp *fa)
+void launch_post(K kernel, uint32_t waves, pcr_ctx *ctx, SeqSet &S, const HitSink &sink, const FusedAmp *fa, uint32_t seq)
 {
 	hipLaunchKernelGGL(kernel, dim3((S.n + waves - 1)/waves), dim3(64*waves), 0, ctx->stream, sink.hits, sink.seq_count, sink.best, sink.ncand, S.planes.p,
 		S.d_blk_off.p, S.irr.p, S.irr_off.p, S.db.p, S.d_seg_hi, sink.counters, sink.epoch, S.n,
 		fa->d_oligos, fa->n_pairs, (2*fa->n_pairs + 31)/32, S.d_len.p, S.d_active.p, fa->a->amp_min, fa->a->amp_max,
-		fa->a->ident_threshold, fa->a->use_taq_mama, fa->d_fr, fa->d_rf, (uint64_t)((S.n + 63)/64), ctx->mail_dev + (ctx->mail_seq % pcr_ctx::MAIL_RING), ctx->mail_seq);
+		fa->a->ident_threshold, fa->a->use_taq_mama, fa->d_fr, fa->d_rf, (uint64_t)((S.n + 63)/64), ctx->mail_dev + (seq % pcr_ctx::MAIL_RING), seq);
 }
-int fused_tail(pcr_ctx *ctx, SeqSet &S, const HitSink &sink, FusedAmp *fa)
+// reserved_seq: the sequence number a pipelined pass was given at enqueue; 0: the next one
+int fused_tail(pcr_ctx *ctx, SeqSet &S, const HitSink &sink, FusedAmp *fa, uint32_t reserved_seq)
 {
-	++ctx->mail_seq;
+	const uint32_t seq = reserved_seq ? reserved_seq : ++ctx->mail_seq;
 	if(sink.cap == POST_CAP){
 		// 8 waves per workgroup: 4 and 16 measured within the noise of 8 (profiles/dbg/r03_ab_post_waves.txt)
-		launch_post(k_post<8>, 8, ctx, S, sink, fa);
+		launch_post(k_post<8>, 8, ctx, S, sink, fa, seq);
 		S.ctrl_clean = true; S.touched_from_seg = true;              // k_post zeroes the counters and fills it has read
 	}
-	else if(sink.cap == 128) launch_post(k_post_big<128, 4>, 4, ctx, S, sink, fa);
-	else launch_post(k_post_big<256, 4>, 4, ctx, S, sink, fa);
+	else if(sink.cap == 128) launch_post(k_post_big<128, 4>, 4, ctx, S, sink, fa, seq);
+	else launch_post(k_post_big<256, 4>, 4, ctx, S, sink, fa, seq);
 	HIP_TRY(hipGetLastError());
 	fa->posted = true;
 	S.touched_built = false;
@@ -785,25 +854,69 @@ uint32_t resized_buckets(bool overflowed, uint32_t cap, uint32_t largest_fill, i
 	return (want*4 <= cap) ? want : 0;
 }
 
-// pcr_select_words proper.  async: enqueue one attempt and return without looking at the counters
-// (pcr_screen_device; the caller records the pass as pending).
-int select_impl(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs, int optimize_5, int optimize_3,
-	float threshold, uint32_t min_oligo_length, uint64_t *n_entries_out, bool async, FusedAmp *fa = nullptr)
+// The buckets a fused tail handles, and the pair count its masks hold.
+inline bool fused_tail_fits(uint32_t cap, uint32_t n_pairs) { return (cap == POST_CAP || cap == 128 || cap == 256) && 2*n_pairs <= 32*POST_MASK_WORDS; }
+inline bool buckets_fit(uint64_t n_slots) { return n_slots < (uint64_t(1) << 32) && n_slots*(sizeof(Hit) + sizeof(DevEntry)) <= (uint64_t(96) << 30); }
+
+// The markers a pass resets before anything else; returns whether the previous pass's fused tail left the control block clean.
+inline bool begin_pass(SeqSet &S)
 {
-	if(!ctx || (n_pairs && !pairs)){ g_err = "pcr_select_words: bad argument"; return PCR_ERR_ARG; }
-	if(min_oligo_length < 1 || min_oligo_length > 32){ g_err = "pcr_select_words: min_oligo_length must be in [1,32]"; return PCR_ERR_ARG; }
-	HIP_TRY(hipSetDevice(ctx->device));
-	SeqSet &S = ctx->sets[which];
 	S.have_db = false; S.n_entries = 0;
-	if(n_entries_out) *n_entries_out = 0;
-	const bool ctrl_was_clean = S.ctrl_clean;         // left so by the fused tail of the previous pass over this set
+	const bool ctrl_was_clean = S.ctrl_clean;
 	S.ctrl_clean = false; S.touched_from_seg = false;
+	return ctrl_was_clean;
+}
+
+// Stage A: candidates, scan plan and host tables of the pass into J -- no launch; device work only where the plan has to build an
+// index of the set first (never in a pipelined pass: plans_without_device_work).
+int plan_pass(pcr_ctx *ctx, PassJob &J, const pcr_pair *pairs, uint32_t n_pairs)
+{
+	SeqSet &S = ctx->sets[J.which];
 	HostTimer timer(ctx, 0);
 	if(ctx->timing) ++ctx->n_timed;
-	std::vector<pcrhost::Candidate> cand;
-	pcrhost::build_candidates((const uint64_t *)pairs, n_pairs, optimize_5 != 0, optimize_3 != 0, threshold, cand);
-	const uint32_t ncand = (uint32_t)cand.size();
+	pcrhost::build_candidates((const uint64_t *)pairs, n_pairs, J.opt5 != 0, J.opt3 != 0, J.thr, J.cand);
+	const uint32_t ncand = (uint32_t)J.cand.size();
+	if(S.n == 0 || ncand == 0) return PCR_OK;
+	int rc;
+	if((rc = choose_scan_form(ctx, S, J.cand, J.opt5, J.opt3, J.min_len, J.P, J.L)) != PCR_OK) return rc;
+	if(ctx->debug_log) fprintf(stderr, "[pcramp] scan plan: form=%s, %u candidates, %zu seeded orientations (%zu seeds), %zu plain, %u/%u IUPAC tiles, %u-slot buckets\n",
+		form_name(J.P.form), ncand, J.P.or_seed.size(), J.P.n_seeds, J.P.or_plain.size(), S.n_degen_tiles, S.n_tiles, S.bucket_cap);
+	prepare_tables(S, J, J.has_fa ? &J.fa : nullptr);
+	return PCR_OK;
+}
+
+// Would planning a default pass over S leave the device alone?  The position index is built (or will not be asked for) and so is
+// the index of the irregular words, where a scan may want it.
+bool plans_without_device_work(const pcr_ctx *ctx, const SeqSet &S, int opt5, int opt3, uint32_t min_len)
+{
+	if(ctx->scan_version != 3 || opt5 || opt3 || ctx->force_seed1) return false;             // (not the second or third form anyway)
+	const bool may_want_seed3 = !ctx->no_seed3 && !ctx->no_irr_index && ctx->s2_dbg == 0;
+	if(may_want_seed3 && !S.pix_valid) return false;
+	if(live_irregular(S, min_len) == 0 || ctx->no_irr_index) return true;
+	return S.irr_n_multi != 0 || (uint64_t)24*S.n_irr >= (uint64_t(1) << 32) || S.irx_valid;   // irr_index_usable() would build nothing
+}
+
+// Can stage B of the planned pass J run on the launcher thread?  A non-empty, fused, asynchronous pass of the second or third
+// form whose buckets fit: run_pass then takes exactly one attempt, ends in fused_tail and touches no state stage A reads.
+bool pass_is_pipelinable(const pcr_ctx *ctx, const PassJob &J)
+{
+	const SeqSet &S = ctx->sets[J.which];
+	return J.async && J.has_fa && J.fuse && S.n != 0 && !J.cand.empty() && is_seed2(J.P.form)
+		&& fused_tail_fits(S.bucket_cap, J.fa.n_pairs) && buckets_fit((uint64_t)S.n*S.bucket_cap);
+}
+
+// Stage B: size the device buffers, stage the tables, launch the scans and the tail.  async: one attempt, nobody looks at the
+// counters (pcr_screen_device; the caller has recorded or will record the pass as pending).
+int run_pass(pcr_ctx *ctx, PassJob &J, uint64_t *n_entries_out)
+{
+	SeqSet &S = ctx->sets[J.which];
+	FusedAmp *const fa = J.has_fa ? &J.fa : nullptr;
+	const bool async = J.async;
+	const bool ctrl_was_clean = J.begun ? J.ctrl_was_clean : begin_pass(S);
+	const ScanPlan &P = J.P;
+	const uint32_t ncand = (uint32_t)J.cand.size();
 	if(S.n == 0 || ncand == 0){ S.have_db = true; S.n_touched = 0; return PCR_OK; }
+	HostTimer timer(ctx, 1);
 	int rc;
 	if((rc = ctx->best.ensure((size_t)S.n*ncand)) != PCR_OK) return rc;
 	if(ctx->best.generation != ctx->best_seen){
@@ -811,12 +924,8 @@ int select_impl(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_p
 		HIP_TRY(hipMemsetAsync(ctx->best.p, 0, ctx->best.cap*sizeof(uint32_t), ctx->stream));
 		ctx->best_seen = ctx->best.generation; ctx->epoch = std::min(ctx->debug_epoch, EPOCH_LIMIT);
 	}
-	ScanPlan P;
-	if((rc = choose_scan_form(ctx, S, cand, optimize_5, optimize_3, min_oligo_length, P)) != PCR_OK) return rc;
-	if(ctx->debug_log) fprintf(stderr, "[pcramp] scan plan: form=%s, %u candidates, %zu seeded orientations (%zu seeds), %zu plain, %u/%u IUPAC tiles, %u-slot buckets\n",
-		form_name(P.form), ncand, P.or_seed.size(), P.n_seeds, P.or_plain.size(), S.n_degen_tiles, S.n_tiles, S.bucket_cap);
 	StagedTables T;
-	if((rc = stage_tables(ctx, S, cand, P, fa, async, ctrl_was_clean, timer, T)) != PCR_OK) return rc;
+	if((rc = stage_tables(ctx, S, J, fa, async, ctrl_was_clean, T)) != PCR_OK) return rc;
 
 	timer.next(2);
 	uint32_t h_counters[4];
@@ -825,7 +934,8 @@ int select_impl(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_p
 	for(int attempt = 0;;++attempt){
 		const uint32_t cap = S.bucket_cap;
 		const uint64_t n_slots = (uint64_t)S.n*cap;
-		if(n_slots >= (uint64_t(1) << 32) || n_slots*(sizeof(Hit) + sizeof(DevEntry)) > (uint64_t(96) << 30)){
+		if(!buckets_fit(n_slots)){
+			assert(J.seq == 0);                              // (pass_is_pipelinable)
 			S.bucket_cap = 64;   // (the size that was refused must not stay: the next pass over this set, with other candidates, starts small and grows again)
 			g_err = "pcr_select_words: the per-sequence hit buckets would not fit (too many tied sites per sequence)"; return PCR_ERR_CAPACITY;
 		}
@@ -841,9 +951,10 @@ int select_impl(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_p
 		++ctx->epoch;
 		HitSink sink; sink.best = ctx->best.p; sink.hits = ctx->hits.p; sink.seq_count = S.ctrl.p + 8;
 		sink.counters = S.ctrl.p; sink.cap = cap; sink.ncand = ncand; sink.epoch = ctx->epoch;
-		if((rc = launch_scans(ctx, S, P, T, fa, sink)) != PCR_OK) return rc;
-		const bool fused = async && fa && fa->staged && (cap == POST_CAP || cap == 128 || cap == 256) && 2*fa->n_pairs <= 32*POST_MASK_WORDS;
-		if((rc = fused ? fused_tail(ctx, S, sink, fa) : plain_tail(ctx, S, sink, async, fa)) != PCR_OK) return rc;
+		const bool fused = async && fa && fa->staged && fused_tail_fits(cap, fa->n_pairs);
+		if(J.seq && !fused){ g_err = "pcr_screen_device: a pipelined pass lost its fused tail"; return PCR_ERR_STATE; }   // (pass_is_pipelinable: cannot happen)
+		if((rc = launch_scans(ctx, S, P, J.L, T, fa, sink)) != PCR_OK) return rc;
+		if((rc = fused ? fused_tail(ctx, S, sink, fa, J.seq) : plain_tail(ctx, S, sink, async, fa)) != PCR_OK) return rc;
 		if(async){
 			S.db_cap = cap; S.n_slots = n_slots;
 			S.n_touched = N_TOUCHED_UNKNOWN; S.n_entries = 1; S.have_db = true;
@@ -870,11 +981,234 @@ int select_impl(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_p
 	return PCR_OK;
 }
 
+void fill_job(pcr_ctx *ctx, PassJob &J, pcr_set which, int optimize_5, int optimize_3, float threshold, uint32_t min_oligo_length, bool async, const FusedAmp *fa)
+{
+	J.ctx = ctx; J.which = (int)which; J.opt5 = optimize_5; J.opt3 = optimize_3; J.thr = threshold; J.min_len = min_oligo_length; J.async = async;
+	J.has_fa = fa != nullptr;
+	if(fa){ J.fa = *fa; J.args = *fa->a; J.fa.a = &J.args; }            // (the job outlives the call: it keeps the arguments by value)
+}
+
+// pcr_select_words proper, and the inline pcr_screen_device pass: stage A and stage B on the calling thread, with a job on the
+// stack.  fa: in/out (staged, posted, pub_*).
+int select_impl(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs, int optimize_5, int optimize_3,
+	float threshold, uint32_t min_oligo_length, uint64_t *n_entries_out, bool async, FusedAmp *fa = nullptr)
+{
+	if(!ctx || (n_pairs && !pairs)){ g_err = "pcr_select_words: bad argument"; return PCR_ERR_ARG; }
+	if(min_oligo_length < 1 || min_oligo_length > 32){ g_err = "pcr_select_words: min_oligo_length must be in [1,32]"; return PCR_ERR_ARG; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	if(n_entries_out) *n_entries_out = 0;
+	assert(ctx->lq_client.queued.load() == 0);           // inline: every caller came through DRAIN or flush_launcher
+	PassJob J;
+	fill_job(ctx, J, which, optimize_5, optimize_3, threshold, min_oligo_length, async, fa);
+	J.ctrl_was_clean = begin_pass(ctx->sets[which]); J.begun = true;
+	int rc = plan_pass(ctx, J, pairs, n_pairs);
+	if(rc == PCR_OK) rc = run_pass(ctx, J, n_entries_out);
+	if(fa){ const pcr_amplify_args *a = fa->a; *fa = J.fa; fa->a = a; }
+	return rc;
+}
+
+// ---- the launcher thread of a stream (pcr_launch_queue.hpp) and the handles' side of it
+
+// One per (device, stream), shared by every handle created on that stream and counted by them: the passes of several handles
+// on one stream (an optimiser screens target, background and multiplex sets in turn, into buffers it alternates) must reach the
+// stream in call order.  Made by the first pipelined pass; stopped and joined when its last handle is destroyed.
+struct Launcher {
+	int device; hipStream_t stream; unsigned refs = 0;
+	cpu_set_t near; bool have_near = false;     // where the thread should run: see near_cpus()
+	pcrq::LaunchQueue q;
+	Launcher(int dev, hipStream_t st, unsigned spin_us);
+};
+std::mutex g_launchers_m;
+std::vector<Launcher *> g_launchers;
+
+PassJob *acquire_job(pcr_ctx *ctx)
+{
+	PassJob *J = nullptr;
+	{
+		std::lock_guard<std::mutex> lk(ctx->job_m);
+		if(!ctx->job_free.empty()){ J = ctx->job_free.back(); ctx->job_free.pop_back(); }
+	}
+	if(!J){ J = new PassJob(); ctx->job_all.push_back(J); }
+	return J;
+}
+void release_job(pcr_ctx *ctx, PassJob *J)
+{
+	J->reset();
+	std::lock_guard<std::mutex> lk(ctx->job_m);
+	ctx->job_free.push_back(J);
+}
+void free_jobs(pcr_ctx *ctx)
+{
+	for(PassJob *J : ctx->job_all) delete J;
+	ctx->job_all.clear(); ctx->job_free.clear();
+}
+
+// After its last job the thread spins on the queue this long before it blocks: a pass arrives every 15-25 us while a caller
+// screens, and a condition-variable wake-up costs more than that.  Bounded: the process has 16 cores, and an idle handle must
+// cost none (PCRAMP_LAUNCH_SPIN_US for the A/B).
+constexpr unsigned LAUNCH_SPIN_US = 200;
+
+// A CPU list of sysfs ("0-7,64-71") as a set.
+bool read_cpu_list(const std::string &path, cpu_set_t &set)
+{
+	CPU_ZERO(&set);
+	FILE *f = fopen(path.c_str(), "r");
+	if(!f) return false;
+	char buf[4096]; const bool got = fgets(buf, sizeof(buf), f) != nullptr;
+	fclose(f);
+	if(!got) return false;
+	for(const char *p = buf;*p && *p != '\n';){
+		char *e; const long a = strtol(p, &e, 10);
+		if(e == p) return false;
+		long b = a;
+		if(*e == '-'){ p = e + 1; b = strtol(p, &e, 10); if(e == p) return false; }
+		for(long c = a;c <= b && c < CPU_SETSIZE;++c) CPU_SET((int)c, &set);
+		p = (*e == ',') ? e + 1 : e;
+	}
+	return true;
+}
+// The CPUs the launcher thread should run on: those that share the last-level cache with the CPU the caller is on, without the
+// caller's own core.  Every pass hands some 25 KB of freshly written tables from the caller's thread to the launcher's; with the
+// two threads on different sockets or cache domains those lines cross the fabric one by one and stage A ran 2-3x slower than
+// inline.  false (no pinning): not Linux's sysfs, or nothing left after the process's own affinity mask.
+bool near_cpus(cpu_set_t &out)
+{
+	const int cpu = sched_getcpu();
+	if(cpu < 0) return false;
+	const std::string base = "/sys/devices/system/cpu/cpu" + std::to_string(cpu);
+	cpu_set_t llc, core, allowed;
+	if(!read_cpu_list(base + "/cache/index3/shared_cpu_list", llc)) return false;
+	if(!read_cpu_list(base + "/topology/thread_siblings_list", core)) CPU_ZERO(&core);
+	CPU_SET(cpu, &core);
+	if(sched_getaffinity(0, sizeof(allowed), &allowed) != 0) return false;
+	CPU_ZERO(&out);
+	for(int c = 0;c < CPU_SETSIZE;++c){ if(CPU_ISSET(c, &llc) && CPU_ISSET(c, &allowed) && !CPU_ISSET(c, &core)) CPU_SET(c, &out); }
+	return CPU_COUNT(&out) > 0;
+}
+
+Launcher::Launcher(int dev, hipStream_t st, unsigned spin_us) : device(dev), stream(st),
+	q([](void *job, std::string &err) -> int {
+		PassJob &J = *(PassJob *)job;
+		assert(J.seq != 0 && J.ctx->launcher);
+		const int rc = run_pass(J.ctx, J, nullptr);
+		if(rc != PCR_OK) err = g_err;                     // (this thread's: the handle's next call copies it into its own)
+		return rc;
+	},
+	[](void *job){ PassJob *J = (PassJob *)job; release_job(J->ctx, J); },
+	[this]{
+		if(have_near) (void)pthread_setaffinity_np(pthread_self(), sizeof(near), &near);
+		(void)hipSetDevice(device);
+	},
+	spin_us)
+{
+	const char *v = getenv("PCRAMP_LAUNCH_PIN");           // =0: leave the thread's placement to the scheduler (A/B)
+	have_near = !(v && v[0] == '0') && near_cpus(near);
+}
+
+Launcher *attach_launcher(pcr_ctx *ctx)
+{
+	if(ctx->launcher) return ctx->launcher;
+	std::lock_guard<std::mutex> lk(g_launchers_m);
+	for(Launcher *L : g_launchers){ if(L->device == ctx->device && L->stream == ctx->stream){ ++L->refs; return ctx->launcher = L; } }
+	unsigned spin = LAUNCH_SPIN_US;
+	if(const char *v = getenv("PCRAMP_LAUNCH_SPIN_US")) spin = (unsigned)std::min<unsigned long>(strtoul(v, nullptr, 0), 10000ul);
+	Launcher *L = new Launcher(ctx->device, ctx->stream, spin);
+	if(ctx->debug_log || ctx->timing) fprintf(stderr, "[pcramp] launcher thread for stream %p: caller on cpu %d, launcher %s (%d cpus), spin %u us\n", (void *)ctx->stream,
+		sched_getcpu(), L->have_near ? "pinned beside it" : "not pinned", L->have_near ? CPU_COUNT(&L->near) : 0, spin);
+	L->refs = 1;
+	g_launchers.push_back(L);
+	return ctx->launcher = L;
+}
+// pcr_destroy, after the handle's flush
+void detach_launcher(pcr_ctx *ctx)
+{
+	Launcher *L = ctx->launcher;
+	if(!L) return;
+	ctx->launcher = nullptr;
+	{
+		std::lock_guard<std::mutex> lk(g_launchers_m);
+		if(--L->refs) return;
+		g_launchers.erase(std::find(g_launchers.begin(), g_launchers.end(), L));
+	}
+	L->q.stop();                                          // joins the thread
+	delete L;
+}
+
+// Wait for the handle's queued passes to be launched.  One of them failed: its error comes back here, once, with the message in
+// this thread's g_err; the passes queued behind it were dropped, and none of them stays pending.
+int flush_launcher(pcr_ctx *ctx)
+{
+	if(!ctx->launcher) return PCR_OK;
+	ctx->launcher->q.flush(&ctx->lq_client);
+	int code; std::string msg; uint32_t seq;
+	if(!ctx->lq_client.take_error(code, msg, seq)) return PCR_OK;
+	std::vector<pcr_ctx::Pending> &pd = ctx->pending;
+	pd.erase(std::remove_if(pd.begin(), pd.end(), [&](const pcr_ctx::Pending &q){ return (int32_t)(q.seq - seq) >= 0; }), pd.end());
+	g_err = msg;
+	return code;
+}
+
+// pcr_screen_device proper.  By default the pass is pipelined: this thread plans it (stage A) and hands it to the stream's
+// launcher thread (stage B), which may still be staging and launching the previous one.  A pass whose planning or launch needs
+// more than that -- the first over a set (it builds the index), first-form tables, shift candidates, a tail that is not fused --
+// flushes the queue and runs inline, as every pass does with PCRAMP_LAUNCH_THREAD=0.
+int screen_pass(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs, int optimize_5, int optimize_3,
+	float select_threshold, uint32_t min_oligo_length, const pcr_amplify_args *args, uint64_t *d_bits_fr, uint64_t *d_bits_rf)
+{
+	if(min_oligo_length < 1 || min_oligo_length > 32){ g_err = "pcr_select_words: min_oligo_length must be in [1,32]"; return PCR_ERR_ARG; }
+	int rc;
+	if(ctx->lq_client.poisoned.load(std::memory_order_acquire) && (rc = flush_launcher(ctx)) != PCR_OK) return rc;
+	HIP_TRY(hipSetDevice(ctx->device));
+	SeqSet &S = ctx->sets[which];
+	FusedAmp fa; fa.pairs = pairs; fa.n_pairs = n_pairs; fa.a = args; fa.d_fr = d_bits_fr; fa.d_rf = d_bits_rf;
+	PassJob *J = acquire_job(ctx);
+	fill_job(ctx, *J, which, optimize_5, optimize_3, select_threshold, min_oligo_length, true, &fa);
+	bool inline_pass = !ctx->launch_thread || !plans_without_device_work(ctx, S, optimize_5, optimize_3, min_oligo_length);
+	if(inline_pass){
+		if((rc = flush_launcher(ctx)) != PCR_OK){ release_job(ctx, J); return rc; }
+		J->ctrl_was_clean = begin_pass(S); J->begun = true;
+	}
+	rc = plan_pass(ctx, *J, pairs, n_pairs);
+	if(rc == PCR_OK && !inline_pass && !pass_is_pipelinable(ctx, *J)){
+		inline_pass = true;
+		rc = flush_launcher(ctx);
+	}
+	if(rc != PCR_OK){
+		if(!J->begun){ (void)flush_launcher(ctx); (void)begin_pass(S); }      // (a failed plan leaves the set as it always has: without a DB)
+		release_job(ctx, J);
+		return rc;
+	}
+	pcr_ctx::Pending p;
+	p.which = (int)which; p.pairs.assign(pairs, pairs + n_pairs); p.opt5 = optimize_5; p.opt3 = optimize_3;
+	p.thr = select_threshold; p.min_len = min_oligo_length; p.args = *args; p.d_fr = d_bits_fr; p.d_rf = d_bits_rf;
+	if(!inline_pass){
+		Launcher *L = attach_launcher(ctx);
+		p.seq = J->seq = ++ctx->mail_seq;
+		J->fa.pairs = nullptr;                                          // (the caller's array: stage A is done with it)
+		ctx->pending.push_back(std::move(p));
+		++ctx->n_pipelined;
+		L->q.push(&ctx->lq_client, J, J->seq);
+		return PCR_OK;
+	}
+	assert(ctx->lq_client.queued.load() == 0);           // stage B on this thread: the launcher thread holds no pass of the handle
+	const uint32_t seq0 = ctx->mail_seq;
+	rc = run_pass(ctx, *J, nullptr);
+	if(rc == PCR_OK && !J->fa.posted) rc = amplify_launch(ctx, S, pairs, n_pairs, args, d_bits_fr, d_bits_rf, &J->fa);
+	release_job(ctx, J);
+	if(rc != PCR_OK) return rc;
+	if(ctx->mail_seq != seq0){                                        // a pass was enqueued (not the empty-input shortcut)
+		p.seq = ctx->mail_seq;
+		ctx->pending.push_back(std::move(p));
+	}
+	return PCR_OK;
+}
+
 // Look at the counters of the passes pcr_screen_device enqueued.  A pass whose buckets overflowed produced
 // an incomplete DB (and so possibly incomplete amplification bits): grow the buckets and replay it and
 // everything enqueued after it, synchronously, into the same output buffers.
 int drain(pcr_ctx *ctx)
 {
+	{ const int frc = flush_launcher(ctx); if(frc != PCR_OK) return frc; }
 	if(ctx->pending.empty()) return PCR_OK;
 	std::vector<pcr_ctx::Pending> pend;
 	pend.swap(ctx->pending);

@@ -236,12 +236,13 @@ int select_sites_impl(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32
 	S.ctrl_clean = false; S.touched_from_seg = false;
 	HostTimer timer(ctx, 0);
 	if(ctx->timing) ++ctx->n_timed;
-	std::vector<pcrhost::Candidate> cand;
+	PassJob J;
+	std::vector<pcrhost::Candidate> &cand = J.cand;
 	pcrhost::build_candidates((const uint64_t *)pairs, n_pairs, false, false, threshold, cand);
 	const uint32_t ncand = (uint32_t)cand.size();
 	if(S.n == 0 || ncand == 0){ S.have_db = true; S.n_touched = 0; return PCR_OK; }
 	int rc;
-	ScanPlan P;
+	ScanPlan &P = J.P;
 	P.form = ScanForm::BitSliced; P.need_plain = true;
 	P.min_len = min_oligo_length; P.n_live = live_irregular(S, min_oligo_length);
 	P.or_plain.resize(2*(size_t)ncand);
@@ -249,7 +250,9 @@ int select_sites_impl(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32
 	if(ctx->debug_log) fprintf(stderr, "[pcramp] all-sites plan: %u candidates, %u/%u IUPAC tiles, %u live irregular words, %u-slot buckets\n",
 		ncand, S.n_degen_tiles, S.n_tiles, P.n_live, S.bucket_cap);
 	StagedTables T;
-	if((rc = stage_tables(ctx, S, cand, P, nullptr, false, false, timer, T)) != PCR_OK) return rc;
+	prepare_tables(S, J, nullptr);
+	timer.next(1);
+	if((rc = stage_tables(ctx, S, J, nullptr, false, false, T)) != PCR_OK) return rc;
 
 	timer.next(2);
 	uint32_t h_counters[4];
