@@ -233,6 +233,11 @@ int pcr_staging_mode(pcr_ctx *ctx);
  * inline on the calling thread), and the largest number of them queued there at once.  Either pointer may be NULL. */
 int pcr_launcher_stats(pcr_ctx *ctx, uint64_t *passes_pipelined, uint32_t *max_queue_depth);
 
+/* What the handles of this process hold on the device right now: out[0] = bytes of device memory, out[1] = bytes of host-mapped
+ * pinned memory, out[2] = HIP events, out[3] = streams the library created itself (a stream passed to pcr_create is borrowed and
+ * not counted).  Process-wide and needs no handle; all four are back at their earlier values once a handle is destroyed. */
+int pcr_live_resources(uint64_t out[4]);
+
 /* ---- multi-GPU: the path's one exchange step.  Targets shard across ranks (one process per GPU,
  * contiguous blocks whose boundaries are multiples of 64 sequences, so every rank owns whole bitset words); the primer pairs are
  * replicated; after a pass every rank needs every rank's orientation bitsets.  This replaces what the reference's MPI mode does

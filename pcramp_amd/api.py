@@ -129,7 +129,7 @@ ABI_SYMBOLS = [
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
-    "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats",
+    "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats", "pcr_live_resources",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
     "pcr_shard_gather_bits", "pcr_shard_sampler_targets", "pcr_design_trial_ranks", "pcr_design_trial_world",
     "pcr_comm_unique_id", "pcr_comm_init_rank", "pcr_comm_world", "pcr_comm_rank", "pcr_exchange_bits", "pcr_comm_destroy", "pcr_comm_library",
@@ -187,6 +187,7 @@ def load_library():
     L.pcr_synchronize.argtypes = [C.c_void_p]
     L.pcr_staging_mode.argtypes = [C.c_void_p]
     L.pcr_launcher_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    L.pcr_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     L.pcr_comm_unique_id.argtypes = [C.c_void_p]
     L.pcr_comm_init_rank.restype = C.c_void_p
     L.pcr_comm_init_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
@@ -255,6 +256,16 @@ def load_library():
 
 def _err(L):
     return (L.pcr_last_error() or b"").decode()
+
+
+def live_resources():
+    """(device bytes, host-mapped bytes, events, streams the library created) that the handles of this process hold right
+    now (pcr_live_resources): back at its earlier value once a handle is closed."""
+    L = load_library()
+    out = (C.c_uint64 * 4)()
+    if L.pcr_live_resources(out) != 0:
+        raise PcrError(_err(L))
+    return tuple(int(v) for v in out)
 
 
 # ---------------------------------------------------------------------------- host-only helpers

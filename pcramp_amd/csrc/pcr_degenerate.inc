@@ -90,7 +90,6 @@ int degenerate_amplicons(pcr_ctx *ctx, SeqSet &S, const pcr_pair *assays, uint32
 	if(e == hipSuccess) e = hipMemcpyAsync(recs.data(), d_recs, (size_t)n_amp*sizeof(AmpRec), hipMemcpyDeviceToHost, ctx->stream);
 	if(e == hipSuccess) e = hipMemcpyAsync(words.data(), d_words.p, 2*(size_t)n_amp*sizeof(uint4), hipMemcpyDeviceToHost, ctx->stream);
 	if(e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-	d_words.release();
 	if(e != hipSuccess){ g_err = std::string("pcr_make_degenerate: ") + hipGetErrorString(e); return PCR_ERR_DEVICE; }
 	for(uint32_t k = 0;k < n_amp;++k){                                            // (sorted by pair, inside a pair in the reference's order)
 		if(recs[k].pair >= n) continue;

@@ -60,9 +60,12 @@
 
 using pcrhost::Planes;
 
+namespace { thread_local std::string g_err; }
+#include "pcr_owned.hpp"
+
 namespace {
 
-thread_local std::string g_err;
+using pcrown::DevBuf; using pcrown::MappedBuf; using pcrown::Event; using pcrown::Stream;
 
 #define HIP_TRY(expr) do{ hipError_t e_ = (expr); if(e_ != hipSuccess){ \
 	g_err = std::string(#expr) + ": " + hipGetErrorString(e_); return PCR_ERR_DEVICE; } }while(0)
@@ -608,26 +611,6 @@ __global__ __launch_bounds__(FINBIG_THREADS) void k_finalize_big(const Hit *__re
 constexpr uint32_t N_TOUCHED_UNKNOWN = 0xFFFFFFFFu;
 constexpr uint32_t EPOCH_LIMIT = (1u << 24) - 1;    // largest pass epoch that fits the 24-bit tag of best[]
 
-template<class T> struct DevBuf {
-	T *p = nullptr; size_t cap = 0;
-	uint64_t generation = 0;     // bumped by every (re)allocation: the contents are undefined afterwards
-	int ensure(size_t n)
-	{
-		if(n <= cap) return PCR_OK;
-		++generation;
-		if(p){ (void)hipFree(p); p = nullptr; cap = 0; }
-		const size_t want = std::max<size_t>(n, 16);
-		hipError_t e = hipMalloc((void **)&p, want*sizeof(T));
-		if(e != hipSuccess){ g_err = std::string("hipMalloc: ") + hipGetErrorString(e); return PCR_ERR_DEVICE; }
-		cap = want;
-		return PCR_OK;
-	}
-	// for lists that grow a little at a time (the irregular words after every batch of splits): a quarter of slack, so that a hipFree +
-	// hipMalloc pair -- a device-wide wait each -- is not paid on every growth
-	int ensure_slack(size_t n) { return (n <= cap) ? PCR_OK : ensure(n + n/4 + 1024); }
-	void release() { if(p){ (void)hipFree(p); p = nullptr; cap = 0; } }
-};
-
 struct SeqSet {
 	uint32_t n = 0;
 	std::vector<std::vector<uint8_t> > packed;   // host copy (split_sequence, irregular re-derivation)
@@ -669,12 +652,6 @@ struct SeqSet {
 	uint32_t n_touched = 0;
 	bool touched_built = false;   // touched[] / counters[3] hold the list of the last pass (the fused tail does not build it)
 	uint32_t *d_seg_hi = nullptr;
-	void release()
-	{
-		d_weight.release(); tile_desc.release(); irr_scan.release(); irx_first.release(); irx_last.release(); irx_words.release(); irx_sums.release(); pix_first.release(); pix_last.release(); pix_ent.release(); pix_sums.release(); blk_info.release(); blk_local.release(); blk_tile0.release(); irr_perm.release(); planes.release(); valid.release(); nib.release(); tb.release(); degen_tiles.release(); tile_degen.release(); blk_seq.release(); tile_seq.release(); tile_pos0.release();
-		irr_off.release(); d_len.release(); d_blk_off.release();
-		d_nblk_real.release(); d_active.release(); d_has_eos.release(); irr.release(); db.release(); touched.release(); ctrl.release(); codes.release(); d_code_off.release();
-	}
 };
 
 } // namespace
@@ -720,11 +697,12 @@ struct pcr_ctx {
 		if(!pool_){ const unsigned hw = std::max(1u, std::thread::hardware_concurrency()); pool_.reset(new HostPool(std::min(hw, 16u) - 1u)); }   // (a GPU box gives its process 16 cores)
 		return *pool_;
 	}
-	hipStream_t stream = nullptr;
-	bool own_stream = false;
+	// Every device resource below frees itself (pcr_owned.hpp).  The streams come first so that they are destroyed last, after
+	// every buffer and event; pcr_destroy synchronises both before it deletes the handle.
+	Stream stream;                      // created by pcr_create, or the caller's (borrowed: never destroyed here)
+	Stream aux_stream;                  // the optimiser's thermodynamics run here, beside the coverage passes on `stream` (pcr_optimize.inc); created on first use
 	std::string design_text;            // the output file of the last pcr_design call
 	DevBuf<uint64_t> split_where;       // pcr_split_many's (block, bit) list
-	hipStream_t aux_stream = nullptr;   // the optimiser's thermodynamics run here, beside the coverage passes on `stream` (pcr_optimize.inc); created on first use
 	pcr_params params;
 	pcrhost::PackFilter filt;
 	SeqSet sets[PCR_N_SETS];   // target, background, multiplex (accepted amplicons), scratch (pcr_multiplex_screen's trial amplicons)
@@ -756,7 +734,7 @@ struct pcr_ctx {
 	float th_dg_salt = -1.0f;   // salt the table in th_dg was built for
 	DevBuf<unsigned long long> th_dbg; bool th_attr_set = false;
 	std::vector<thermo::Job> th_host_jobs; std::vector<thermo::JobOut> th_host_res;   // pcr_thermo's job records and results, kept between calls
-	uint8_t *sw_pin = nullptr, *sw_pin_dev = nullptr; hipEvent_t sw_done[2] = {nullptr, nullptr};   // pcr_sw_align_words: two pinned chunk buffers (words in, results out)
+	MappedBuf<uint8_t> sw_pin; Event sw_done[2];   // pcr_sw_align_words: two pinned chunk buffers (words in, results out)
 	DevBuf<pcr_amplicon> mx_amp;   // pcr_collect_amplicons records
 	DevBuf<OligoDev> opt_oligos; DevBuf<uint2> opt_jobs; DevBuf<float> opt_cov; DevBuf<uint32_t> opt_loc, opt_tasks;   // pcr_optimize_batch: base oligos + trial words, per-oligo variant ranges, coverages
 	DevBuf<Planes> mx_keys; uint32_t mx_n_keys = 0; DevBuf<uint32_t> mx_count;   // multiplex background: unique words of the accepted amplicons (pcr_multiplex.inc)
@@ -791,24 +769,25 @@ struct pcr_ctx {
 	// ring of host-mapped staging buffers: a slot is rewritten only after the k_stage that read it has run,
 	// so the host can prepare the next pass while the previous one is still on the GPU
 	static constexpr int STAGE_RING = 4;
-	struct StageSlot { uint8_t *host = nullptr, *dev = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool busy = false;
+	struct StageSlot { MappedBuf<uint8_t> buf; Event done; bool busy = false;
 	                   uint32_t guard_seq = 0; /* != 0: free once the pass with this mailbox sequence number has published */ };
 	StageSlot stage[STAGE_RING]; int stage_next = 0;
 	// The lean form of the fused pass needs no staging launch at all: its tables are written by the CPU straight into
 	// fine-grained DEVICE memory (large BAR: posted writes, ordered before the doorbell of the launch that follows; measured
 	// 0.6 us for 32 KB, profiles/microbench/bar_write.hip), a ring of its own because the kernels read the slot itself.
-	StageSlot dstage[STAGE_RING]; int dstage_next = 0;
+	struct DirectSlot { DevBuf<uint8_t> buf{true}; uint32_t guard_seq = 0; };
+	DirectSlot dstage[STAGE_RING]; int dstage_next = 0;
 	bool direct_ok = false;       // fine-grained device memory can be had and written (probed in pcr_create; PCRAMP_STAGE=kernel turns it off)
 	typedef PassMail Mail;
 	static constexpr uint32_t MAIL_RING = 8;
-	Mail *mail = nullptr, *mail_dev = nullptr;   // host-mapped ring (slot = seq % MAIL_RING): k_publish writes it, the host spins on seq
+	MappedBuf<Mail> mail;   // host-mapped ring (slot = seq % MAIL_RING): k_publish writes it, the host spins on seq
 	uint32_t mail_seq = 0;
 	// results of the small synchronous calls (move coverage, thermodynamics) come back the same way: a kernel
 	// copies them into a host-mapped buffer and raises a flag the host spins on (no copy-engine packets, no
 	// interrupt wake-up; three pageable hipMemcpyAsync + a stream sync cost ~1.8 ms per call instead)
-	uint8_t *ret_host = nullptr, *ret_dev = nullptr; size_t ret_cap = 0;
-	uint8_t *in_host = nullptr, *in_dev = nullptr; size_t in_cap = 0;   // the way in for small synchronous calls: a mapped buffer the kernel reads directly (the call waits for its results, so one buffer is enough)
-	uint32_t *ret_flag = nullptr, *ret_flag_dev = nullptr; uint32_t ret_seq = 0;
+	MappedBuf<uint8_t> ret;
+	MappedBuf<uint8_t> in;   // the way in for small synchronous calls: a mapped buffer the kernel reads directly (the call waits for its results, so one buffer is enough)
+	MappedBuf<uint32_t> ret_flag; uint32_t ret_seq = 0;
 	// passes enqueued by pcr_screen_device whose counters have not been looked at yet (pcr_synchronize / any
 	// other entry point drains them; a bucket overflow found then replays the passes synchronously)
 	struct Pending {
@@ -830,10 +809,10 @@ struct pcr_ctx {
 	bool timing = false; double t_host[8] = {0, 0, 0, 0, 0, 0, 0, 0}; uint64_t n_timed = 0;
 	// profiling
 	bool prof = false; uint32_t prof_stride = 1, prof_pass = 0;   // events bracket the scan of every prof_stride-th pass
-	std::vector<std::pair<hipEvent_t, hipEvent_t> > prof_events;
+	std::vector<std::pair<Event, Event> > prof_events;
 	double prof_ms = 0.0; uint64_t prof_launches = 0;
 	// the same for the other kernels bench.py prices (PCR_PROF_SW, PCR_PROF_THERMO): every launch while profiling is on
-	std::vector<std::pair<hipEvent_t, hipEvent_t> > prof_events_k[PCR_PROF_KERNELS];
+	std::vector<std::pair<Event, Event> > prof_events_k[PCR_PROF_KERNELS];
 	double prof_ms_k[PCR_PROF_KERNELS] = {0.0, 0.0, 0.0}; uint64_t prof_launches_k[PCR_PROF_KERNELS] = {0, 0, 0};
 };
 
@@ -847,19 +826,18 @@ void free_jobs(pcr_ctx *ctx);
 // HIP events around the launches of a priced kernel (PCR_PROF_*), on the launch stream, while profiling is on.  The pair is
 // handed to the context when the scope ends (also on an error return), so no event is ever left behind.
 struct ProfScope {
-	pcr_ctx *ctx; int k; hipEvent_t e0 = nullptr, e1 = nullptr;
+	pcr_ctx *ctx; int k; Event e0, e1;
 	ProfScope(pcr_ctx *c, int kernel, bool on = true) : ctx(c), k(kernel)
 	{
 		if(!on || !ctx->prof || k < 0 || k >= PCR_PROF_KERNELS) return;
-		if(hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess){ if(e0) (void)hipEventDestroy(e0); e0 = e1 = nullptr; return; }
+		if(e0.create() != hipSuccess || e1.create() != hipSuccess){ e0.release(); return; }
 		(void)hipEventRecord(e0, ctx->stream);
 	}
 	void finish()
 	{
 		if(!e0) return;
 		(void)hipEventRecord(e1, ctx->stream);
-		((k == PCR_PROF_SCAN) ? ctx->prof_events : ctx->prof_events_k[k]).push_back(std::make_pair(e0, e1));
-		e0 = e1 = nullptr;
+		((k == PCR_PROF_SCAN) ? ctx->prof_events : ctx->prof_events_k[k]).emplace_back(std::move(e0), std::move(e1));
 	}
 	~ProfScope() { finish(); }
 };
@@ -973,6 +951,15 @@ int upload_irregular(pcr_ctx *ctx, SeqSet &S)
 	return PCR_OK;
 }
 
+// starts[] = the exclusive prefix sums of counts[0 .. n), and counts[] = a copy of them; sums: one word per 4096 counts
+void launch_exclusive_scan(pcr_ctx *ctx, uint32_t *counts, uint32_t *starts, uint32_t n, uint32_t *sums)
+{
+	const uint32_t n_blocks = (n + 4095u)/4096u;
+	hipLaunchKernelGGL(k_scan_blocks, dim3(n_blocks), dim3(1024), 0, ctx->stream, counts, starts, n, sums);
+	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, sums, n_blocks);
+	hipLaunchKernelGGL(k_scan_add, dim3(n_blocks), dim3(1024), 0, ctx->stream, starts, counts, n, sums);
+}
+
 // The inverse index of the set's irregular words (pcr_scan_seed2.inc), for the state the set is in: counting sort of (word, slot
 // offset) by the 9-gram read there.  ~1 ms for C2's 1.2e6 words; rebuilt after the irregular list changes (load, splits).
 constexpr uint32_t IRX_MAX_RUN = 1024;
@@ -1000,9 +987,7 @@ int ensure_irr_index(pcr_ctx *ctx, SeqSet &S)
 		S.irx_usable = longest <= IRX_MAX_RUN;
 		if(!S.irx_usable){ S.irx_valid = true; return PCR_OK; }
 	}
-	hipLaunchKernelGGL(k_scan_blocks, dim3(n_blocks), dim3(1024), 0, ctx->stream, S.irx_last.p, S.irx_first.p, IRX_KEYS, S.irx_sums.p);
-	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, S.irx_sums.p, n_blocks);
-	hipLaunchKernelGGL(k_scan_add, dim3(n_blocks), dim3(1024), 0, ctx->stream, S.irx_first.p, S.irx_last.p, IRX_KEYS, S.irx_sums.p);   // first = starts; last = a copy, advanced by the scatter to the ends
+	launch_exclusive_scan(ctx, S.irx_last.p, S.irx_first.p, IRX_KEYS, S.irx_sums.p);   // first = starts; last = a copy, advanced by the scatter to the ends
 	HIP_TRY(hipGetLastError());
 	if(S.n_irr){
 		hipLaunchKernelGGL(k_irx_scatter, dim3((S.n_irr + 255)/256), dim3(256), 0, ctx->stream, S.irr.p, S.n_irr, S.irx_last.p, S.irx_words.p);
@@ -1047,9 +1032,7 @@ int ensure_pos_index(pcr_ctx *ctx, SeqSet &S)
 	HIP_TRY(hipMemsetAsync(S.pix_last.p, 0, (size_t)PIX_CODES*sizeof(uint32_t), ctx->stream));
 	const unsigned grid = (unsigned)((S.total_blocks + 255)/256);
 	hipLaunchKernelGGL(k_pix_build<false>, dim3(grid), dim3(256), 0, ctx->stream, S.tb_d(), S.blk_seq.p, S.d_blk_off.p, S.d_len.p, S.total_blocks, S.pix_last.p, (uint4 *)nullptr);
-	hipLaunchKernelGGL(k_scan_blocks, dim3(n_blocks), dim3(1024), 0, ctx->stream, S.pix_last.p, S.pix_first.p, PIX_CODES, S.pix_sums.p);
-	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, S.pix_sums.p, n_blocks);
-	hipLaunchKernelGGL(k_scan_add, dim3(n_blocks), dim3(1024), 0, ctx->stream, S.pix_first.p, S.pix_last.p, PIX_CODES, S.pix_sums.p);
+	launch_exclusive_scan(ctx, S.pix_last.p, S.pix_first.p, PIX_CODES, S.pix_sums.p);
 	hipLaunchKernelGGL(k_pix_build<true>, dim3(grid), dim3(256), 0, ctx->stream, S.tb_d(), S.blk_seq.p, S.d_blk_off.p, S.d_len.p, S.total_blocks, S.pix_last.p, S.pix_ent.p);
 	HIP_TRY(hipGetLastError());
 	{
@@ -1100,17 +1083,7 @@ void fill_oligo_planes(OligoDev &o, const Planes &m, float thr2)
 	o.p2 = (o.stop >= 0) ? pcrhost::planes_nibble(o.m, o.stop) : 0;
 }
 
-void fill_oligo(OligoDev &o, const uint64_t w[2], float thr2)
-{
-	o.m = pcrhost::planes_of_word(w);
-	const unsigned size = (unsigned)pcrhost::planes_size(o.m);
-	o.floor2 = (unsigned)((float)size*thr2);                                     // optimize.cpp:293
-	o.norm = (size > 0) ? (float)(1.0/size) : 0.0f;                              // optimize.cpp:221
-	o.start = pcrhost::planes_start(o.m);
-	o.stop = pcrhost::planes_stop(o.m);
-	o.p1 = (o.stop >= 1) ? pcrhost::planes_nibble(o.m, o.stop - 1) : 0;
-	o.p2 = (o.stop >= 0) ? pcrhost::planes_nibble(o.m, o.stop) : 0;
-}
+void fill_oligo(OligoDev &o, const uint64_t w[2], float thr2) { fill_oligo_planes(o, pcrhost::planes_of_word(w), thr2); }
 
 // Packs small host arrays into a host-mapped pinned buffer; ONE kernel (k_stage) pulls them into the
 // device arena and clears up to two device regions in the same launch -- a copy-engine transfer and a
@@ -1126,51 +1099,62 @@ __global__ void k_stage(const uint4 *__restrict__ src, uint4 *__restrict__ dst, 
 	for(uint32_t k = i;k < n2;k += stride) z2[k] = zero;
 }
 
+// Spins until seen() holds -- a flag in host-mapped memory that a kernel of `stream` raises -- and asks the stream every
+// 16 384 spins whether anything is still running on it.  On SPIN_ERROR, err holds the stream's error.
+enum SpinEnd { SPIN_SEEN, SPIN_IDLE, SPIN_ERROR };
+template<class Seen> inline SpinEnd spin_until(hipStream_t stream, Seen seen, hipError_t &err)
+{
+	for(uint64_t spins = 1;!seen();++spins){
+		__builtin_ia32_pause();
+		if((spins & 0x3FFF) == 0){
+			err = hipStreamQuery(stream);
+			if(err == hipSuccess) return SPIN_IDLE;
+			if(err != hipErrorNotReady) return SPIN_ERROR;
+		}
+	}
+	return SPIN_SEEN;
+}
+
 // Has the pass with mailbox sequence number `seq` published?  Publications happen in stream order and slot
 // seq % MAIL_RING is reused by seq + MAIL_RING, ...: any value of that slot at or beyond seq means yes.
 int wait_published(pcr_ctx *ctx, uint32_t seq)
 {
-	const PassMail *const slot = ctx->mail + (seq % pcr_ctx::MAIL_RING);
-	uint64_t spins = 0;
-	while(true){
+	const PassMail *const slot = ctx->mail.host + (seq % pcr_ctx::MAIL_RING);
+	hipError_t e = hipSuccess;
+	const SpinEnd end = spin_until(ctx->stream, [&]{
 		const uint32_t v = __atomic_load_n((const uint32_t *)&slot->seq, __ATOMIC_ACQUIRE);
-		if(v >= seq && (v - seq) % pcr_ctx::MAIL_RING == 0) return PCR_OK;
-		__builtin_ia32_pause();
-		if((++spins & 0x3FFF) == 0){
-			const hipError_t e = hipStreamQuery(ctx->stream);
-			if(e == hipSuccess) return PCR_OK;                       // stream idle: whatever used the slot is over (the pass may have failed before publishing)
-			if(e != hipErrorNotReady){ g_err = std::string("device pass failed: ") + hipGetErrorString(e); return PCR_ERR_DEVICE; }
-		}
-	}
+		return v >= seq && (v - seq) % pcr_ctx::MAIL_RING == 0; }, e);
+	if(end == SPIN_ERROR){ g_err = std::string("device pass failed: ") + hipGetErrorString(e); return PCR_ERR_DEVICE; }
+	return PCR_OK;                                              // (stream idle: whatever used the slot is over; the pass may have failed before publishing)
 }
 
 struct Stager {
 	pcr_ctx *ctx; size_t used = 0; bool direct = false;
 	explicit Stager(pcr_ctx *c) : ctx(c) {}
-	pcr_ctx::StageSlot *slot = nullptr;
+	pcr_ctx::StageSlot *slot = nullptr; pcr_ctx::DirectSlot *dslot = nullptr;   // the slot of this call, in stage[] or (direct) in dstage[]
+	uint8_t *host = nullptr, *dev = nullptr;                     // the slot's bytes as the CPU and as the kernels address them
 	// direct: the bytes go straight into a slot of device memory (see pcr_ctx::dstage); the caller launches no k_stage for
 	// them and passes the sequence number of ITS pass to seal(): the slot is free again once the NEXT pass has published,
 	// i.e. once every kernel of this one is over.
 	int begin_direct(size_t bytes)
 	{
 		direct = true;
-		slot = &ctx->dstage[ctx->dstage_next];
+		dslot = &ctx->dstage[ctx->dstage_next];
 		ctx->dstage_next = (ctx->dstage_next + 1) % pcr_ctx::STAGE_RING;
-		if(slot->guard_seq){ const int grc = wait_published(ctx, slot->guard_seq); if(grc != PCR_OK) return grc; slot->guard_seq = 0; }
-		if(bytes + 256 > slot->cap){
-			if(slot->dev){ HIP_TRY(hipStreamSynchronize(ctx->stream)); (void)hipFree(slot->dev); slot->dev = slot->host = nullptr; slot->cap = 0; }
-			const size_t want = std::max<size_t>((bytes + 256)*2, 1 << 17);
-			HIP_TRY(hipExtMallocWithFlags((void **)&slot->dev, want, hipDeviceMallocFinegrained));
-			slot->host = slot->dev;                                  // one address for the CPU's stores and the kernels' loads
-			slot->cap = want;
+		if(dslot->guard_seq){ const int grc = wait_published(ctx, dslot->guard_seq); if(grc != PCR_OK) return grc; dslot->guard_seq = 0; }
+		if(bytes + 256 > dslot->buf.cap){
+			if(dslot->buf.p) HIP_TRY(hipStreamSynchronize(ctx->stream));
+			const int rc = dslot->buf.ensure(std::max<size_t>((bytes + 256)*2, 1 << 17));
+			if(rc != PCR_OK) return rc;
 		}
+		host = dev = dslot->buf.p;                                  // one address for the CPU's stores and the kernels' loads
 		used = 0;
 		return PCR_OK;
 	}
 	void seal(uint32_t pass_seq)
 	{
 		__builtin_ia32_sfence();                                     // the write-combined stores leave the core before the doorbell is rung
-		slot->guard_seq = pass_seq + 1;
+		dslot->guard_seq = pass_seq + 1;
 	}
 	int begin(size_t bytes)
 	{
@@ -1178,15 +1162,11 @@ struct Stager {
 		ctx->stage_next = (ctx->stage_next + 1) % pcr_ctx::STAGE_RING;
 		if(slot->busy){ HIP_TRY(hipEventSynchronize(slot->done)); slot->busy = false; }
 		if(slot->guard_seq){ const int grc = wait_published(ctx, slot->guard_seq); if(grc != PCR_OK) return grc; slot->guard_seq = 0; }
-		if(bytes > slot->cap){
-			if(slot->host){ (void)hipHostFree(slot->host); slot->host = nullptr; slot->cap = 0; }
-			const size_t want = std::max<size_t>(bytes*2, 1 << 16);
-			HIP_TRY(hipHostMalloc((void **)&slot->host, want, hipHostMallocMapped | hipHostMallocCoherent));
-			HIP_TRY(hipHostGetDevicePointer((void **)&slot->dev, slot->host, 0));
-			slot->cap = want;
-		}
-		if(!slot->done) HIP_TRY(hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
-		int rc = ctx->arena.ensure(bytes + 256);
+		int rc = slot->buf.ensure(bytes, std::max<size_t>(bytes*2, 1 << 16));
+		if(rc != PCR_OK) return rc;
+		host = slot->buf.host; dev = slot->buf.dev;
+		if(!slot->done) HIP_TRY(slot->done.create(hipEventDisableTiming));
+		rc = ctx->arena.ensure(bytes + 256);
 		used = 0;
 		return rc;
 	}
@@ -1194,10 +1174,10 @@ struct Stager {
 	template<class T> T *put(const T *src, size_t n)
 	{
 		used = (used + 15) & ~size_t(15);
-		memcpy(slot->host + used, src, n*sizeof(T));
-		T *dev = (T *)((direct ? slot->dev : ctx->arena.p) + used);
+		memcpy(host + used, src, n*sizeof(T));
+		T *at = (T *)((direct ? dev : ctx->arena.p) + used);
 		used += n*sizeof(T);
-		return dev;
+		return at;
 	}
 	// z0/z1: device regions to clear in the same launch (16-byte aligned, sizes rounded UP to 16 bytes: the
 	// caller's buffers must be allocated with that slack)
@@ -1207,7 +1187,7 @@ struct Stager {
 		const uint32_t most = std::max(std::max(n16, n2), std::max(n0, n1));
 		if(most){
 			const unsigned grid = std::min<unsigned>((most + 255)/256, 512u);
-			hipLaunchKernelGGL(k_stage, dim3(grid), dim3(256), 0, ctx->stream, (const uint4 *)slot->dev, (uint4 *)ctx->arena.p, n16,
+			hipLaunchKernelGGL(k_stage, dim3(grid), dim3(256), 0, ctx->stream, (const uint4 *)dev, (uint4 *)ctx->arena.p, n16,
 				(uint4 *)z0, n0, (uint4 *)z1, n1, (uint4 *)z2, n2);
 			HIP_TRY(hipGetLastError());
 		}
@@ -1234,19 +1214,12 @@ __global__ void k_publish(const uint32_t *__restrict__ counters, pcr_ctx::Mail *
 
 int mail_wait(pcr_ctx *ctx, uint32_t seq, uint32_t out[4])
 {
-	uint64_t spins = 0;
-	pcr_ctx::Mail *const slot = ctx->mail + (seq % pcr_ctx::MAIL_RING);
-	while(__atomic_load_n((const uint32_t *)&slot->seq, __ATOMIC_ACQUIRE) != seq){
-		__builtin_ia32_pause();
-		if((++spins & 0x3FFF) == 0){
-			const hipError_t e = hipStreamQuery(ctx->stream);
-			if(e == hipSuccess){                          // everything drained: the flag must be there now
-				if(__atomic_load_n((const uint32_t *)&slot->seq, __ATOMIC_ACQUIRE) == seq) break;
-				g_err = "device pass finished without publishing its counters"; return PCR_ERR_DEVICE;
-			}
-			if(e != hipErrorNotReady){ g_err = std::string("device pass failed: ") + hipGetErrorString(e); return PCR_ERR_DEVICE; }
-		}
-	}
+	pcr_ctx::Mail *const slot = ctx->mail.host + (seq % pcr_ctx::MAIL_RING);
+	auto seen = [&]{ return __atomic_load_n((const uint32_t *)&slot->seq, __ATOMIC_ACQUIRE) == seq; };
+	hipError_t e = hipSuccess;
+	const SpinEnd end = spin_until(ctx->stream, seen, e);
+	if(end == SPIN_ERROR){ g_err = std::string("device pass failed: ") + hipGetErrorString(e); return PCR_ERR_DEVICE; }
+	if(end == SPIN_IDLE && !seen()){ g_err = "device pass finished without publishing its counters"; return PCR_ERR_DEVICE; }   // everything drained: the flag must be there now
 	for(int i = 0;i < 4;++i) out[i] = slot->counters[i];
 	return PCR_OK;
 }
@@ -1273,41 +1246,30 @@ int return_to_host(pcr_ctx *ctx, const void *s0, size_t b0, const void *s1, size
 {
 	const uint32_t n0 = (uint32_t)((b0 + 15)/16), n1 = (uint32_t)((b1 + 15)/16), n2 = (uint32_t)((b2 + 15)/16);
 	const size_t need = ((size_t)n0 + n1 + n2)*16;
-	if(!ctx->ret_flag){
-		HIP_TRY(hipHostMalloc((void **)&ctx->ret_flag, 64, hipHostMallocMapped | hipHostMallocCoherent));
-		HIP_TRY(hipHostGetDevicePointer((void **)&ctx->ret_flag_dev, ctx->ret_flag, 0));
-		*ctx->ret_flag = 0;
+	int rc;
+	if(!ctx->ret_flag.host){
+		if((rc = ctx->ret_flag.ensure(64)) != PCR_OK) return rc;
+		*ctx->ret_flag.host = 0;
 	}
-	if(need > ctx->ret_cap){
+	if(need > ctx->ret.cap){
 		HIP_TRY(hipStreamSynchronize(ctx->stream));
-		if(ctx->ret_host){ (void)hipHostFree(ctx->ret_host); ctx->ret_host = nullptr; ctx->ret_cap = 0; }
-		const size_t want = std::max<size_t>(need*2, 1 << 20);
-		HIP_TRY(hipHostMalloc((void **)&ctx->ret_host, want, hipHostMallocMapped | hipHostMallocCoherent));
-		HIP_TRY(hipHostGetDevicePointer((void **)&ctx->ret_dev, ctx->ret_host, 0));
-		ctx->ret_cap = want;
+		if((rc = ctx->ret.ensure(need, std::max<size_t>(need*2, 1 << 20))) != PCR_OK) return rc;
 	}
 	const uint32_t most = std::max(n0, std::max(n1, n2));
 	if(most){
 		const unsigned grid = std::min<unsigned>((most + 255)/256, 1024u);
-		hipLaunchKernelGGL(k_return, dim3(grid), dim3(256), 0, ctx->stream, (const uint4 *)s0, n0, (const uint4 *)s1, n1, (const uint4 *)s2, n2, (uint4 *)ctx->ret_dev);
+		hipLaunchKernelGGL(k_return, dim3(grid), dim3(256), 0, ctx->stream, (const uint4 *)s0, n0, (const uint4 *)s1, n1, (const uint4 *)s2, n2, (uint4 *)ctx->ret.dev);
 		HIP_TRY(hipGetLastError());
 	}
 	const uint32_t seq = ++ctx->ret_seq;
-	hipLaunchKernelGGL(k_return_flag, dim3(1), dim3(1), 0, ctx->stream, ctx->ret_flag_dev, seq);
+	hipLaunchKernelGGL(k_return_flag, dim3(1), dim3(1), 0, ctx->stream, ctx->ret_flag.dev, seq);
 	HIP_TRY(hipGetLastError());
-	uint64_t spins = 0;
-	while(__atomic_load_n((const uint32_t *)ctx->ret_flag, __ATOMIC_ACQUIRE) != seq){
-		__builtin_ia32_pause();
-		if((++spins & 0x3FFF) == 0){
-			const hipError_t e = hipStreamQuery(ctx->stream);
-			if(e == hipSuccess){
-				if(__atomic_load_n((const uint32_t *)ctx->ret_flag, __ATOMIC_ACQUIRE) == seq) break;
-				g_err = "device work finished without raising the return flag"; return PCR_ERR_DEVICE;
-			}
-			if(e != hipErrorNotReady){ g_err = std::string("device work failed: ") + hipGetErrorString(e); return PCR_ERR_DEVICE; }
-		}
-	}
-	out[0] = ctx->ret_host; out[1] = ctx->ret_host + (size_t)n0*16; out[2] = ctx->ret_host + ((size_t)n0 + n1)*16;
+	auto seen = [&]{ return __atomic_load_n((const uint32_t *)ctx->ret_flag.host, __ATOMIC_ACQUIRE) == seq; };
+	hipError_t e = hipSuccess;
+	const SpinEnd end = spin_until(ctx->stream, seen, e);
+	if(end == SPIN_ERROR){ g_err = std::string("device work failed: ") + hipGetErrorString(e); return PCR_ERR_DEVICE; }
+	if(end == SPIN_IDLE && !seen()){ g_err = "device work finished without raising the return flag"; return PCR_ERR_DEVICE; }
+	out[0] = ctx->ret.host; out[1] = ctx->ret.host + (size_t)n0*16; out[2] = ctx->ret.host + ((size_t)n0 + n1)*16;
 	return PCR_OK;
 }
 
@@ -1315,16 +1277,13 @@ int return_to_host(pcr_ctx *ctx, const void *s0, size_t b0, const void *s1, size
 // hipMemcpyAsync costs ~20 us).  Valid until the next call; the caller waits for its results before returning.
 int mapped_input(pcr_ctx *ctx, const void *src, size_t bytes, const void **dev_out)
 {
-	if(bytes > ctx->in_cap){
+	if(bytes > ctx->in.cap){
 		HIP_TRY(hipStreamSynchronize(ctx->stream));
-		if(ctx->in_host){ (void)hipHostFree(ctx->in_host); ctx->in_host = nullptr; ctx->in_cap = 0; }
-		const size_t want = std::max<size_t>(bytes*2, 1 << 18);
-		HIP_TRY(hipHostMalloc((void **)&ctx->in_host, want, hipHostMallocMapped | hipHostMallocCoherent));
-		HIP_TRY(hipHostGetDevicePointer((void **)&ctx->in_dev, ctx->in_host, 0));
-		ctx->in_cap = want;
+		const int rc = ctx->in.ensure(bytes, std::max<size_t>(bytes*2, 1 << 18));
+		if(rc != PCR_OK) return rc;
 	}
-	memcpy(ctx->in_host, src, bytes);
-	*dev_out = ctx->in_dev;
+	memcpy(ctx->in.host, src, bytes);
+	*dev_out = ctx->in.dev;
 	return PCR_OK;
 }
 
@@ -1407,7 +1366,7 @@ int amplify_launch(pcr_ctx *ctx, SeqSet &S, const pcr_pair *pairs, uint32_t n_pa
 	// k_match also clears the status word (it runs before k_pair in stream order)
 	hipLaunchKernelGGL(k_match, dim3(std::max(mgrid, 1u)), dim3(64*MATCH_WAVES), 0, ctx->stream, S.db.p, n_t, n_dev, S.db_cap,
 		S.touched.p, S.d_seg_hi, ctx->d_oligos, 2*n_pairs, mask_words, ctx->mask.p, ctx->status.p,
-		prestaged ? fa->pub_counters : (const uint32_t *)nullptr, prestaged ? ctx->mail_dev + (fa->pub_seq % pcr_ctx::MAIL_RING) : (pcr_ctx::Mail *)nullptr,
+		prestaged ? fa->pub_counters : (const uint32_t *)nullptr, prestaged ? ctx->mail.dev + (fa->pub_seq % pcr_ctx::MAIL_RING) : (pcr_ctx::Mail *)nullptr,
 		prestaged ? fa->pub_seq : 0u);
 	HIP_TRY(hipGetLastError());
 	hipLaunchKernelGGL(k_pair, dim3(grid), dim3(threads), 0, ctx->stream, S.db.p, n_db, n_dev, S.db_cap, S.touched.p, S.d_seg_hi, ctx->mask.p,
@@ -1498,11 +1457,8 @@ pcr_ctx *pcr_create(int device, void *hip_stream, const pcr_params *params)
 	}
 	pcr_ctx *ctx = new pcr_ctx();
 	ctx->device = device;
-	if(hip_stream){ ctx->stream = (hipStream_t)hip_stream; ctx->own_stream = false; }
-	else{
-		if(hipStreamCreate(&ctx->stream) != hipSuccess){ g_err = "pcr_create: hipStreamCreate failed"; delete ctx; return nullptr; }
-		ctx->own_stream = true;
-	}
+	if(hip_stream) ctx->stream.borrow((hipStream_t)hip_stream);
+	else if(ctx->stream.create() != hipSuccess){ g_err = "pcr_create: hipStreamCreate failed"; delete ctx; return nullptr; }
 	if(params){ ctx->params = *params; }
 	else{ ctx->params.pack_max_degen = 256; ctx->params.pack_min_gc = 0.0f; ctx->params.pack_max_gc = 1.0f; }
 	{ hipDeviceProp_t prop; if(hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ctx->n_cu = (uint32_t)prop.multiProcessorCount; }
@@ -1524,27 +1480,23 @@ pcr_ctx *pcr_create(int device, void *hip_stream, const pcr_params *params)
 		// pattern stored by the CPU, fenced, must come back through a kernel that copies it into mapped host memory.
 		const char *v = getenv("PCRAMP_STAGE");
 		if(!(v && v[0] == 'k') && prop.isLargeBar){
-			void *probe = nullptr; uint32_t *back = nullptr, *back_dev = nullptr;
+			DevBuf<uint32_t> probe(true); MappedBuf<uint32_t> back; const std::string err_before = g_err;
 			constexpr uint32_t PROBE_WORDS = 1024;
-			if(hipExtMallocWithFlags(&probe, PROBE_WORDS*sizeof(uint32_t), hipDeviceMallocFinegrained) == hipSuccess && probe &&
-			   hipHostMalloc((void **)&back, PROBE_WORDS*sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess && back &&
-			   hipHostGetDevicePointer((void **)&back_dev, back, 0) == hipSuccess){
+			if(probe.ensure(PROBE_WORDS) == PCR_OK && back.ensure(PROBE_WORDS*sizeof(uint32_t)) == PCR_OK){
 				hipPointerAttribute_t at;
-				bool ok = hipPointerGetAttributes(&at, probe) == hipSuccess;
+				bool ok = hipPointerGetAttributes(&at, probe.p) == hipSuccess;
 				for(int round = 0;ok && round < 2;++round){
-					volatile uint32_t *w = (volatile uint32_t *)probe;
-					for(uint32_t i = 0;i < PROBE_WORDS;++i){ w[i] = 0x9E3779B9u*(i + 1) + (uint32_t)round; back[i] = 0; }
+					volatile uint32_t *w = (volatile uint32_t *)probe.p;
+					for(uint32_t i = 0;i < PROBE_WORDS;++i){ w[i] = 0x9E3779B9u*(i + 1) + (uint32_t)round; back.host[i] = 0; }
 					__builtin_ia32_sfence();
-					hipLaunchKernelGGL(k_stage, dim3(1), dim3(256), 0, ctx->stream, (const uint4 *)probe, (uint4 *)back_dev, PROBE_WORDS/4,
+					hipLaunchKernelGGL(k_stage, dim3(1), dim3(256), 0, ctx->stream, (const uint4 *)probe.p, (uint4 *)back.dev, PROBE_WORDS/4,
 						(uint4 *)nullptr, 0u, (uint4 *)nullptr, 0u, (uint4 *)nullptr, 0u);
 					ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
-					for(uint32_t i = 0;ok && i < PROBE_WORDS;++i) ok = back[i] == 0x9E3779B9u*(i + 1) + (uint32_t)round;
+					for(uint32_t i = 0;ok && i < PROBE_WORDS;++i) ok = back.host[i] == 0x9E3779B9u*(i + 1) + (uint32_t)round;
 				}
 				ctx->direct_ok = ok;
 			}
-			else (void)hipGetLastError();
-			if(probe) (void)hipFree(probe);
-			if(back) (void)hipHostFree(back);
+			else{ (void)hipGetLastError(); g_err = err_before; }    // (no large-BAR staging: not an error of pcr_create)
 		}
 	}
 	ctx->filt.max_degen = ctx->params.pack_max_degen;
@@ -1561,11 +1513,8 @@ pcr_ctx *pcr_create(int device, void *hip_stream, const pcr_params *params)
 	   hipMemcpyToSymbol(HIP_SYMBOL(thermo::c_wc), PCR_WC, sizeof(PCR_WC)) != hipSuccess){
 		g_err = "pcr_create: hipMemcpyToSymbol failed"; delete ctx; return nullptr;
 	}
-	if(hipHostMalloc((void **)&ctx->mail, sizeof(pcr_ctx::Mail)*pcr_ctx::MAIL_RING, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-	   hipHostGetDevicePointer((void **)&ctx->mail_dev, ctx->mail, 0) != hipSuccess){
-		g_err = "pcr_create: mapped host allocation failed"; if(ctx->mail) (void)hipHostFree(ctx->mail); delete ctx; return nullptr;
-	}
-	memset((void *)ctx->mail, 0, sizeof(pcr_ctx::Mail)*pcr_ctx::MAIL_RING);
+	if(ctx->mail.ensure(sizeof(pcr_ctx::Mail)*pcr_ctx::MAIL_RING) != PCR_OK){ g_err = "pcr_create: mapped host allocation failed"; delete ctx; return nullptr; }
+	memset((void *)ctx->mail.host, 0, sizeof(pcr_ctx::Mail)*pcr_ctx::MAIL_RING);
 	return ctx;
 }
 
@@ -1575,7 +1524,8 @@ void pcr_destroy(pcr_ctx *ctx)
 	(void)hipSetDevice(ctx->device);
 	(void)flush_launcher(ctx);                    // queued passes are launched (or dropped after a failed one) before anything is freed
 	detach_launcher(ctx);                         // the stream's last handle stops and joins the launcher thread
-	(void)hipStreamSynchronize(ctx->stream);
+	(void)hipStreamSynchronize(ctx->stream);      // nothing may be in flight when the owners free (pcr_owned.hpp): synchronise, then delete
+	if(ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
 	ctx->pending.clear();
 	free_jobs(ctx);
 	if(ctx->timing && ctx->n_timed){
@@ -1586,26 +1536,6 @@ void pcr_destroy(pcr_ctx *ctx)
 		fprintf(stderr, "[pcramp] host us/pass: plan %.1f  stage %.1f  launch %.1f  wait %.1f | amplify prep %.1f  launch %.1f  (%llu passes)\n",
 			ctx->t_host[0]/n, ctx->t_host[1]/n, ctx->t_host[2]/n, ctx->t_host[3]/n, ctx->t_host[4]/n, ctx->t_host[5]/n, (unsigned long long)ctx->n_timed);
 	}
-	for(auto &pr : ctx->prof_events){ (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-	for(int k = 0;k < PCR_PROF_KERNELS;++k){ for(auto &pr : ctx->prof_events_k[k]){ (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); } }
-	for(int s = 0;s < PCR_N_SETS;++s) ctx->sets[s].release();
-	ctx->best.release();
-	ctx->counters.release(); ctx->mask.release(); ctx->status.release(); ctx->hits.release();
-	ctx->s1_image.release(); ctx->s1_heads.release(); ctx->s1_multi.release(); ctx->s1_part.release();
-	ctx->bits_fr.release(); ctx->bits_rf.release(); ctx->arena.release(); ctx->fin_scratch.release();
-	for(auto &sl : ctx->stage){ if(sl.host) (void)hipHostFree(sl.host); if(sl.done) (void)hipEventDestroy(sl.done); }
-	for(auto &sl : ctx->dstage){ if(sl.dev) (void)hipFree(sl.dev); }
-	if(ctx->mail) (void)hipHostFree(ctx->mail);
-	if(ctx->ret_host) (void)hipHostFree(ctx->ret_host);
-	if(ctx->in_host) (void)hipHostFree(ctx->in_host);
-	if(ctx->ret_flag) (void)hipHostFree(ctx->ret_flag);
-	if(ctx->sw_pin) (void)hipHostFree(ctx->sw_pin);
-	for(int k = 0;k < 2;++k){ if(ctx->sw_done[k]) (void)hipEventDestroy(ctx->sw_done[k]); }
-	ctx->oligos.release(); ctx->sw_jobs.release(); ctx->sw_out.release(); ctx->sw_q.release(); ctx->sw_qlen.release(); ctx->sw_t.release(); ctx->entry_codes.release(); ctx->entry_lens.release(); ctx->amp_recs.release(); ctx->amp_recs2.release(); ctx->amp_keys.release(); ctx->amp_pkeys.release(); ctx->amp_pair_start.release(); ctx->sort_tmp.release(); ctx->bg_pairs.release(); ctx->th_jobs.release(); ctx->th_out.release(); ctx->th_dg.release(); ctx->th_dbg.release(); ctx->split_where.release(); ctx->th_map.release(); ctx->th_bad.release(); ctx->mx_keys.release(); ctx->mx_count.release(); ctx->mx_amp.release(); ctx->opt_oligos.release(); ctx->opt_jobs.release(); ctx->opt_cov.release(); ctx->opt_loc.release(); ctx->opt_tasks.release();
-	ctx->pool_in.release(); ctx->pool_tmp.release(); ctx->pool_cnt.release(); ctx->pool_ord.release(); ctx->pool_eoff.release(); ctx->pool_ioff.release(); ctx->pool_keys.release(); ctx->pool_items.release(); ctx->pool_rec.release();
-	ctx->site_in.release(); ctx->site_tmp.release(); ctx->site_cnt.release(); ctx->site_ord.release(); ctx->site_flag.release(); ctx->site_eoff.release(); ctx->site_joff.release(); ctx->site_keys.release(); ctx->site_items.release(); ctx->site_res.release(); ctx->site_rec.release();
-	if(ctx->aux_stream){ (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
-	if(ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
 	delete ctx;
 }
 
@@ -1619,6 +1549,13 @@ int pcr_launcher_stats(pcr_ctx *ctx, uint64_t *passes_pipelined, uint32_t *max_q
 	if(!ctx){ g_err = "null ctx"; return PCR_ERR_ARG; }
 	if(passes_pipelined) *passes_pipelined = ctx->n_pipelined;
 	if(max_queue_depth) *max_queue_depth = ctx->lq_client.max_depth;
+	return PCR_OK;
+}
+
+int pcr_live_resources(uint64_t out[4])
+{
+	if(!out){ g_err = "pcr_live_resources: bad argument"; return PCR_ERR_ARG; }
+	for(int k = 0;k < 4;++k) out[k] = pcrown::g_live[k].load();
 	return PCR_OK;
 }
 
@@ -1716,24 +1653,23 @@ static int load_sequences_impl(pcr_ctx *ctx, int which, const uint8_t *packed4, 
 	int rc;
 	DevBuf<uint8_t> d_packed; DevBuf<uint64_t> d_byte_off;
 	if((rc = d_packed.ensure(total_bytes)) != PCR_OK) return rc;
-	if((rc = d_byte_off.ensure(n)) != PCR_OK){ d_packed.release(); return rc; }
-	auto fail = [&](int code){ d_packed.release(); d_byte_off.release(); return code; };
-	if((rc = S.planes.ensure(total_blocks)) != PCR_OK) return fail(rc);
-	if((rc = S.valid.ensure(S2_VALID_FRONT + total_blocks + S2_TAIL_BLOCKS)) != PCR_OK) return fail(rc);
-	if((rc = S.nib.ensure(total_blocks*4 + 8)) != PCR_OK) return fail(rc);
-	if((rc = S.tb.ensure(S2_TB_FRONT + (total_blocks + S2_TAIL_BLOCKS)*2 + 8)) != PCR_OK) return fail(rc);
-	if((rc = S.tile_degen.ensure(n_tiles + 1)) != PCR_OK) return fail(rc);
-	if((rc = S.degen_tiles.ensure(n_tiles + 1)) != PCR_OK) return fail(rc);
-	if((rc = S.blk_seq.ensure(total_blocks)) != PCR_OK) return fail(rc);
-	if((rc = S.tile_seq.ensure(n_tiles)) != PCR_OK) return fail(rc);
-	if((rc = S.tile_pos0.ensure(n_tiles)) != PCR_OK) return fail(rc);
-	if((rc = S.d_len.ensure(n)) != PCR_OK) return fail(rc);
-	if((rc = S.d_blk_off.ensure(n + 1)) != PCR_OK) return fail(rc);
-	if((rc = S.d_nblk_real.ensure(n)) != PCR_OK) return fail(rc);
-	if((rc = S.d_active.ensure(n)) != PCR_OK) return fail(rc);
-	if((rc = S.d_has_eos.ensure(n)) != PCR_OK) return fail(rc);
+	if((rc = d_byte_off.ensure(n)) != PCR_OK) return rc;
+	if((rc = S.planes.ensure(total_blocks)) != PCR_OK) return rc;
+	if((rc = S.valid.ensure(S2_VALID_FRONT + total_blocks + S2_TAIL_BLOCKS)) != PCR_OK) return rc;
+	if((rc = S.nib.ensure(total_blocks*4 + 8)) != PCR_OK) return rc;
+	if((rc = S.tb.ensure(S2_TB_FRONT + (total_blocks + S2_TAIL_BLOCKS)*2 + 8)) != PCR_OK) return rc;
+	if((rc = S.tile_degen.ensure(n_tiles + 1)) != PCR_OK) return rc;
+	if((rc = S.degen_tiles.ensure(n_tiles + 1)) != PCR_OK) return rc;
+	if((rc = S.blk_seq.ensure(total_blocks)) != PCR_OK) return rc;
+	if((rc = S.tile_seq.ensure(n_tiles)) != PCR_OK) return rc;
+	if((rc = S.tile_pos0.ensure(n_tiles)) != PCR_OK) return rc;
+	if((rc = S.d_len.ensure(n)) != PCR_OK) return rc;
+	if((rc = S.d_blk_off.ensure(n + 1)) != PCR_OK) return rc;
+	if((rc = S.d_nblk_real.ensure(n)) != PCR_OK) return rc;
+	if((rc = S.d_active.ensure(n)) != PCR_OK) return rc;
+	if((rc = S.d_has_eos.ensure(n)) != PCR_OK) return rc;
 #define H2D(dst, src, bytes) do{ if((bytes) > 0){ hipError_t e_ = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); \
-	if(e_ != hipSuccess){ g_err = std::string("hipMemcpy: ") + hipGetErrorString(e_); return fail(PCR_ERR_DEVICE); } } }while(0)
+	if(e_ != hipSuccess){ g_err = std::string("hipMemcpy: ") + hipGetErrorString(e_); return PCR_ERR_DEVICE; } } }while(0)
 	{   // one transfer for all sequences (a copy per sequence was 10 000 copy-engine packets at C2)
 		std::vector<uint8_t> flat(total_bytes);
 		for(uint32_t s = 0;s < n;++s){ if(!S.packed[s].empty()) memcpy(flat.data() + dev_byte_off[s], S.packed[s].data(), S.packed[s].size()); }
@@ -1754,37 +1690,37 @@ static int load_sequences_impl(pcr_ctx *ctx, int which, const uint8_t *packed4, 
 		if(e_ == hipSuccess) e_ = hipMemsetAsync(S.valid_d() + total_blocks, 0, S2_TAIL_BLOCKS*sizeof(uint32_t), ctx->stream);
 		if(e_ == hipSuccess) e_ = hipMemsetAsync(S.tb.p, 0, S2_TB_FRONT*sizeof(uint32_t), ctx->stream);
 		if(e_ == hipSuccess) e_ = hipMemsetAsync(S.tb_d() + total_blocks*2, 0, (S2_TAIL_BLOCKS*2 + 8)*sizeof(uint32_t), ctx->stream);
-		if(e_ != hipSuccess){ g_err = std::string("load: padding memset: ") + hipGetErrorString(e_); return fail(PCR_ERR_DEVICE); }
+		if(e_ != hipSuccess){ g_err = std::string("load: padding memset: ") + hipGetErrorString(e_); return PCR_ERR_DEVICE; }
 	}
 	if(total_blocks){
 		const unsigned threads = 256;
 		const unsigned grid = (unsigned)((total_blocks + threads - 1)/threads);
 		hipLaunchKernelGGL(k_transpose, dim3(grid), dim3(threads), 0, ctx->stream, d_packed.p, d_byte_off.p, S.d_len.p,
 			S.d_blk_off.p, S.blk_seq.p, S.planes.p, S.nib.p, S.tb_d(), total_blocks);
-		if(hipGetLastError() != hipSuccess){ g_err = "k_transpose launch failed"; return fail(PCR_ERR_DEVICE); }
-		if((rc = run_valid(ctx, S, 0, total_blocks)) != PCR_OK) return fail(rc);
+		if(hipGetLastError() != hipSuccess){ g_err = "k_transpose launch failed"; return PCR_ERR_DEVICE; }
+		if((rc = run_valid(ctx, S, 0, total_blocks)) != PCR_OK) return rc;
 	}
 	S.bucket_cap = 64;               // grown by earlier passes over other data: start small again
 	S.n_degen_tiles = 0;
 	if(n_tiles){
 		hipLaunchKernelGGL(k_tile_degen, dim3((unsigned)((n_tiles + 255)/256)), dim3(256), 0, ctx->stream, S.planes.p, S.d_blk_off.p,
 			S.d_nblk_real.p, S.tile_seq.p, S.tile_pos0.p, (uint32_t)n_tiles, S.tile_degen.p);
-		if(hipGetLastError() != hipSuccess){ g_err = "k_tile_degen launch failed"; return fail(PCR_ERR_DEVICE); }
+		if(hipGetLastError() != hipSuccess){ g_err = "k_tile_degen launch failed"; return PCR_ERR_DEVICE; }
 	}
-	if(total_blocks >= (uint64_t(1) << 40)){ g_err = "pcr_load_sequences: more than 2^40 blocks"; return fail(PCR_ERR_CAPACITY); }
-	if((rc = build_tile_desc(ctx, S)) != PCR_OK) return fail(rc);
-	if(hipStreamSynchronize(ctx->stream) != hipSuccess){ g_err = "load: stream sync failed"; return fail(PCR_ERR_DEVICE); }
+	if(total_blocks >= (uint64_t(1) << 40)){ g_err = "pcr_load_sequences: more than 2^40 blocks"; return PCR_ERR_CAPACITY; }
+	if((rc = build_tile_desc(ctx, S)) != PCR_OK) return rc;
+	if(hipStreamSynchronize(ctx->stream) != hipSuccess){ g_err = "load: stream sync failed"; return PCR_ERR_DEVICE; }
 	if(n_tiles){
 		std::vector<uint8_t> flags(n_tiles);
 		std::vector<uint32_t> list;
-		if(hipMemcpy(flags.data(), S.tile_degen.p, n_tiles, hipMemcpyDeviceToHost) != hipSuccess){ g_err = "load: flag download failed"; return fail(PCR_ERR_DEVICE); }
+		if(hipMemcpy(flags.data(), S.tile_degen.p, n_tiles, hipMemcpyDeviceToHost) != hipSuccess){ g_err = "load: flag download failed"; return PCR_ERR_DEVICE; }
 		for(uint64_t t2 = 0;t2 < n_tiles;++t2){ if(flags[t2]) list.push_back((uint32_t)t2); }
 		S.n_degen_tiles = (uint32_t)list.size();
 		if(!list.empty() && hipMemcpy(S.degen_tiles.p, list.data(), list.size()*sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess){
-			g_err = "load: tile list upload failed"; return fail(PCR_ERR_DEVICE);
+			g_err = "load: tile list upload failed"; return PCR_ERR_DEVICE;
 		}
 	}
-	d_packed.release(); d_byte_off.release();
+	d_packed.release(); d_byte_off.release();     // (before the irregular lists are allocated: the packed copy is as large as the set)
 	return upload_irregular(ctx, S);
 }
 
@@ -2057,7 +1993,6 @@ int pcr_profile_read(pcr_ctx *ctx, double *scan_ms, uint64_t *scan_launches, int
 		float ms = 0.0f;
 		HIP_TRY(hipEventElapsedTime(&ms, pr.first, pr.second));
 		ctx->prof_ms += ms; ctx->prof_launches += 1;
-		(void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second);
 	}
 	ctx->prof_events.clear();
 	if(scan_ms) *scan_ms = ctx->prof_ms;
@@ -2076,7 +2011,6 @@ int pcr_profile_read_kernel(pcr_ctx *ctx, int kernel, double *ms, uint64_t *laun
 		float t = 0.0f;
 		HIP_TRY(hipEventElapsedTime(&t, pr.first, pr.second));
 		ctx->prof_ms_k[kernel] += t; ctx->prof_launches_k[kernel] += 1;
-		(void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second);
 	}
 	ctx->prof_events_k[kernel].clear();
 	if(ms) *ms = ctx->prof_ms_k[kernel];

@@ -112,14 +112,11 @@ int pcr_sw_align_words(pcr_ctx *ctx, const pcr_word128 *queries, const pcr_word1
 	// host-mapped chunk buffers: while the GPU aligns chunk k the host copies chunk k + 1 in and chunk k - 1 out, so
 	// the call lasts about as long as the slower of the two (host copies ~ PCIe + kernel), not their sum.
 	const uint32_t CH = 1u << 16;                                                  // lanes per chunk: 2 MB of words, 1 MB of results
-	if(!ctx->sw_pin){
-		HIP_TRY(hipHostMalloc((void **)&ctx->sw_pin, 2*(size_t)CH*(2*sizeof(pcr_word128) + sizeof(SwOut)), hipHostMallocMapped | hipHostMallocCoherent));
-		HIP_TRY(hipHostGetDevicePointer((void **)&ctx->sw_pin_dev, ctx->sw_pin, 0));
-		for(int k = 0;k < 2;++k) HIP_TRY(hipEventCreateWithFlags(&ctx->sw_done[k], hipEventDisableTiming));
-	}
+	{ const int rc = ctx->sw_pin.ensure(2*(size_t)CH*(2*sizeof(pcr_word128) + sizeof(SwOut))); if(rc != PCR_OK) return rc; }
+	for(int k = 0;k < 2;++k){ if(!ctx->sw_done[k]) HIP_TRY(ctx->sw_done[k].create(hipEventDisableTiming)); }
 	const size_t slot_bytes = (size_t)CH*(2*sizeof(pcr_word128) + sizeof(SwOut));
 	const uint32_t n_chunks = (n + CH - 1)/CH;
-	auto host_q = [&](uint32_t k){ return (pcr_word128 *)(ctx->sw_pin + (k & 1u)*slot_bytes); };
+	auto host_q = [&](uint32_t k){ return (pcr_word128 *)(ctx->sw_pin.host + (k & 1u)*slot_bytes); };
 	auto copy_out = [&](uint32_t c) -> int {
 		HIP_TRY(hipEventSynchronize(ctx->sw_done[c & 1u]));
 		const uint32_t lo = c*CH, cnt = std::min(CH, n - lo);
@@ -133,7 +130,7 @@ int pcr_sw_align_words(pcr_ctx *ctx, const pcr_word128 *queries, const pcr_word1
 		pcr_word128 *hq = host_q(c), *ht = hq + CH;
 		memcpy(hq, queries + lo, (size_t)cnt*sizeof(pcr_word128));
 		memcpy(ht, templates + lo, (size_t)cnt*sizeof(pcr_word128));
-		const uint8_t *dev = ctx->sw_pin_dev + (c & 1u)*slot_bytes;
+		const uint8_t *dev = ctx->sw_pin.dev + (c & 1u)*slot_bytes;
 		const unsigned jobs_per_block = SW_THREADS/32;
 		{
 			ProfScope prof(ctx, PCR_PROF_SW);

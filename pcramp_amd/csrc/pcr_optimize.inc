@@ -789,7 +789,7 @@ int evaluate_iteration(pcr_ctx *ctx, std::vector<IterAssay> &A, const pcr_optimi
 	bool beside = !tj.empty() && !getenv("PCRAMP_OPT_SERIAL");
 	if(beside){
 		hipError_t e = hipSuccess;
-		if(!ctx->aux_stream) e = hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking);
+		if(!ctx->aux_stream) e = ctx->aux_stream.create(hipStreamNonBlocking);
 		if(e == hipSuccess) e = hipStreamSynchronize(ctx->stream);               // (nothing of this handle is in flight that the records could race with)
 		if(e != hipSuccess){ g_err = std::string("pcr_optimize_batch: ") + hipGetErrorString(e); return fail(PCR_ERR_DEVICE); }
 		try{

@@ -784,7 +784,7 @@ void launch_post(K kernel, uint32_t waves, pcr_ctx *ctx, SeqSet &S, const HitSin
 	hipLaunchKernelGGL(kernel, dim3((S.n + waves - 1)/waves), dim3(64*waves), 0, ctx->stream, sink.hits, sink.seq_count, sink.best, sink.ncand, S.planes.p,
 		S.d_blk_off.p, S.irr.p, S.irr_off.p, S.db.p, S.d_seg_hi, sink.counters, sink.epoch, S.n,
 		fa->d_oligos, fa->n_pairs, (2*fa->n_pairs + 31)/32, S.d_len.p, S.d_active.p, fa->a->amp_min, fa->a->amp_max,
-		fa->a->ident_threshold, fa->a->use_taq_mama, fa->d_fr, fa->d_rf, (uint64_t)((S.n + 63)/64), ctx->mail_dev + (seq % pcr_ctx::MAIL_RING), seq);
+		fa->a->ident_threshold, fa->a->use_taq_mama, fa->d_fr, fa->d_rf, (uint64_t)((S.n + 63)/64), ctx->mail.dev + (seq % pcr_ctx::MAIL_RING), seq);
 }
 // reserved_seq: the sequence number a pipelined pass was given at enqueue; 0: the next one
 int fused_tail(pcr_ctx *ctx, SeqSet &S, const HitSink &sink, FusedAmp *fa, uint32_t reserved_seq)
@@ -830,7 +830,7 @@ int plain_tail(pcr_ctx *ctx, SeqSet &S, const HitSink &sink, bool async, FusedAm
 	++ctx->mail_seq;
 	if(async && fa && fa->staged){ fa->pub_seq = ctx->mail_seq; fa->pub_counters = sink.counters; }   // k_match publishes
 	else{
-		hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, ctx->stream, sink.counters, ctx->mail_dev + (ctx->mail_seq % pcr_ctx::MAIL_RING), ctx->mail_seq);
+		hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, ctx->stream, sink.counters, ctx->mail.dev + (ctx->mail_seq % pcr_ctx::MAIL_RING), ctx->mail_seq);
 		HIP_TRY(hipGetLastError());
 	}
 	return PCR_OK;
