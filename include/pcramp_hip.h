@@ -774,6 +774,14 @@ int64_t pcr_host_candidates(const pcr_pair *pairs, uint32_t n_pairs, int optimiz
 int64_t pcr_host_orientation_seeds(const pcr_word128 *oligo, uint32_t floor, uint32_t *codes, uint8_t *q,
 	uint8_t *off, uint64_t cap);
 
+/* The seeds the position-index form of the scan reads for one orientation: the oligo's 10-gram seeds folded back into
+ * 9-gram seeds with a constraint on the base behind the 9-gram (the index is sorted by it).  A window reaches `floor`
+ * matching slots only if, for some returned seed i, its bases off[i] .. off[i]+8 spell codes[i] and the code of base
+ * off[i]+9 lies in lo[i] .. hi[i] (A,C,G,T = 0..3; 0..3 = no constraint); every off[i] is at most 22.  Returns the seed
+ * count (may exceed cap), or -1 if the oligo has no 10-gram block structure (the scan then reads its 9-gram seeds whole). */
+int64_t pcr_host_orientation_fold_seeds(const pcr_word128 *oligo, uint32_t floor, uint32_t *codes, uint8_t *off,
+	uint8_t *lo, uint8_t *hi, uint64_t cap);
+
 /* The trial words of one local-search move of optimize_pcr.cpp for `oligo`, in the reference's order and
  * after its degeneracy / length gates (increase_degeneracy :17-19,:54-76; decrease_degeneracy :232-247;
  * trim5/trim3 :391-399; grow5/grow3 :671-673,:709-713), before is_valid (pcr_thermo) and the coverage

@@ -123,7 +123,7 @@ ABI_SYMBOLS = [
     "pcr_select_words", "pcr_select_sites", "pcr_get_entries", "pcr_amplify", "pcr_amplify_device", "pcr_screen_device", "pcr_move_coverage", "pcr_coverage_from_bits",
     "pcr_weighted_coverage", "pcr_num_sequences", "pcr_bitset_words", "pcr_profile_enable", "pcr_profile_read", "pcr_profile_read_kernel",
     "pcr_synchronize", "pcr_host_irregular_words", "pcr_host_window_valid", "pcr_host_candidates",
-    "pcr_host_orientation_seeds", "pcr_host_move_trials",
+    "pcr_host_orientation_seeds", "pcr_host_orientation_fold_seeds", "pcr_host_move_trials",
     "pcr_sw_align_words", "pcr_background_match", "pcr_multiplex_match",
     "pcr_thermo", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
@@ -243,6 +243,8 @@ def load_library():
     L.pcr_host_move_trials.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_uint64]
     L.pcr_host_orientation_seeds.restype = C.c_int64
     L.pcr_host_orientation_seeds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.pcr_host_orientation_fold_seeds.restype = C.c_int64
+    L.pcr_host_orientation_fold_seeds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     for fn in ("pcr_format_oligos", "pcr_format_header", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer"):
         getattr(L, fn).restype = C.c_int64
     L.pcr_format_oligos.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_char_p, C.c_uint64]
@@ -335,6 +337,19 @@ def host_move_trials(word, move, max_degen=1, primer_min=18, primer_max=25):
     if n < 0:
         raise PcrError(_err(L))
     return [(int(out[i, 0]), int(out[i, 1])) for i in range(int(n))]
+
+
+def host_orientation_fold_seeds(word, floor):
+    """Folded seeds (code, off, lo, hi) of one oligo word as the position-index scan reads them, or None if it has no 10-gram structure."""
+    L = load_library()
+    w = np.array([int(word[0]), int(word[1])], dtype=np.uint64)
+    n = L.pcr_host_orientation_fold_seeds(w.ctypes.data, int(floor), None, None, None, None, 0)
+    if n < 0:
+        return None
+    codes = np.zeros(max(int(n), 1), np.uint32)
+    off, lo, hi = (np.zeros(max(int(n), 1), np.uint8) for _ in range(3))
+    L.pcr_host_orientation_fold_seeds(w.ctypes.data, int(floor), codes.ctypes.data, off.ctypes.data, lo.ctypes.data, hi.ctypes.data, n)
+    return [(int(codes[i]), int(off[i]), int(lo[i]), int(hi[i])) for i in range(int(n))]
 
 
 def host_orientation_seeds(word, floor):

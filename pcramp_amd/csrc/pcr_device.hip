@@ -639,7 +639,7 @@ struct SeqSet {
 	DevBuf<uint32_t> irx_first, irx_last, irx_words, irx_sums; bool irx_valid = false, irx_usable = false;   // their inverse index (pcr_scan_seed2.inc), built on demand; usable: no key's run is longer than IRX_MAX_RUN
 	uint32_t irr_n_multi = 0;     // irregular words holding an IUPAC slot (they meet every candidate: no index for them)
 	// the positions of the set by the 9-gram that starts there (pcr_scan_seed3.inc), built on demand after a load
-	DevBuf<uint32_t> pix_first, pix_last, pix_sums, blk_info, blk_local, blk_tile0; DevBuf<uint4> pix_ent; std::vector<uint32_t> pix_count_h; uint64_t pix_generation = 0; bool pix_valid = false, pix_usable = false;
+	DevBuf<uint32_t> pix_first, pix_last, pix_sums, blk_info, blk_local, blk_tile0; DevBuf<uint4> pix_ent; std::vector<uint32_t> pix_start_h; uint64_t pix_generation = 0; bool pix_valid = false, pix_usable = false;
 	DevBuf<uint8_t> codes; DevBuf<uint64_t> d_code_off; bool have_codes = false;
 	// word DB of the last select
 	bool have_db = false;
@@ -713,12 +713,21 @@ struct pcr_ctx {
 	// second form of the seed scan: the per-oligo seed cache (the pass's lists live in its PassJob: PlanLists, pcr_select.inc)
 	struct S2Key { uint32_t a, c, g, t, floor_; bool operator==(const S2Key &o) const { return a == o.a && c == o.c && g == o.g && t == o.t && floor_ == o.floor_; } };
 	struct S2KeyHash { size_t operator()(const S2Key &k) const { uint64_t h = 0x9E3779B97F4A7C15ull; for(uint32_t v : {k.a, k.c, k.g, k.t, k.floor_}){ h ^= v; h *= 0x100000001B3ull; h ^= h >> 29; } return (size_t)h; } };
-	struct S2Entry { std::vector<uint32_t> seeds; /* code << 14 | off << 9 */ uint32_t off_mask; bool seedable; uint4 mask; /* the orientation's interleaved mask entry (k_seed2 / k_seed3) */
-		std::vector<uint32_t> chunks; uint32_t chunks_total = 0; uint64_t chunks_gen = 0; /* third form: running 64-entry chunks of the seeds' runs in the set whose position index has this generation */ };
+	struct S2Entry { std::vector<uint32_t> seeds; /* code << 14 | off << 9 */ uint32_t off_mask; bool seedable; uint4 mask; /* the orientation's interleaved mask entry (k_seed2 / k_seed3) */ };
 	std::unordered_map<S2Key, S2Entry, S2KeyHash> s2_cache;
 	std::vector<pcrhost::Seed> s2_tmp;
+	// third form: the oligo's FOLDED seeds (pcrhost::orientation_fold_seeds; a cache of its own: the second form's 9-gram lists are other
+	// lists under the same key), a span byte per seed, and the running 64-entry chunks of the seeds' spans in the sets whose position
+	// index has these generations -- the last S3_CHUNK_SETS of them, so that sets which alternate (the targets and backgrounds of a
+	// design iteration, a caller rotating over sets) do not recompute them pass after pass
+	static constexpr int S3_CHUNK_SETS = 4;
+	struct S3Chunks { uint64_t gen = 0; uint32_t total = 0; std::vector<uint32_t> run; };
+	struct S3Entry : S2Entry { std::vector<uint8_t> spans; /* lo | hi << 2 */ S3Chunks chunks[S3_CHUNK_SETS]; uint32_t next_slot = 0; };
+	std::unordered_map<S2Key, S3Entry, S2KeyHash> s3_cache;
+	std::vector<pcrhost::FoldSeed> s3_tmp;
 	struct S3Launch { Seed3Slices W; uint32_t n_chunks, per_wg, slice_cap, n_irr_wg; };
 	bool no_seed3 = false, s3_attr_set = false;   // PCRAMP_SEED3=0: second form (A/B)
+	bool s3_next = true;                          // PCRAMP_S3_NEXT=0: the third form with the plain 9-gram lists, span A..T: what it read before the index was sorted by the next base (A/B)
 	bool s2_attr_set = false; uint32_t s2_dbg = 0; bool no_irr_index = false;   // PCRAMP_IRR_INDEX=0: the irregular words scanned in chunks by every wave (A/B)
 	// first form, tables built on the device (k_seed_tables): the pass's seed list, its own per-oligo cache (8-gram seeds), the tables
 	std::unordered_map<S2Key, S2Entry, S2KeyHash> s1_cache;
@@ -997,17 +1006,17 @@ int ensure_irr_index(pcr_ctx *ctx, SeqSet &S)
 	return PCR_OK;
 }
 
-// The set's positions by the 9-gram that starts there (pcr_scan_seed3.inc), each with the 23 + 23 context bases around it: counting sort
-// on the device.  One 16-byte entry per base; built once per load.
+// The set's positions by the 9-gram that starts there and the base behind it (pcr_scan_seed3.inc), each with the 23 + 23 context bases
+// around it: counting sort on the device.  One 16-byte entry per base; built once per load.
 int ensure_pos_index(pcr_ctx *ctx, SeqSet &S)
 {
 	if(S.pix_valid) return PCR_OK;
 	S.pix_valid = true; S.pix_usable = false;
 	if(S.total_blocks == 0 || S.total_blocks*32 >= (uint64_t(1) << 32) - 64) return PCR_OK;   // positions are 32-bit
 	int rc;
-	if((rc = S.pix_first.ensure(PIX_CODES + 4)) != PCR_OK) return rc;
-	if((rc = S.pix_last.ensure(PIX_CODES + 4)) != PCR_OK) return rc;
-	const uint32_t n_blocks = (PIX_CODES + 4095u)/4096u;
+	if((rc = S.pix_first.ensure(PIX_KEYS + 4)) != PCR_OK) return rc;
+	if((rc = S.pix_last.ensure(PIX_KEYS + 4)) != PCR_OK) return rc;
+	const uint32_t n_blocks = (PIX_KEYS + 4095u)/4096u;
 	if((rc = S.pix_sums.ensure(n_blocks + 4)) != PCR_OK) return rc;
 	if((rc = S.pix_ent.ensure(S.total_blocks*32 + 64)) != PCR_OK) return rc;
 	{
@@ -1029,19 +1038,18 @@ int ensure_pos_index(pcr_ctx *ctx, SeqSet &S)
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipStreamSynchronize(ctx->stream));                                  // (tile0 is a local)
 	}
-	HIP_TRY(hipMemsetAsync(S.pix_last.p, 0, (size_t)PIX_CODES*sizeof(uint32_t), ctx->stream));
+	HIP_TRY(hipMemsetAsync(S.pix_last.p, 0, (size_t)PIX_KEYS*sizeof(uint32_t), ctx->stream));
 	const unsigned grid = (unsigned)((S.total_blocks + 255)/256);
 	hipLaunchKernelGGL(k_pix_build<false>, dim3(grid), dim3(256), 0, ctx->stream, S.tb_d(), S.blk_seq.p, S.d_blk_off.p, S.d_len.p, S.total_blocks, S.pix_last.p, (uint4 *)nullptr);
-	launch_exclusive_scan(ctx, S.pix_last.p, S.pix_first.p, PIX_CODES, S.pix_sums.p);
+	launch_exclusive_scan(ctx, S.pix_last.p, S.pix_first.p, PIX_KEYS, S.pix_sums.p);
 	hipLaunchKernelGGL(k_pix_build<true>, dim3(grid), dim3(256), 0, ctx->stream, S.tb_d(), S.blk_seq.p, S.d_blk_off.p, S.d_len.p, S.total_blocks, S.pix_last.p, S.pix_ent.p);
 	HIP_TRY(hipGetLastError());
 	{
-		std::vector<uint32_t> first(PIX_CODES), last(PIX_CODES);
-		HIP_TRY(hipMemcpyAsync(first.data(), S.pix_first.p, (size_t)PIX_CODES*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-		HIP_TRY(hipMemcpyAsync(last.data(), S.pix_last.p, (size_t)PIX_CODES*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		// the host's mirror: the exclusive prefix of the PIX_KEYS sub-run lengths and their total -- a span's length is one subtraction
+		S.pix_start_h.resize((size_t)PIX_KEYS + 1);
+		HIP_TRY(hipMemcpyAsync(S.pix_start_h.data(), S.pix_first.p, (size_t)PIX_KEYS*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(hipMemcpyAsync(S.pix_start_h.data() + PIX_KEYS, S.pix_last.p + (PIX_KEYS - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(hipStreamSynchronize(ctx->stream));
-		S.pix_count_h.resize(PIX_CODES);
-		for(uint32_t c = 0;c < PIX_CODES;++c) S.pix_count_h[c] = last[c] - first[c];
 		static uint64_t generations = 0;
 		S.pix_generation = ++generations;
 	}
@@ -1472,6 +1480,7 @@ pcr_ctx *pcr_create(int device, void *hip_stream, const pcr_params *params)
 	if(const char *v = getenv("PCRAMP_S2DBG")) ctx->s2_dbg = (uint32_t)atoi(v);
 	if(const char *v = getenv("PCRAMP_IRR_INDEX")) ctx->no_irr_index = v[0] == '0';
 	if(const char *v = getenv("PCRAMP_SEED3")) ctx->no_seed3 = v[0] == '0';
+	if(const char *v = getenv("PCRAMP_S3_NEXT")) ctx->s3_next = v[0] != '0';
 	if(const char *v = getenv("PCRAMP_LAUNCH_THREAD")) ctx->launch_thread = v[0] != '0';   // A/B, and for callers that want no helper thread
 	if(const char *v = getenv("PCRAMP_SCAN")){ if(v[0] == '1') ctx->scan_version = 1; else if(v[0] == '2') ctx->scan_version = 2; }   // A/B: 1 = popcount scan, 2 = bit-sliced only
 	{
@@ -2093,6 +2102,20 @@ int64_t pcr_host_orientation_seeds(const pcr_word128 *oligo, uint32_t floor, uin
 		if(codes) codes[i] = seeds[i].code;
 		if(q) q[i] = seeds[i].q;
 		if(off) off[i] = seeds[i].off;
+	}
+	return (int64_t)seeds.size();
+}
+
+int64_t pcr_host_orientation_fold_seeds(const pcr_word128 *oligo, uint32_t floor, uint32_t *codes, uint8_t *off, uint8_t *lo, uint8_t *hi, uint64_t cap)
+{
+	if(!oligo){ g_err = "null oligo"; return PCR_ERR_ARG; }
+	std::vector<pcrhost::FoldSeed> seeds; std::vector<pcrhost::Seed> tmp;
+	if(!pcrhost::orientation_fold_seeds(pcrhost::planes_of_word(oligo->w), floor, seeds, tmp)) return -1;
+	for(size_t i = 0;i < seeds.size() && i < cap;++i){
+		if(codes) codes[i] = seeds[i].code;
+		if(off) off[i] = seeds[i].off;
+		if(lo) lo[i] = seeds[i].lo;
+		if(hi) hi[i] = seeds[i].hi;
 	}
 	return (int64_t)seeds.size();
 }

@@ -548,7 +548,7 @@ inline double planes_degeneracy(const Planes &w)
 // (more than MAX_SEED_CODES codes: very low thresholds, or IUPAC slots that expand too far).
 struct Seed { uint32_t code; uint16_t orient; uint8_t q; uint8_t off; };   // q = gram length (8, or 9 for the second form of the seed scan); orient = 2*candidate + {0: fwd, 1: rc}; off = slot of the window's first base
 
-enum { SEED_Q = 8, SEED_Q_MAX = 9, MIN_SEED_BLOCK = 5, MAX_SEED_CODES = 512 /* per orientation */ };
+enum { SEED_Q = 8, SEED_Q_MAX = 10, MIN_SEED_BLOCK = 5, MAX_SEED_CODES = 512 /* per orientation */ };
 
 // all codes whose position j lies in sets[j] (4-bit base sets, bit 0 = A ... bit 3 = T; first base in the LOW bits)
 inline void seed_emit(const unsigned *sets, int Q, uint32_t orient, uint32_t off, std::vector<Seed> &out)
@@ -642,7 +642,8 @@ struct SeedLayout {
 // max_exact_pos (optional): largest first slot of a padded block (-1 if none); while it stays <= 32 - Q under a
 // slot shift of the oligo the seeds of the shifted oligo are these seeds with `off` moved by the shift.
 // Q: gram length (8 bases = 16-bit codes, the first form of the scan; 9 = 18-bit codes, the second form: three times fewer
-// false seed hits per target position for the same oligo, since the code space grows faster than the code lists).
+// false seed hits per target position for the same oligo, since the code space grows faster than the code lists; 10 = 20-bit
+// codes, which orientation_fold_seeds folds back into 9-gram seeds for the third form).
 inline bool orientation_seeds(const Planes &m, uint32_t floor_, uint32_t orient, std::vector<Seed> &out, int *max_exact_pos = nullptr, int Q = SEED_Q)
 {
 	if(max_exact_pos) *max_exact_pos = -1;
@@ -689,6 +690,126 @@ inline bool orientation_seeds(const Planes &m, uint32_t floor_, uint32_t orient,
 		seed_emit_block(sets, Q, orient, (uint32_t)ws, budget, out);
 		if(len < Q && max_exact_pos) *max_exact_pos = std::max(*max_exact_pos, pos);
 	});
+	return true;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Folded seeds (third form of the scan, pcr_scan_seed3.inc).  The position index is sorted by the 10-gram at a position: a
+// 9-gram's run is four sub-runs side by side, one per base behind the 9-gram.  The 10-gram codes of a block structure fold back
+// into 9-gram seeds: the codes of one offset that share their first nine bases become ONE seed -- the 9-gram code, the offset, and
+// lo..hi, the span from the lowest to the highest tenth base among them -- which reads sub-runs lo..hi only.  A span may cover a
+// base that is not in the group (A|G covers C): a superset, the exact count decides.  Cost = entries read = sum(hi - lo + 1)/4
+// runs of a 9-gram; the plain 9-gram list pays one whole run per seed (span A..T).
+struct FoldSeed { uint32_t code; uint8_t off, lo, hi; };   // code: 18 bits; a window matches the seed when its bases off..off+8 spell code and base off+9 lies in lo..hi
+
+// What a block's folded seeds read, in quarter runs, and how many they are: a 9-prefix with m < budget positions outside their
+// base sets leaves room for the tenth base to be anything (whole run); with m == budget the tenth lies in its base set.
+inline unsigned seed_block_fold_cost(const unsigned *sets, int budget, unsigned &n_seeds)
+{
+	unsigned d[9], n[3] = { 1, 0, 0 };
+	for(int j = 0;j < 9;++j){ d[j] = (unsigned)__builtin_popcount(sets[j]); n[0] *= d[j]; }
+	if(n[0] == 0 || sets[9] == 0){ n_seeds = 0; return 0; }
+	if(budget >= 1){
+		for(int j = 0;j < 9;++j){
+			if(d[j] == 4) continue;
+			const unsigned cj = n[0]/d[j]*(4 - d[j]);
+			n[1] += cj;
+			if(budget >= 2){ for(int i = j + 1;i < 9;++i){ if(d[i] < 4) n[2] += cj/d[i]*(4 - d[i]); } }
+		}
+	}
+	const unsigned last = sets[9];
+	const unsigned span = (unsigned)(32 - __builtin_clz(last)) - (unsigned)__builtin_ctz(last);
+	unsigned cost = 0; n_seeds = 0;
+	for(int m = 0;m <= budget;++m){ n_seeds += n[m]; cost += n[m]*((m < budget && last != 15u) ? 4u : span); }
+	return cost;
+}
+
+// Group 10-gram seeds (all of one orientation) by (offset, first nine bases), the tenth bases of a group ORed into a set.
+inline void fold_seeds(const std::vector<Seed> &q10, std::vector<FoldSeed> &out)
+{
+	std::vector<uint32_t> key(q10.size());                                   // off << 20 | first nine << 2 | tenth
+	for(size_t i = 0;i < q10.size();++i) key[i] = ((uint32_t)q10[i].off << 20) | ((q10[i].code & 0x3FFFFu) << 2) | (q10[i].code >> 18);
+	std::sort(key.begin(), key.end());
+	for(size_t i = 0;i < key.size();){
+		unsigned set = 0; size_t j = i;
+		for(;j < key.size() && (key[j] >> 2) == (key[i] >> 2);++j) set |= 1u << (key[j] & 3u);
+		FoldSeed f; f.code = (key[i] >> 2) & 0x3FFFFu; f.off = (uint8_t)(key[i] >> 20);
+		f.lo = (uint8_t)__builtin_ctz(set); f.hi = (uint8_t)(31 - __builtin_clz(set));
+		out.push_back(f);
+		i = j;
+	}
+}
+
+// Appends the folded seeds of one orientation; false (nothing appended) if it has no block structure at Q = 10 with at most
+// MAX_SEED_CODES folded seeds.  Among the admissible structures the one that reads the fewest entries is taken, not the one with
+// the fewest codes: entries read are what the third form pays for.  Every offset is <= 22: base off + 9 lies inside the window.
+// cost4 (optional): quarter runs read.
+inline bool orientation_fold_seeds(const Planes &m, uint32_t floor_, std::vector<FoldSeed> &out, std::vector<Seed> &tmp, unsigned *cost4 = nullptr)
+{
+	const int Q = 10;
+	if(cost4) *cost4 = 0;
+	const uint32_t occ = m.a | m.c | m.g | m.t;
+	const int size = __builtin_popcount(occ);
+	if(size == 0 || floor_ == 0 || floor_ > (uint32_t)size) return floor_ > (uint32_t)size;   // dead orientation: trivially "seeded" with no seeds
+	const int k = size - (int)floor_, first = __builtin_ctz(occ);
+	if(size < Q || (occ >> first) != ((size == 32) ? 0xFFFFFFFFu : ((1u << size) - 1u))) return false;   // no room for a 10-gram; holes
+	unsigned slot_set[32];
+	for(int j = 0;j < 32;++j) slot_set[j] = (j >= first && j < first + size) ? planes_nibble(m, j) : 0u;
+	auto window = [&](int pos, int len, unsigned *sets) -> int {
+		const int ws = std::min(pos, 32 - Q);
+		for(int j = 0;j < Q;++j){ const int sl = ws + j; sets[j] = (sl >= pos && sl < pos + len) ? slot_set[sl] : 15u; }
+		return ws;
+	};
+	SeedLayout best = { 0, 0, 0, 0 }; bool have = false; unsigned best_cost = 0;
+	for(int n2 = 0;3*(n2 - 1) < k + 1;++n2){
+		for(int n1 = 0;3*n2 + 2*(n1 - 1) < k + 1;++n1){
+			const int n0 = std::max(0, k + 1 - 3*n2 - 2*n1);
+			if(n0 + n1 + n2 == 0) continue;
+			for(int n1s = 0;n1s <= n1;++n1s){
+				const int rest = size - Q*(n1 - n1s) - (Q - 1)*n1s - Q*n2;
+				if(rest < 0 || (n0 > 0 && rest/n0 < MIN_SEED_BLOCK)) continue;
+				const SeedLayout lay = { n0, n1, n1s, n2 };
+				unsigned seeds = 0, cost = 0;
+				lay.each(first, size, Q, [&](int pos, int len, int budget){
+					unsigned sets[SEED_Q_MAX], ns = 0;
+					window(pos, len, sets);
+					if(seeds <= MAX_SEED_CODES){ cost += seed_block_fold_cost(sets, budget, ns); seeds += ns; }
+				});
+				if(seeds > MAX_SEED_CODES) continue;
+				if(!have || cost < best_cost){ have = true; best = lay; best_cost = cost; }
+			}
+		}
+	}
+	if(!have) return false;
+	tmp.clear();
+	best.each(first, size, Q, [&](int pos, int len, int budget){
+		unsigned sets[SEED_Q_MAX];
+		const int ws = window(pos, len, sets);
+		seed_emit_block(sets, Q, 0, (uint32_t)ws, budget, tmp);
+	});
+	fold_seeds(tmp, out);
+	if(cost4) *cost4 = best_cost;
+	return true;
+}
+
+// The seeds the third form reads for one orientation: the folded list where it exists and reads fewer entries than the plain 9-gram
+// list (fold = false: never), else the plain list with span A..T -- a seed of today's kind, which reads its code's whole run.  false
+// exactly when orientation_seeds(Q = 9) returns false, so that the third form takes the passes it always took.
+inline bool orientation_index_seeds(const Planes &m, uint32_t floor_, bool fold, std::vector<FoldSeed> &out, std::vector<Seed> &tmp, unsigned *cost4 = nullptr)
+{
+	tmp.clear();
+	if(!orientation_seeds(m, floor_, 0, tmp, nullptr, 9)) return false;
+	const size_t at = out.size();
+	const unsigned plain_cost = 4u*(unsigned)tmp.size();
+	for(const Seed &sd : tmp){ FoldSeed f; f.code = sd.code; f.off = sd.off; f.lo = 0; f.hi = 3; out.push_back(f); }
+	if(cost4) *cost4 = plain_cost;
+	if(!fold || tmp.empty()) return true;
+	std::vector<FoldSeed> folded; unsigned c4 = 0;
+	if(orientation_fold_seeds(m, floor_, folded, tmp, &c4) && c4 < plain_cost){
+		out.resize(at);
+		out.insert(out.end(), folded.begin(), folded.end());
+		if(cost4) *cost4 = c4;
+	}
 	return true;
 }
 

@@ -23,6 +23,13 @@
 // workgroups (n_irr_wg), which read no chunks: that chain of dependent loads runs beside the chunk waves' instead of behind it.
 
 constexpr uint32_t PIX_CODES = 1u << 18;
+// The runs are sorted once more, by the base BEHIND the 9-gram: the sort key is 9-gram << 2 | code of base p + 9, so a 9-gram's run is four
+// sub-runs side by side and pix_first / pix_last have PIX_KEYS entries.  A seed carries a span lo..hi of next bases (host: the 10-gram
+// seeds of an oligo folded back into 9-gram seeds, pcr_host.hpp) and reads pix_first[code << 2 | lo] ... pix_last[code << 2 | hi]: a
+// quarter of the run where the tenth base is fixed, all of it (lo..hi = A..T) where it is free.  The last 9-gram of a sequence is
+// sorted under whatever tb holds behind it: a seed that constrains that base has offset <= 22, so its window covers p + 9 and
+// leaves the sequence -- the validity bit says so.
+constexpr uint32_t PIX_KEYS = PIX_CODES << 2;
 constexpr uint32_t S3_BATCH = 8;
 
 // a block of 32 positions: the 9-gram that starts at each (inside its sequence) -- counted, then scattered to its code's run together
@@ -44,7 +51,8 @@ __global__ void k_pix_build(const uint32_t *__restrict__ tb, const uint32_t *__r
 #pragma unroll
 	for(int i = 0;i < 32;++i){
 		if(p0 + i + 9 > L) break;
-		const uint32_t code = ((i < 16) ? funnel(w[2], w[3], 2*i) : funnel(w[3], w[4], 2*(i - 16))) & S2_CODE_MASK;
+		const uint32_t ten = (i < 16) ? funnel(w[2], w[3], 2*i) : funnel(w[3], w[4], 2*(i - 16));   // bases p ... p + 15
+		const uint32_t code = ((ten & S2_CODE_MASK) << 2) | ((ten >> 18) & 3u);                     // 9-gram << 2 | base p + 9
 		if(SCATTER){
 			const uint32_t at = atomicAdd(&count_or_cursor[code], 1u);
 			// left = bases p - 23 ... p - 1, right = bases p + 9 ... p + 31 (46 bits each; the 9-gram between them is the run's key)
@@ -61,9 +69,10 @@ __global__ void k_pix_build(const uint32_t *__restrict__ tb, const uint32_t *__r
 struct Seed3Tables {
 	const uint32_t *seeds;        // as Seed2Tables
 	const uint32_t *chunk_prefix; // [n_seeds + 1]: 64-entry chunks of the runs of the seeds before this one (host, per pass, from its copy of the run lengths)
+	const uint8_t *spans;         // [n_seeds]: lo | hi << 2, the next bases (sub-runs of the code's run) the seed reads
 	const uint4 *masks; const uint8_t *floors;
 	uint32_t n_seeds, n_or, or_base;
-	const uint32_t *pix_first, *pix_last; const uint4 *pix_ent;     // entry: position | left 23 bases, right 23 bases of its 9-gram (92 bits)
+	const uint32_t *pix_first, *pix_last; const uint4 *pix_ent;     // [PIX_KEYS] sub-run bounds; entry: position | left 23 bases, right 23 bases of its 9-gram (92 bits)
 	uint32_t n_chunks, per_wg, slice_cap;   // workgroup w takes chunks [w * per_wg, (w + 1) * per_wg); LDS holds slice_cap list entries
 	uint32_t n_irr_wg;                      // the launch's first n_irr_wg workgroups look the irregular words up and do nothing else (0: the chunk waves do it afterwards)
 };
@@ -140,11 +149,12 @@ template<uint32_t S3_THREADS>
 __global__ __launch_bounds__(S3_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_seed3(Seed3Tables T3, Seed3Set Q, IrrArgs2 IA, const uint4 *__restrict__ cand_fwd, const uint32_t *__restrict__ cand_floor,
 	HitSink sink, S2Clear Z, Seed3Slices W)
 {
-	extern __shared__ uint4 s3_dyn[];                          // masks [n_or] | the workgroup's slice of chunk_prefix and of the seeds [slice_cap each] | floors [n_or]
+	extern __shared__ uint4 s3_dyn[];                          // masks [n_or] | the workgroup's slice of chunk_prefix and of the seeds [slice_cap each] | floors [n_or, padded to 16] | the slice of the spans
 	uint4 *const masks = s3_dyn;
 	uint32_t *const prefix = (uint32_t *)(masks + T3.n_or);
 	uint32_t *const seeds = prefix + T3.slice_cap;
 	uint8_t *const floors = (uint8_t *)(seeds + T3.slice_cap);
+	uint8_t *const spans = floors + ((T3.n_or + 15u) & ~15u);
 	const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
 	// the lean fused pass has no staging launch: what k_seed2 clears in its prologue is cleared here
 	for(uint32_t i = blockIdx.x*S3_THREADS + threadIdx.x;i < Z.n0;i += gridDim.x*S3_THREADS) Z.z0[i] = make_uint4(0, 0, 0, 0);
@@ -159,7 +169,7 @@ __global__ __launch_bounds__(S3_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
 	const uint32_t wg = blockIdx.x - T3.n_irr_wg, n_wg = gridDim.x - T3.n_irr_wg;     // among the workgroups that read the chunks
 	const uint32_t s_lo = W.start[wg];
 	const uint32_t n_slice = min(min(W.start[wg + 1] + 2u, T3.n_seeds + 1u) - s_lo, T3.slice_cap);   // list entries s_lo ... start[w + 1] + 1
-	for(uint32_t i = threadIdx.x;i < n_slice;i += S3_THREADS){ prefix[i] = T3.chunk_prefix[s_lo + i]; seeds[i] = (s_lo + i < T3.n_seeds) ? T3.seeds[s_lo + i] : 0u; }
+	for(uint32_t i = threadIdx.x;i < n_slice;i += S3_THREADS){ prefix[i] = T3.chunk_prefix[s_lo + i]; const bool in = s_lo + i < T3.n_seeds; seeds[i] = in ? T3.seeds[s_lo + i] : 0u; spans[i] = in ? T3.spans[s_lo + i] : (uint8_t)0; }
 	__syncthreads();
 	const uint32_t gw = wg*S3_WAVES + wave, n_gw = n_wg*S3_WAVES;
 	const uint32_t q_lo = wg*T3.per_wg, q_hi = min(q_lo + T3.per_wg, T3.n_chunks);
@@ -172,8 +182,8 @@ __global__ __launch_bounds__(S3_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
 				uint32_t lo = 0, hi = n_slice - 1u;                                // prefix[lo] <= q < prefix[hi]
 				while(hi - lo > 1u){ const uint32_t mid = (lo + hi) >> 1; if(prefix[mid] <= q) lo = mid; else hi = mid; }
 				c_sd = seeds[lo];
-				const uint32_t code = c_sd >> 14;
-				const uint32_t f = T3.pix_first[code], e = T3.pix_last[code], j0 = (q - prefix[lo])*64u;
+				const uint32_t key = (c_sd >> 14) << 2, sp = spans[lo];               // sub-runs key + lo .. key + hi
+				const uint32_t f = T3.pix_first[key + (sp & 3u)], e = T3.pix_last[key + (sp >> 2)], j0 = (q - prefix[lo])*64u;
 				c_first = f + j0; c_cnt = (e - f) - j0;                           // entries of the run from this chunk on (> 0)
 			}
 		}

@@ -8,11 +8,12 @@ struct PlanLists {
 	std::vector<uint32_t> s2_group_end, s2_group_offmask, s2_group_or, s2_group_nor;   // per group: end in the seed list, forward-seed slot offsets, first orientation, orientations spanned
 	std::vector<pcr_ctx::S3Launch> s3_launch;      // third form: per launch group, the workgroups' slices of the chunk list
 	std::vector<uint32_t> s3_prefix;               // third form: the pass's chunk list
+	std::vector<uint8_t> s3_spans;                 // third form: per seed of s2_seeds the next bases it reads, lo | hi << 2
 	std::vector<uint32_t> s1_seeds;                // first form, tables built on the device: the pass's seed list
 	void clear()
 	{
 		s2_seeds.clear(); s2_masks.clear(); s2_floors.clear(); s2_group_end.clear(); s2_group_offmask.clear(); s2_group_or.clear(); s2_group_nor.clear();
-		s3_launch.clear(); s3_prefix.clear(); s1_seeds.clear();
+		s3_launch.clear(); s3_prefix.clear(); s3_spans.clear(); s1_seeds.clear();
 	}
 };
 
@@ -30,9 +31,11 @@ inline uint32_t spread16(uint32_t v)               // bit i of the low half -> b
 // batch of 1 000 trial assays (pcramp.h:32) is 4 000 orientations = 16+ groups (r02 sent it to the first form with host-built
 // tables: 21 ms per select_words on a C5 shard).  false: an orientation whose seeds alone exceed one launch.
 constexpr uint32_t S2_MAX_GROUPS = 4096;
-// S3 (optional): the set whose position index the third form will read -- the chunk list of every launch group (L.s3_prefix: the
-// running number of 64-entry chunks of the group's seeds' runs, its total behind it) is made alongside, from chunk counts cached
-// beside each oligo's seeds for the set last used.
+// S3 (optional): the set whose position index the third form will read.  The seeds are then the oligo's FOLDED seeds, from a cache
+// of their own (ctx->s3_cache; PCRAMP_S3_NEXT=0: the plain 9-gram list with span A..T), listed in the same u32 form with a span
+// byte per seed beside them (L.s3_spans), and the chunk list of every launch group (L.s3_prefix: the running number of 64-entry
+// chunks of the group's seeds' spans, its total behind it) is made alongside, from chunk counts cached beside each oligo's seeds
+// for the sets last used.
 bool plan_seed2(pcr_ctx *ctx, PlanLists &L, const std::vector<pcrhost::Candidate> &cand, std::vector<uint32_t> &or_seed, std::vector<uint32_t> &or_plain, uint32_t &irr_off_mask,
 	const SeqSet *S3 = nullptr)
 {
@@ -52,25 +55,50 @@ bool plan_seed2(pcr_ctx *ctx, PlanLists &L, const std::vector<pcrhost::Candidate
 		if(S3) return g_or <= S3_MAX_OR && n <= S3_MAX_SEEDS;
 		return g_or <= S2_MAX_OR && n <= S2_MAX_SEEDS && sizeof(S2Shared) + 17*(size_t)g_or + 8*n + 1024 <= 160*1024;
 	};
+	// per orientation ONE 16-byte mask entry: the four base-set planes, slots 0..15 spread to the even bits (slot k -> bit 2k) and
+	// slots 16..31 to the odd bits (slot 16 + k -> bit 2k + 1): both halves of a window are counted by one multiplexer pass
+	// (s2_count) from one LDS read
+	auto mask_of = [](const Planes &m){
+		return make_uint4(spread16(m.a) | (spread16(m.a >> 16) << 1), spread16(m.c) | (spread16(m.c >> 16) << 1),
+		                  spread16(m.g) | (spread16(m.g >> 16) << 1), spread16(m.t) | (spread16(m.t >> 16) << 1));
+	};
+	std::vector<uint8_t> &spans = L.s3_spans;
+	spans.clear();
+	if(ctx->s3_cache.size() > 16384) ctx->s3_cache.clear();
 	for(uint32_t o = 0;o < n_or;++o){
 		const pcrhost::Candidate &c = cand[o >> 1];
 		const Planes &m = (o & 1u) ? c.rc : c.fwd;
 		const pcr_ctx::S2Key key = {m.a, m.c, m.g, m.t, c.floor_};
-		auto it = ctx->s2_cache.find(key);
-		if(it == ctx->s2_cache.end()){
-			pcr_ctx::S2Entry e; e.off_mask = 0;
-			ctx->s2_tmp.clear();
-			e.seedable = pcrhost::orientation_seeds(m, c.floor_, 0, ctx->s2_tmp, nullptr, S2_Q);
-			// per orientation ONE 16-byte mask entry: the four base-set planes, slots 0..15 spread to the even bits (slot k -> bit 2k) and
-			// slots 16..31 to the odd bits (slot 16 + k -> bit 2k + 1): both halves of a window are counted by one multiplexer pass
-			// (s2_count) from one LDS read
-			e.mask = make_uint4(spread16(m.a) | (spread16(m.a >> 16) << 1), spread16(m.c) | (spread16(m.c >> 16) << 1),
-			                    spread16(m.g) | (spread16(m.g >> 16) << 1), spread16(m.t) | (spread16(m.t >> 16) << 1));
-			e.seeds.reserve(ctx->s2_tmp.size());
-			for(const pcrhost::Seed &sd : ctx->s2_tmp){ e.seeds.push_back((sd.code << 14) | ((uint32_t)sd.off << 9)); e.off_mask |= 1u << sd.off; }
-			it = ctx->s2_cache.emplace(key, std::move(e)).first;
+		pcr_ctx::S3Entry *e3 = nullptr; const pcr_ctx::S2Entry *e2 = nullptr;
+		if(S3){
+			auto it = ctx->s3_cache.find(key);
+			if(it == ctx->s3_cache.end()){
+				pcr_ctx::S3Entry e; e.off_mask = 0;
+				ctx->s3_tmp.clear(); ctx->s2_tmp.clear();
+				e.seedable = pcrhost::orientation_index_seeds(m, c.floor_, ctx->s3_next, ctx->s3_tmp, ctx->s2_tmp);
+				e.mask = mask_of(m);
+				e.seeds.reserve(ctx->s3_tmp.size()); e.spans.reserve(ctx->s3_tmp.size());
+				for(const pcrhost::FoldSeed &sd : ctx->s3_tmp){
+					e.seeds.push_back((sd.code << 14) | ((uint32_t)sd.off << 9)); e.spans.push_back((uint8_t)(sd.lo | (sd.hi << 2))); e.off_mask |= 1u << sd.off;
+				}
+				it = ctx->s3_cache.emplace(key, std::move(e)).first;
+			}
+			e3 = &it->second; e2 = e3;
 		}
-		pcr_ctx::S2Entry &e = it->second;
+		else{
+			auto it = ctx->s2_cache.find(key);
+			if(it == ctx->s2_cache.end()){
+				pcr_ctx::S2Entry e; e.off_mask = 0;
+				ctx->s2_tmp.clear();
+				e.seedable = pcrhost::orientation_seeds(m, c.floor_, 0, ctx->s2_tmp, nullptr, S2_Q);
+				e.mask = mask_of(m);
+				e.seeds.reserve(ctx->s2_tmp.size());
+				for(const pcrhost::Seed &sd : ctx->s2_tmp){ e.seeds.push_back((sd.code << 14) | ((uint32_t)sd.off << 9)); e.off_mask |= 1u << sd.off; }
+				it = ctx->s2_cache.emplace(key, std::move(e)).first;
+			}
+			e2 = &it->second;
+		}
+		const pcr_ctx::S2Entry &e = *e2;
 		L.s2_masks[o] = e.mask;
 		if(!e.seedable){ or_plain.push_back(o); continue; }
 		or_seed.push_back(o);
@@ -86,16 +114,25 @@ bool plan_seed2(pcr_ctx *ctx, PlanLists &L, const std::vector<pcrhost::Candidate
 		out.resize(at + e.seeds.size());
 		for(size_t k = 0;k < e.seeds.size();++k) out[at + k] = e.seeds[k] | (o - group_or0);
 		if(S3){
-			if(e.chunks_gen != S3->pix_generation){                                   // exclusive running chunk counts of the oligo's seeds in this set
-				e.chunks.resize(e.seeds.size());
+			spans.insert(spans.end(), e3->spans.begin(), e3->spans.end());
+			// exclusive running chunk counts of the oligo's seeds in this set: kept for the last S3_CHUNK_SETS index generations
+			pcr_ctx::S3Chunks *ch = nullptr;
+			for(pcr_ctx::S3Chunks &x : e3->chunks){ if(x.gen == S3->pix_generation){ ch = &x; break; } }
+			if(!ch){
+				ch = &e3->chunks[e3->next_slot]; e3->next_slot = (e3->next_slot + 1u) % pcr_ctx::S3_CHUNK_SETS;
+				ch->run.resize(e.seeds.size());
+				const uint32_t *const start = S3->pix_start_h.data();
 				uint32_t run = 0;
-				for(size_t k = 0;k < e.seeds.size();++k){ e.chunks[k] = run; run += (S3->pix_count_h[e.seeds[k] >> 14] + 63u) >> 6; }
-				e.chunks_total = run; e.chunks_gen = S3->pix_generation;
+				for(size_t k = 0;k < e.seeds.size();++k){
+					const uint32_t key4 = (e.seeds[k] >> 14) << 2, sp = e3->spans[k];
+					ch->run[k] = run; run += (start[key4 + (sp >> 2) + 1u] - start[key4 + (sp & 3u)] + 63u) >> 6;
+				}
+				ch->total = run; ch->gen = S3->pix_generation;
 			}
 			const size_t pa = pf.size();
-			pf.resize(pa + e.chunks.size());
-			for(size_t k = 0;k < e.chunks.size();++k) pf[pa + k] = pf_run + e.chunks[k];
-			pf_run += e.chunks_total;
+			pf.resize(pa + ch->run.size());
+			for(size_t k = 0;k < ch->run.size();++k) pf[pa + k] = pf_run + ch->run[k];
+			pf_run += ch->total;
 		}
 		if(!(o & 1u)){ irr_off_mask |= e.off_mask; group_mask |= e.off_mask; }   // slot offsets at which forward seeds sit (irregular-word scan)
 	}
@@ -137,7 +174,7 @@ bool plan_seed3_slices(pcr_ctx *ctx, PlanLists &PL, bool with_irr)
 		}
 		for(uint32_t w = G + 1;w <= S3_MAX_WG;++w) L.W.start[w] = at;
 		for(uint32_t w = 0;w < G;++w) L.slice_cap = std::max(L.slice_cap, std::min(L.W.start[w + 1] + 2u, ns + 1u) - L.W.start[w]);
-		if(17*(size_t)PL.s2_group_nor[g] + 8*(size_t)L.slice_cap + 64 > S3_LDS_BUDGET) return false;
+		if(17*(size_t)PL.s2_group_nor[g] + 9*(size_t)L.slice_cap + 64 > S3_LDS_BUDGET) return false;   // masks, floors | slice of the chunk list, the seeds and their spans
 	}
 	return true;
 }
@@ -440,7 +477,7 @@ int choose_scan_form(pcr_ctx *ctx, SeqSet &S, const std::vector<pcrhost::Candida
 	// ... and the third form -- the targets' positions indexed by their 9-grams, the seeds looked up (pcr_scan_seed3.inc) -- where every
 	// candidate is seeded (and the irregular words can come in through their index too: want_seed3, decided before the planning)
 	const bool use_seed3 = use_seed2 && want_seed3 && or_plain.empty() && !or_seed.empty()
-		&& L.s3_prefix.size() == L.s2_seeds.size() + L.s2_group_end.size();
+		&& L.s3_prefix.size() == L.s2_seeds.size() + L.s2_group_end.size() && L.s3_spans.size() == L.s2_seeds.size();
 	if(use_seed2){ P.form = use_seed3 ? ScanForm::Seed3 : ScanForm::Seed2; P.n_seeds = L.s2_seeds.size(); }
 	else if(no_shifts && !ctx->host_seed_tables && n_or <= S1_MAX_OR){      // first form, tables built by k_seed_tables
 		plan_seed1(ctx, L, cand, or_seed, or_plain, P.irr_off_mask);
@@ -475,7 +512,7 @@ int choose_scan_form(pcr_ctx *ctx, SeqSet &S, const std::vector<pcrhost::Candida
 //   launcher thread (stage B): the Stager rings with their wait_published spin; the sizing of S.ctrl / hits / S.db / best / S.touched;
 //     the lean decision and the epoch; every launch; S.ctrl_clean, touched_from_seg, touched_built, d_seg_hi and the have_db markers
 //     (have_db, n_entries, n_touched, db_cap, n_slots); d_cand_*; the profiling events; t_host[1], t_host[2].
-//   set state that stage A READS (pix_*, pix_count_h, irx_valid, irr_size_count, irr_n_multi, n_irr, n_degen_tiles, n, bucket_cap)
+//   set state that stage A READS (pix_*, pix_start_h, irx_valid, irr_size_count, irr_n_multi, n_irr, n_degen_tiles, n, bucket_cap)
 //     is written only while the queue holds no job of the handle: every writer sits behind DRAIN / flush_launcher.
 struct PassJob {
 	// the call
@@ -500,7 +537,7 @@ struct Scan2Staged { Scan2Tables T; const uint32_t *d_tab = nullptr, *d_bias = n
 struct StagedTables {
 	SeedTables ST = {};
 	Seed2Tables ST2 = {};
-	const uint32_t *d_s3_prefix = nullptr;
+	const uint32_t *d_s3_prefix = nullptr; const uint8_t *d_s3_spans = nullptr;
 	Scan2Staged plain, seedset;
 	bool lean = false, fuse = false;                  // lean: the fused pass without a staging launch (see pcr_ctx::dstage)
 	size_t bits_bytes = 0;                            // of each of the fused pass's two result bitsets
@@ -561,7 +598,7 @@ int stage_tables(pcr_ctx *ctx, SeqSet &S, const PassJob &J, FusedAmp *fa, bool a
 	bytes += (H.image.size() + H.heads.size() + H.multi.size() + 64)*sizeof(uint32_t);
 	if(seed2){
 		bytes += L.s2_masks.size()*sizeof(uint4) + L.s2_floors.size() + L.s2_seeds.size()*sizeof(uint32_t) + 512;
-		if(seed3) bytes += L.s3_prefix.size()*sizeof(uint32_t) + 64;
+		if(seed3) bytes += L.s3_prefix.size()*sizeof(uint32_t) + L.s3_spans.size() + 128;
 	}
 	if(build_tables) bytes += L.s1_seeds.size()*sizeof(uint32_t) + 256;
 	T.bits_bytes = J.bits_bytes; T.fuse = J.fuse;
@@ -598,7 +635,7 @@ int stage_tables(pcr_ctx *ctx, SeqSet &S, const PassJob &J, FusedAmp *fa, bool a
 		T.ST2.masks = st.put(L.s2_masks.data(), L.s2_masks.size());
 		T.ST2.floors = st.put(L.s2_floors.data(), L.s2_floors.size());
 		T.ST2.n_seeds = (uint32_t)L.s2_seeds.size(); T.ST2.n_or = n_or;
-		if(seed3) T.d_s3_prefix = st.put(L.s3_prefix.data(), L.s3_prefix.size());
+		if(seed3){ T.d_s3_prefix = st.put(L.s3_prefix.data(), L.s3_prefix.size()); T.d_s3_spans = st.put(L.s3_spans.data(), L.s3_spans.size()); }
 	}
 	// the staging launch also clears the control block and the result bitsets -- unless the pass is lean: then the tables
 	// are already in device memory, the control block was left clean by the previous pass's tail and the first scan launch
@@ -664,16 +701,16 @@ int launch_seed1(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const StagedTables 
 }
 
 // Third form: the launch of one seed group (its slices: plan_seed3_slices).
-int launch_seed3_group(pcr_ctx *ctx, SeqSet &S, const Seed2Tables &Tg, const uint32_t *d_chunk_prefix, const pcr_ctx::S3Launch &L3, const IrrArgs2 &IA,
+int launch_seed3_group(pcr_ctx *ctx, SeqSet &S, const Seed2Tables &Tg, const uint32_t *d_chunk_prefix, const uint8_t *d_spans, const pcr_ctx::S3Launch &L3, const IrrArgs2 &IA,
 	const HitSink &sink, const S2Clear &Z)
 {
-	Seed3Tables T3; T3.seeds = Tg.seeds; T3.chunk_prefix = d_chunk_prefix; T3.masks = Tg.masks; T3.floors = Tg.floors;
+	Seed3Tables T3; T3.seeds = Tg.seeds; T3.spans = d_spans; T3.chunk_prefix = d_chunk_prefix; T3.masks = Tg.masks; T3.floors = Tg.floors;
 	T3.n_seeds = Tg.n_seeds; T3.n_or = Tg.n_or; T3.or_base = Tg.or_base;
 	T3.pix_first = S.pix_first.p; T3.pix_last = S.pix_last.p; T3.pix_ent = S.pix_ent.p;
 	Seed3Set Q3 = { S.valid_d(), S.blk_info.p, S.blk_local.p, S.d_active.p };
 	T3.n_chunks = L3.n_chunks; T3.per_wg = L3.per_wg; T3.slice_cap = L3.slice_cap;
 	T3.n_irr_wg = IA.ix_first ? L3.n_irr_wg : 0u;           // (without the index the chunk workgroups are fewer than they could be: harmless)
-	const size_t dyn3 = (size_t)Tg.n_or*sizeof(uint4) + 2*(size_t)T3.slice_cap*sizeof(uint32_t) + (((size_t)Tg.n_or + 15) & ~size_t(15)) + 16;
+	const size_t dyn3 = (size_t)Tg.n_or*sizeof(uint4) + 2*(size_t)T3.slice_cap*sizeof(uint32_t) + (((size_t)Tg.n_or + 15) & ~size_t(15)) + (((size_t)T3.slice_cap + 15) & ~size_t(15)) + 16;
 	if(!ctx->s3_attr_set){
 		HIP_TRY(hipFuncSetAttribute((const void *)k_seed3<S3_WG_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 128*1024));
 		ctx->s3_attr_set = true;
@@ -707,6 +744,7 @@ int launch_seed_groups(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const PlanLis
 	for(size_t g = 0;g < L.s2_group_end.size();++g){
 		Seed2Tables Tg = T.ST2;
 		const uint32_t or0 = L.s2_group_or[g], g_or = L.s2_group_nor[g];
+		const uint8_t *const d_spans = seed3 ? T.d_s3_spans + g_begin : nullptr;         // (the group's offset in the seed list is the spans' too)
 		Tg.seeds = T.ST2.seeds + g_begin; Tg.n_seeds = L.s2_group_end[g] - g_begin;
 		Tg.masks = T.ST2.masks + (size_t)or0; Tg.floors = T.ST2.floors + or0; Tg.n_or = g_or; Tg.or_base = or0;
 		g_begin = L.s2_group_end[g];
@@ -730,7 +768,7 @@ int launch_seed_groups(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const PlanLis
 			Z.z0 = (uint4 *)fa->d_fr; Z.z1 = (uint4 *)fa->d_rf; Z.n0 = Z.n1 = (uint32_t)(T.bits_bytes/16); Z.ctrl = sink.counters;
 		}
 		if(seed3){
-			if((rc = launch_seed3_group(ctx, S, Tg, T.d_s3_prefix + g_prefix, L.s3_launch[g], IA, sink, Z)) != PCR_OK) return rc;
+			if((rc = launch_seed3_group(ctx, S, Tg, T.d_s3_prefix + g_prefix, d_spans, L.s3_launch[g], IA, sink, Z)) != PCR_OK) return rc;
 			g_prefix += Tg.n_seeds + 1u;
 		}
 		else hipLaunchKernelGGL(k_seed2_of_ctx, sgrid, sblock, dyn, ctx->stream, S.tb_d(), S.valid_d(), S.tile_desc.p, S.n_tiles, Tg, S.d_active.p, ctx->d_cand_fwd, ctx->d_cand_floor,
