@@ -412,6 +412,15 @@ typedef struct {
 int pcr_thermo(pcr_ctx *ctx, const pcr_word128 *oligos, uint32_t n, int check_homo_dimer,
 	const pcr_thermo_args *args, pcr_thermo_result *out);
 
+/* PCR::is_valid without the dimer test (valid_pcr.cpp:5-31) for n words: valid_out[i] = 1 iff every expansion of
+ * words[i] has its perfect-match duplex Tm in [tm_min, tm_max] and its hairpin Tm <= max_hairpin, at strand
+ * concentration primer_strand/degeneracy.  The same verdicts as pcr_thermo with check_homo_dimer = 0, by the path the
+ * local search takes for its trial words: one record per word, the expansions spelt and the verdict reduced on the
+ * device.  Errors as pcr_thermo: PCR_ERR_ARG for an empty word, a hole between the oligo's ends or a length over 32,
+ * PCR_ERR_CAPACITY for more than 65536 expansions. */
+int pcr_valid_words(pcr_ctx *ctx, const pcr_word128 *words, uint32_t n, const pcr_thermo_args *args,
+	uint8_t *valid_out);
+
 /* PCR::max_dimer_tm (pcr_assay.cpp:232-269): max heterodimer Tm of F x R over all expansions,
  * strand(primer_strand/D(F), primer_strand/D(R)) (nuc_cruc.h:818-838). */
 int pcr_dimer(pcr_ctx *ctx, const pcr_pair *pairs, uint32_t n, const pcr_thermo_args *args, float *max_tm);

@@ -125,7 +125,7 @@ ABI_SYMBOLS = [
     "pcr_synchronize", "pcr_host_irregular_words", "pcr_host_window_valid", "pcr_host_candidates",
     "pcr_host_orientation_seeds", "pcr_host_orientation_fold_seeds", "pcr_host_move_trials",
     "pcr_sw_align_words", "pcr_background_match", "pcr_multiplex_match",
-    "pcr_thermo", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
+    "pcr_thermo", "pcr_valid_words", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
@@ -209,6 +209,7 @@ def load_library():
     L.pcr_background_match.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(BackgroundArgs), C.c_void_p]
     L.pcr_multiplex_match.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_void_p]
     L.pcr_thermo.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(ThermoArgs), C.c_void_p]
+    L.pcr_valid_words.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ThermoArgs), C.c_void_p]
     L.pcr_dimer.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ThermoArgs), C.c_void_p]
     L.pcr_multiplex_compatible.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ThermoArgs), C.c_void_p]
     L.pcr_random_assays.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(SamplerArgs),
@@ -705,6 +706,15 @@ class Screener:
             return np.frombuffer(out, dtype=np.uint32).reshape(-1, 8)[:len(oligos), 0] != 0
         return [dict(valid=bool(r.valid), n=r.n_expansions, tm=np.float32(r.tm), dH=np.float32(r.dH), dS=np.float32(r.dS),
                      hairpin_tm=np.float32(r.hairpin_tm), homodimer_tm=np.float32(r.homodimer_tm), dG=np.float32(r.dG)) for r in out[:len(oligos)]]
+
+    def valid_words(self, words, salt=0.05, primer_strand=9e-7, tm_min=50.0, tm_max=75.0, max_hairpin=40.0):
+        """PCR::is_valid without the dimer test for a batch of words, by the validity form of the kernel (one record per
+        word, expansions spelt on the device: the local search's path) -> bool array."""
+        a = np.array([[w[0], w[1]] for w in words], dtype=np.uint64).reshape(-1, 2)
+        out = np.zeros(max(len(words), 1), np.uint8)
+        args = self._targs(salt, primer_strand, tm_min, tm_max, max_hairpin, 0.0)
+        self._check(self.L.pcr_valid_words(self.h, a.ctypes.data, len(words), C.byref(args), out.ctypes.data))
+        return out[:len(words)].astype(bool)
 
     def collect_amplicons(self, pair, threshold=1.0, amp_min=80, amp_max=200, which=TARGET, cap=4096):
         """PCR::collect_unique_amplicons: -> [dict(sequence, begin, end, inner_start, inner_length, orientation)]

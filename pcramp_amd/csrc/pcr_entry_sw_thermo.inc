@@ -740,6 +740,31 @@ int pcr_thermo(pcr_ctx *ctx, const pcr_word128 *oligos, uint32_t n, int check_ho
 	return PCR_OK;
 }
 
+// The validity form (thermo::ThermoValid) as the local search drives it (pcr_optimize.inc: one record per trial word, then
+// run_thermo_valid), for a caller's own words.
+int pcr_valid_words(pcr_ctx *ctx, const pcr_word128 *words, uint32_t n, const pcr_thermo_args *args, uint8_t *valid_out)
+{
+	if(!ctx || !args || (n && (!words || !valid_out))){ g_err = "pcr_valid_words: bad argument"; return PCR_ERR_ARG; }
+	FLUSH(ctx);
+	HIP_TRY(hipSetDevice(ctx->device));
+	std::vector<thermo::Job> recs;
+	std::vector<uint32_t> n_exp;
+	recs.reserve(n); n_exp.reserve(n);
+	for(uint32_t i = 0;i < n;++i){
+		const Planes w = pcrhost::planes_of_word(words[i].w);
+		if(!pcrhost::planes_occupied(w)){ g_err = "pcr_valid_words: empty oligo"; return PCR_ERR_ARG; }
+		if(!append_valid_record(w, args, recs, n_exp)){
+			g_err = "pcr_valid_words: oligo is longer than 32, holds a non-base slot (NucCruc::set_query throws) or has more than 65536 expansions";
+			return (pcrhost::planes_degeneracy(w) > (double)MAX_EXPANSIONS) ? PCR_ERR_CAPACITY : PCR_ERR_ARG;
+		}
+	}
+	std::vector<uint8_t> bad;
+	const int rc = run_thermo_valid(ctx, recs, n_exp, args, bad);
+	if(rc != PCR_OK) return rc;
+	for(uint32_t i = 0;i < n;++i) valid_out[i] = bad[i] ? 0 : 1;
+	return PCR_OK;
+}
+
 int pcr_dimer(pcr_ctx *ctx, const pcr_pair *pairs, uint32_t n, const pcr_thermo_args *args, float *max_tm)
 {
 	if(!ctx || !args || (n && (!pairs || !max_tm))){ g_err = "pcr_dimer: bad argument"; return PCR_ERR_ARG; }
