@@ -551,6 +551,57 @@ typedef struct {
 int64_t pcr_site_tm(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs, float threshold,
 	const pcr_thermo_args *args, float template_strand, uint32_t *oligo_id, pcr_site *out, uint64_t cap);
 
+/* ---- Every oligo-by-oligo dimer of a primer pool */
+
+/* One cell of the pool's dimer matrix: an ordered pair of distinct-oligo ids, reduced over its duplexes (40 bytes). */
+typedef struct {
+	uint32_t query_oligo, target_oligo;   /* distinct-oligo ids (as pcr_pool_products); equal: the homodimer cell */
+	uint32_t n_duplexes;                  /* D(query) * D(target); homodimer cell: D(query) */
+	uint32_t q_expansion, t_expansion;    /* the duplex attaining tm_max, indices in Word::begin()/next() order; homodimer: equal */
+	uint32_t flags;                       /* PCR_DIMER_HOMO = 1u */
+	float    tm_max, tm_min;              /* highest / lowest Tm over the cell's duplexes, degrees C (NucCruc clamps at 0) */
+	float    dH, dS;                      /* of the duplex attaining tm_max */
+} pcr_pool_dimer;
+
+#define PCR_DIMER_HOMO 1u
+#define PCR_DIMER_RULE_POOL  0   /* pcr_assay.cpp:815-852 */
+#define PCR_DIMER_RULE_ASSAY 1   /* pcr_assay.cpp:232-269, valid_pcr.cpp:13 */
+
+/* Which oligos of a pool anneal to each other: the Tm of every ordered pair of the pool's distinct oligos, and of every oligo
+ * with itself.
+ *   Oligo ids.  The pool's 2*n_pool oligo words get distinct ids in order of first appearance, as in pcr_pool_products;
+ * oligo_id[2*n_pool] receives them.  D(x) = Word::degeneracy() of oligo x.
+ *   Cells.  There is a cell for every ordered pair (q, t), 0 <= q, t < n_distinct, in row-major order.  The order matters:
+ * NucCruc::approximate_tm_heterodimer is not symmetric under exchange of query and target (the last bits of Tm, dH and dS
+ * differ for most pairs), so the result is a full matrix, not a triangle.  Off the diagonal the cell's duplexes are
+ * (expansion iq of q) x (expansion it of t), expansions in the order of Word::begin() / next(), duplex iq * D(t) + it (the
+ * reference's loops, query outer), each NucCruc::approximate_tm_heterodimer with query = q's expansion and target = t's
+ * expansion, both spelt 5'->3' as the words hold them.  On the diagonal there is one duplex per expansion,
+ * NucCruc::approximate_tm_homodimer of that expansion, as PCR::is_valid loops (valid_pcr.cpp:34-41); the homodimer is not
+ * the heterodimer of an oligo with itself (the symmetry term changes dS).  Dimers between DIFFERENT expansions of one
+ * degenerate oligo are not formed: the diagonal cell has D(q) duplexes, not D(q)^2.
+ *   Strand concentration, salt = args->salt (only salt and primer_strand of args are read).  PCR_DIMER_RULE_POOL: every
+ * duplex at args->primer_strand, no degeneracy correction -- with it, the maximum of tm_max over the four cells
+ * (a.F, a.R) x (b.F, b.R) decides pcr_multiplex_compatible(a, b) exactly (incompatible iff that maximum >= max_dimer).
+ * PCR_DIMER_RULE_ASSAY: off the diagonal NucCruc's two-concentration rule (nuc_cruc.h:818-838) of primer_strand / D(q) and
+ * primer_strand / D(t) -- with it, tm_max of cell (F, R) is pcr_dimer of the assay (F, R); on the diagonal
+ * primer_strand / D(q), PCR::is_valid's (valid_pcr.cpp:13).
+ *   Reduction.  tm_max and tm_min are taken over the cell's duplexes; q_expansion, t_expansion, dH and dS are those of the
+ * duplex attaining tm_max, the lowest-numbered one on a tie (ties are common: most random pairs melt below 0 C and are
+ * clamped to Tm 0 with different dH).
+ *   Records are the cells with tm_max >= tm_floor, in cell order; tm_floor <= 0 keeps all n_distinct^2 cells.  Returns their
+ * number or a negative error; if it exceeds cap the contents of out are unspecified (cap = 0: count only; with tm_floor > 0
+ * that still runs the thermodynamics).  n_pool = 0 returns 0.
+ *   PCR_ERR_ARG (from the arguments alone, checked before the handle, in this order): null pointers or cap without out;
+ * n_pool > PCR_POOL_MAX_PAIRS; an unknown rule; primer_strand <= 0; salt outside [1e-6, 1]; an oligo that is empty, has a
+ * hole between its ends or more than PCR_SITE_MAX_EXPANSIONS expansions (which keeps every cell within the 65 536 duplexes
+ * of pcr_dimer).  PCR_ERR_CAPACITY (also before the handle) when the pool's duplexes number 2^31 or more.  Then a null
+ * handle.  PCR_ERR_RANGE if a trace-back fails inside the engine.
+ *   Needs no sequence set and no word DB: it runs on a fresh handle, changes nothing other calls read, and is the same on a
+ * handle with a target shard attached (no collective is made). */
+int64_t pcr_pool_dimers(pcr_ctx *ctx, const pcr_pair *pool, uint32_t n_pool, const pcr_thermo_args *args, int rule,
+	float tm_floor, uint32_t *oligo_id, pcr_pool_dimer *out, uint64_t cap);
+
 /* ---- The multiplex compatibility filter of the trial loop (main.cpp:744-803), batched over the trial assays */
 
 typedef struct {

@@ -72,6 +72,14 @@ SITE_DTYPE = np.dtype([("oligo", np.uint32), ("sequence", np.uint32), ("loc5", n
 SITE_NO_TM = 1                                # PCR_SITE_NO_TM
 SITE_MAX_EXPANSIONS = 256                     # PCR_SITE_MAX_EXPANSIONS
 
+# pcr_pool_dimer: one ordered (query oligo, target oligo) cell of a pool's dimer matrix (Screener.pool_dimers)
+POOL_DIMER_DTYPE = np.dtype([("query_oligo", np.uint32), ("target_oligo", np.uint32), ("n_duplexes", np.uint32),
+                             ("q_expansion", np.uint32), ("t_expansion", np.uint32), ("flags", np.uint32),
+                             ("tm_max", np.float32), ("tm_min", np.float32), ("dH", np.float32), ("dS", np.float32)])
+DIMER_HOMO = 1                                # PCR_DIMER_HOMO
+DIMER_RULE_POOL, DIMER_RULE_ASSAY = 0, 1      # PCR_DIMER_RULE_*
+POOL_DIMER_BATCH_JOBS = 1 << 21               # POOL_DIMER_BATCH_JOBS of pcr_pool_dimers.inc: the duplexes melted per batch
+
 
 class SamplerArgs(C.Structure):
     _fields_ = [("primer_min", C.c_int32), ("primer_max", C.c_int32), ("amp_min", C.c_int32), ("amp_max", C.c_int32),
@@ -127,7 +135,7 @@ ABI_SYMBOLS = [
     "pcr_sw_align_words", "pcr_background_match", "pcr_multiplex_match",
     "pcr_thermo", "pcr_valid_words", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
-    "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm",
+    "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats", "pcr_live_resources",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -222,6 +230,9 @@ def load_library():
     L.pcr_site_tm.restype = C.c_int64
     L.pcr_site_tm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.POINTER(ThermoArgs), C.c_float, C.c_void_p,
                               C.c_void_p, C.c_uint64]
+    L.pcr_pool_dimers.restype = C.c_int64
+    L.pcr_pool_dimers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ThermoArgs), C.c_int, C.c_float, C.c_void_p,
+                                  C.c_void_p, C.c_uint64]
     L.pcr_multiplex_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.pcr_multiplex_coverage.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_void_p]
     L.pcr_host_pool_overlaps.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -818,6 +829,50 @@ class Screener:
                                % (int((at < 0).sum()), side))
             out.append(tab["tm_max"][at].astype(np.float32))
         return out[0], out[1]
+
+    def pool_dimers(self, pool, salt=0.05, primer_strand=9e-7, rule="pool", tm_floor=0.0, cap=None):
+        """Which oligos of the pool anneal to each other (pcr_pool_dimers) -> (oligo_id uint32[2 * len(pool)], records:
+        POOL_DIMER_DTYPE array in cell order).
+
+        oligo_id is pool_products' numbering.  A record is one ORDERED (query_oligo, target_oligo) cell: the highest and
+        lowest heterodimer Tm over (expansion of the query) x (expansion of the target), which expansions attain the
+        highest, and its dH / dS; query_oligo == target_oligo (flags & DIMER_HOMO) is the oligo's homodimer, one duplex per
+        expansion.  The matrix is not symmetric in its last bits.  `rule` sets the strand concentration: "pool" is
+        multiplex_compatible's (primer_strand for every duplex: the maximum over the four cells of two assays decides it),
+        "assay" is max_dimer_tm's and is_valid's (primer_strand / degeneracy: cell (F, R) is the assay's dimer Tm).  Records
+        are the cells with tm_max >= tm_floor; tm_floor <= 0 keeps all n_distinct ** 2.  Needs no sequences and no word DB."""
+        rules = {"pool": DIMER_RULE_POOL, "assay": DIMER_RULE_ASSAY, DIMER_RULE_POOL: DIMER_RULE_POOL, DIMER_RULE_ASSAY: DIMER_RULE_ASSAY}
+        if rule not in rules:
+            raise ValueError("pool_dimers: rule must be 'pool' or 'assay'")
+        a = W.pairs_array(pool)
+        ids = np.zeros(max(2 * len(pool), 1), np.uint32)
+        args = self._targs(salt, primer_strand, 0.0, 0.0, 0.0, 0.0)
+        call = lambda out, cap: self.L.pcr_pool_dimers(self.h, a.ctypes.data, len(pool), C.byref(args), rules[rule], float(tm_floor),
+                                                       ids.ctypes.data, out, cap)
+        if cap is None:
+            if tm_floor <= 0:                                              # every cell is a record: the ids tell how many
+                n = call(None, 0)
+                if n < 0:
+                    raise PcrError(_err(self.L))
+                cap = int(n)
+            else:
+                cap = 1 << 16
+        while True:
+            out = np.zeros(max(cap, 1), POOL_DIMER_DTYPE)
+            n = call(out.ctypes.data, cap)
+            if n < 0:
+                raise PcrError(_err(self.L))
+            if n <= cap:
+                return ids[:2 * len(pool)].copy(), out[:n].copy()
+            cap = int(n)                                                   # the count: one retry
+
+    @staticmethod
+    def dimer_matrix(records, n, field="tm_max"):
+        """pool_dimers' records as a dense float32 [n, n] matrix of `field` (row: query oligo, column: target oligo); 0 where
+        there is no record."""
+        m = np.zeros((int(n), int(n)), np.float32)
+        m[records["query_oligo"], records["target_oligo"]] = records[field]
+        return m
 
     def multiplex_load(self, seqs, min_oligo_length=18):
         """The multiplex background keys (main.cpp:989-1001) from amplicon texts -> number of unique keys."""

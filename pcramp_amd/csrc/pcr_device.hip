@@ -28,6 +28,7 @@
 //   k_sw, k_sw_words, k_bg_*, k_mx_* : SeqOverlap Smith-Waterman and the background / multiplex screens (pcr_sw.inc)
 //   thermo::k_thermo_wave  : NucCruc (pcr_thermo.inc)
 //   k_site_tm, k_site_reduce : the same engine over the binding sites of the word DB, jobs built on the device (pcr_site_tm.inc)
+//   k_pool_dimer, k_pool_dimer_reduce : the same engine over every ordered oligo pair of a pool, jobs derived from the job number (pcr_pool_dimers.inc)
 // Host side in the same library: pcr_optimize.inc (optimize() batched over trial assays), pcr_sampler.inc, pcr_multiplex.inc,
 // pcr_multiplex_screen.inc, pcr_writers.inc; pcr_exchange.inc: the bitset all-gather over RCCL.
 #include <hip/hip_runtime.h>
@@ -823,6 +824,10 @@ struct pcr_ctx {
 	// the same for the other kernels bench.py prices (PCR_PROF_SW, PCR_PROF_THERMO): every launch while profiling is on
 	std::vector<std::pair<Event, Event> > prof_events_k[PCR_PROF_KERNELS];
 	double prof_ms_k[PCR_PROF_KERNELS] = {0.0, 0.0, 0.0}; uint64_t prof_launches_k[PCR_PROF_KERNELS] = {0, 0, 0};
+	// pcr_pool_dimers (pcr_pool_dimers.inc): oligo table + prefixes + log strands, scan scratch, per-duplex results, per-cell records and the kept ones, keep flags and their scan, error flag.
+	// (Last, so that every member above keeps its place: the screen pass is host-bound and two threads share this struct.)
+	DevBuf<uint8_t> pdim_in, pdim_tmp; DevBuf<float4> pdim_res; DevBuf<pcr_pool_dimer> pdim_rec, pdim_out; DevBuf<uint32_t> pdim_keep, pdim_off, pdim_flag;
+	bool pdim_attr_set = false;
 };
 
 namespace {
@@ -2141,4 +2146,5 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_multiplex_screen.inc"
 #include "pcr_pool.inc"
 #include "pcr_site_tm.inc"
+#include "pcr_pool_dimers.inc"
 #include "pcr_writers.inc"
