@@ -602,6 +602,54 @@ typedef struct {
 int64_t pcr_pool_dimers(pcr_ctx *ctx, const pcr_pair *pool, uint32_t n_pool, const pcr_thermo_args *args, int rule,
 	float tm_floor, uint32_t *oligo_id, pcr_pool_dimer *out, uint64_t cap);
 
+/* ---- Products of a pool with the Tm of their two sites, Tm-floored, and the pool's amplification bitsets at that floor */
+
+/* One product with the duplex Tm of its plus site and of its minus site (48 bytes). */
+typedef struct {
+	uint32_t plus_oligo, minus_oligo, sequence;
+	int32_t  begin, end, inner_start, inner_length;
+	uint32_t intended;                  /* the eight fields of pcr_product, same meaning */
+	float    tm_plus, tm_minus;         /* tm_max of the plus site / of the minus site, degrees C */
+	uint32_t flags;                     /* PCR_PRODUCT_* */
+	uint32_t reserved;                  /* 0 */
+} pcr_product_tm;
+
+#define PCR_PRODUCT_PLUS_NO_TM  1u      /* the plus site is a PCR_SITE_NO_TM site: tm_plus = 0 */
+#define PCR_PRODUCT_MINUS_NO_TM 2u      /* the same for the minus site and tm_minus */
+
+/* Which products of a pool form at an annealing temperature, and which sequences each pool pair still amplifies there: the
+ * records of pcr_pool_products joined on the device with the site Tm of pcr_site_tm, floored, and reduced to bitsets.
+ *   Products.  Exactly the records pcr_pool_products returns for the same handle state, pool, threshold and amplicon range:
+ * the same eight fields, uniqueness and order by (plus_oligo, minus_oligo, sequence, begin, end); oligo_id[2*n_pool] is the
+ * same numbering.  That is: a product joins a plus site (strand 1) of oligo x with a minus site (strand 2) of oligo y on one
+ * sequence, with p3 < m5 (loc3 of the plus site before loc5 of the minus site), amp_min <= m3 - p5 + 1 <= amp_max, the
+ * inner stretch (inner_start = p3 - 3, inner_length = m5 - inner_start + 8, as pcr_amplicon) inside the sequence and free
+ * of EOS; begin = p5, end = m3.
+ *   Tm.  tm_plus is tm_max of the record pcr_site_tm returns for (plus_oligo, sequence, loc5 = begin, strand 1) with the same
+ * args and template_strand, tm_minus that of (minus_oligo, sequence, loc3 = end, strand 2) -- bit for bit: the entry the
+ * target is read from, PCR_SITE_NO_TM, the lowest expansion winning a tie and the two-concentration rule are pcr_site_tm's.
+ * A PCR_SITE_NO_TM site gives Tm 0 and its bit in flags.
+ *   Floor.  A product is kept iff tm_floor <= 0 or min(tm_plus, tm_minus) >= tm_floor (in float).  Records are the kept
+ * products, in order.  Returns their number or a negative error; if it exceeds cap the contents of out are unspecified
+ * (cap = 0: count only).  n_pool = 0 returns 0.
+ *   Bitsets.  bits_fr / bits_rf, either may be NULL: n_pool x pcr_bitset_words(ctx, which) u64 in the bit layout of
+ * pcr_amplify.  Bit s of row i of bits_fr is set iff a kept product has plus_oligo = id(F_i), minus_oligo = id(R_i) and
+ * sequence s; bits_rf the same with plus_oligo = id(R_i), minus_oligo = id(F_i).  Rows are written in full, zeros included,
+ * whenever the call returns >= 0 -- also when the count exceeds cap and with cap = 0; they are reduced on the device from the
+ * join, not from the records.  Pool pairs with the same (F, R) get equal rows; a pair with F = R gets bits_fr = bits_rf.
+ *   The thermodynamics run iff tm_floor > 0, records are written (cap > 0) or a bitset is asked for; otherwise the call is
+ * pcr_pool_products' count.
+ *   PCR_ERR_ARG, from the arguments alone and before the handle, in pcr_site_tm's order: unknown set or PCR_SET_MULTIPLEX;
+ * null pointers or cap without out; n_pool > PCR_POOL_MAX_PAIRS; a negative concentration; salt outside [1e-6, 1]; an oligo
+ * that is empty, has a hole between its ends, more than PCR_SITE_MAX_EXPANSIONS expansions or a zero strand concentration;
+ * then a tm_floor that is not finite; then a null handle.  PCR_ERR_STATE without a word DB; PCR_ERR_CAPACITY for 2^31 or
+ * more sites, (site, expansion) jobs or products; PCR_ERR_RANGE if a trace-back fails inside the engine.  Changes nothing
+ * other calls read.  On a handle with a target shard attached, sequence indices are local to the rank's block and no
+ * collective is made (as pcr_pool_products). */
+int64_t pcr_pool_products_tm(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor,
+	uint32_t *oligo_id, pcr_product_tm *out, uint64_t cap, uint64_t *bits_fr, uint64_t *bits_rf);
+
 /* ---- The multiplex compatibility filter of the trial loop (main.cpp:744-803), batched over the trial assays */
 
 typedef struct {

@@ -80,6 +80,12 @@ DIMER_HOMO = 1                                # PCR_DIMER_HOMO
 DIMER_RULE_POOL, DIMER_RULE_ASSAY = 0, 1      # PCR_DIMER_RULE_*
 POOL_DIMER_BATCH_JOBS = 1 << 21               # POOL_DIMER_BATCH_JOBS of pcr_pool_dimers.inc: the duplexes melted per batch
 
+# pcr_product_tm: a product with the Tm of its two sites (Screener.pool_products_tm)
+PRODUCT_TM_DTYPE = np.dtype([("plus_oligo", np.uint32), ("minus_oligo", np.uint32), ("sequence", np.uint32), ("begin", np.int32),
+                             ("end", np.int32), ("inner_start", np.int32), ("inner_length", np.int32), ("intended", np.uint32),
+                             ("tm_plus", np.float32), ("tm_minus", np.float32), ("flags", np.uint32), ("reserved", np.uint32)])
+PRODUCT_PLUS_NO_TM, PRODUCT_MINUS_NO_TM = 1, 2   # PCR_PRODUCT_*_NO_TM
+
 
 class SamplerArgs(C.Structure):
     _fields_ = [("primer_min", C.c_int32), ("primer_max", C.c_int32), ("amp_min", C.c_int32), ("amp_max", C.c_int32),
@@ -136,6 +142,7 @@ ABI_SYMBOLS = [
     "pcr_thermo", "pcr_valid_words", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers",
+    "pcr_pool_products_tm",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats", "pcr_live_resources",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -230,6 +237,9 @@ def load_library():
     L.pcr_site_tm.restype = C.c_int64
     L.pcr_site_tm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.POINTER(ThermoArgs), C.c_float, C.c_void_p,
                               C.c_void_p, C.c_uint64]
+    L.pcr_pool_products_tm.restype = C.c_int64
+    L.pcr_pool_products_tm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
+                                       C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     L.pcr_pool_dimers.restype = C.c_int64
     L.pcr_pool_dimers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ThermoArgs), C.c_int, C.c_float, C.c_void_p,
                                   C.c_void_p, C.c_uint64]
@@ -829,6 +839,45 @@ class Screener:
                                % (int((at < 0).sum()), side))
             out.append(tab["tm_max"][at].astype(np.float32))
         return out[0], out[1]
+
+    def pool_products_tm(self, pool, threshold=1.0, tm_floor=0.0, salt=0.05, primer_strand=9e-7,
+                         template_strand=0.0, amp_min=80, amp_max=200, which=TARGET, select=False,
+                         bits=False, cap=1 << 16):
+        """Which products the pool forms at an annealing temperature (pcr_pool_products_tm) -> (oligo_id uint32[2 * len(pool)],
+        records: PRODUCT_TM_DTYPE array in pool_products' order), and with bits=True also (fr, rf): uint64
+        [len(pool), bitset_words] each, pcr_amplify's layout.
+
+        The records are pool_products' with tm_plus / tm_minus, the tm_max site_tm reports for the product's plus and
+        minus site (flags & PRODUCT_PLUS_NO_TM / PRODUCT_MINUS_NO_TM: that site was not melted and counts as Tm 0), joined
+        on the device.  tm_floor > 0 keeps the products with min(tm_plus, tm_minus) >= tm_floor.  Bit s of fr[i] says that
+        a kept product with F of pair i in the plus and R in the minus role exists on sequence s; rf[i] the same with the
+        roles exchanged: fr[i] | rf[i] is the thermodynamic counterpart of find_target_match's row.
+        `select` as for pool_products and site_tm: True runs select_words first, "all" runs select_sites (both REPLACE the
+        set's word DB), False reads the DB as it stands."""
+        thr2 = float(np.float32(threshold) * np.float32(threshold))
+        if isinstance(select, str):
+            if select != "all":
+                raise ValueError("pool_products_tm: select must be True, False or 'all'")
+            self.select_sites(pool, thr2, which=which)
+        elif select:
+            self.select_words(pool, thr2, which=which)
+        a = W.pairs_array(pool)
+        ids = np.zeros(max(2 * len(pool), 1), np.uint32)
+        args = self._targs(salt, primer_strand, 0.0, 0.0, 0.0, 0.0)
+        words = int(self.bitset_words(which))
+        fr = np.zeros((len(pool), words), np.uint64) if bits else None
+        rf = np.zeros((len(pool), words), np.uint64) if bits else None
+        while True:
+            out = np.zeros(max(cap, 1), PRODUCT_TM_DTYPE)
+            n = self.L.pcr_pool_products_tm(self.h, which, a.ctypes.data, len(pool), float(threshold), int(amp_min), int(amp_max),
+                                            C.byref(args), float(template_strand), float(tm_floor), ids.ctypes.data,
+                                            out.ctypes.data, cap, fr.ctypes.data if bits else None, rf.ctypes.data if bits else None)
+            if n < 0:
+                raise PcrError(_err(self.L))
+            if n <= cap:
+                rec = out[:n].copy()
+                return (ids[:2 * len(pool)].copy(), rec, fr, rf) if bits else (ids[:2 * len(pool)].copy(), rec)
+            cap = int(n)                                                   # the count: one retry
 
     def pool_dimers(self, pool, salt=0.05, primer_strand=9e-7, rule="pool", tm_floor=0.0, cap=None):
         """Which oligos of the pool anneal to each other (pcr_pool_dimers) -> (oligo_id uint32[2 * len(pool)], records:

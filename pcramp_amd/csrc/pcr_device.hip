@@ -29,6 +29,7 @@
 //   thermo::k_thermo_wave  : NucCruc (pcr_thermo.inc)
 //   k_site_tm, k_site_reduce : the same engine over the binding sites of the word DB, jobs built on the device (pcr_site_tm.inc)
 //   k_pool_dimer, k_pool_dimer_reduce : the same engine over every ordered oligo pair of a pool, jobs derived from the job number (pcr_pool_dimers.inc)
+//   k_item_tm, k_products_join : k_site_tm's Tm per item, and k_pool_join's geometry with the two sites' Tm, the floor and the pool's bit rows (pcr_products_tm.inc)
 // Host side in the same library: pcr_optimize.inc (optimize() batched over trial assays), pcr_sampler.inc, pcr_multiplex.inc,
 // pcr_multiplex_screen.inc, pcr_writers.inc; pcr_exchange.inc: the bitset all-gather over RCCL.
 #include <hip/hip_runtime.h>
@@ -828,6 +829,10 @@ struct pcr_ctx {
 	// (Last, so that every member above keeps its place: the screen pass is host-bound and two threads share this struct.)
 	DevBuf<uint8_t> pdim_in, pdim_tmp; DevBuf<float4> pdim_res; DevBuf<pcr_pool_dimer> pdim_rec, pdim_out; DevBuf<uint32_t> pdim_keep, pdim_off, pdim_flag;
 	bool pdim_attr_set = false;
+	// pcr_pool_products_tm (pcr_products_tm.inc): oligo tables + pair table + intended bitmap, per-entry / per-item counts and offsets, items, job offsets,
+	// per-job results, per-item Tm, the pool's bit rows, records, sort keys and order, error flag.  (After pdim_*, for the same reason.)
+	DevBuf<uint8_t> ptm_in, ptm_tmp; DevBuf<uint32_t> ptm_cnt, ptm_ord, ptm_flag; DevBuf<uint64_t> ptm_eoff, ptm_joff, ptm_ioff, ptm_keys, ptm_bits;
+	DevBuf<uint2> ptm_items; DevBuf<float4> ptm_res; DevBuf<uint2> ptm_item_tm; DevBuf<pcr_product_tm> ptm_rec;
 };
 
 namespace {
@@ -2147,4 +2152,5 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_pool.inc"
 #include "pcr_site_tm.inc"
 #include "pcr_pool_dimers.inc"
+#include "pcr_products_tm.inc"
 #include "pcr_writers.inc"
