@@ -650,6 +650,67 @@ int64_t pcr_pool_products_tm(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, 
 	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor,
 	uint32_t *oligo_id, pcr_product_tm *out, uint64_t cap, uint64_t *bits_fr, uint64_t *bits_rf);
 
+/* ---- Probe hits: which products of a pool a panel's hydrolysis probes bind inside, and which sequences each assay detects */
+
+/* One probe site inside one product (64 bytes). */
+typedef struct {
+	uint32_t plus_oligo, minus_oligo;   /* primer ids, pcr_pool_products' numbering */
+	uint32_t probe;                     /* distinct-probe id (see probe_id) */
+	uint32_t sequence;
+	int32_t  begin, end, inner_start, inner_length;   /* the product, as pcr_product */
+	int32_t  probe_loc5, probe_loc3;    /* the probe site, as pcr_site.loc5 / loc3: loc5 <= loc3 on either strand */
+	uint32_t probe_strand;              /* 1 / 2 as pcr_site.strand */
+	uint32_t intended;                  /* PCR_HIT_PRODUCT_INTENDED | PCR_HIT_PROBE_INTENDED */
+	float    tm_plus, tm_minus, tm_probe;
+	uint32_t flags;                     /* PCR_PRODUCT_PLUS_NO_TM | PCR_PRODUCT_MINUS_NO_TM | PCR_HIT_PROBE_NO_TM */
+} pcr_probe_hit;
+
+#define PCR_HIT_PRODUCT_INTENDED 1u     /* pcr_product.intended: {plus, minus} is a pool pair */
+#define PCR_HIT_PROBE_INTENDED   2u     /* some pool pair i has {F_i, R_i} = {plus, minus} AND P_i = this probe */
+#define PCR_HIT_PROBE_NO_TM      4u     /* the probe site is a PCR_SITE_NO_TM site: tm_probe = 0 */
+#define PCR_NO_PROBE 0xFFFFFFFFu        /* probe_id of a pair without a probe */
+
+/* Which products of a pool a probe binds inside, and which sequences each (F, R, probe) assay of the pool detects: the
+ * products of pcr_pool_products_tm joined on the device with the probes' sites, floored, and reduced to one bitset per assay.
+ *   Oligos.  oligo_id[2*n_pool] is exactly what pcr_pool_products writes for the same pool.  probes[i] is the probe of pair
+ * i; an all-zero word means the pair has none, and probe_id[i] = PCR_NO_PROBE.  The other probe words get ids of their own,
+ * 0 .. n_probe - 1, in order of first appearance: an id space separate from the primers'.  A probe word may equal a primer
+ * word: it is then two oligos, each with its own concentration.  Distinct primers plus distinct probes must number at most
+ * 2*PCR_POOL_MAX_PAIRS.  Probe oligos never take a primer role and primer oligos never take the probe role.
+ *   Products.  pcr_pool_products_tm's products for the same handle state, pool, threshold, amplicon range, args,
+ * template_strand and tm_floor: the eight product fields, tm_plus, tm_minus and the two product NO_TM flags of a record are
+ * bit for bit those of that call's record.
+ *   Probe sites.  The sites pcr_site_tm reports for the panel (P, P) of the distinct probes on the same DB at the same
+ * threshold, with args->salt, primer_strand = probe_strand_conc and the same template_strand: tm_probe is that record's
+ * tm_max, and PCR_SITE_NO_TM becomes PCR_HIT_PROBE_NO_TM with tm_probe = 0.  Sites on both strands count.  The DB must
+ * hold them: fill it with pcr_select_sites over the pool plus one pair (P, P) per probe.
+ *   A hit is a product and a site of any probe of the pool on the same sequence with p3 < probe_loc5 and probe_loc3 < m5,
+ * where p3 = inner_start + 3 is the plus primer's 3' base and m5 = inner_start + inner_length - 8 the minus primer's 5' base
+ * -- the strict non-overlap the two primers obey with each other -- that also passes probe_tm_floor <= 0 or
+ * tm_probe >= probe_tm_floor (in float).
+ *   Records are the hits, unique and sorted by (plus_oligo, minus_oligo, sequence, begin, end, probe, probe_loc5,
+ * probe_strand).  Returns their number or a negative error; if it exceeds cap the contents of out are unspecified (cap = 0:
+ * count only).  n_pool = 0 returns 0.
+ *   detected may be NULL: n_pool x pcr_bitset_words(ctx, which) u64 in the bit layout of pcr_amplify, every row written in
+ * full whenever the call returns >= 0, reduced on the device from the join and not from the records.  Row i of a pair with a
+ * probe: bit s is set iff a hit on sequence s has {plus_oligo, minus_oligo} = {id(F_i), id(R_i)} in either orientation and
+ * probe = probe_id[i].  Row i of a pair without a probe: bits_fr | bits_rf of row i of pcr_pool_products_tm at the same
+ * tm_floor -- such a pair is detected by its product.  Pairs with equal (F, R) and different probes get different rows;
+ * equal triples get equal rows.
+ *   PCR_ERR_ARG, from the arguments alone and before the handle, in this order: unknown set or PCR_SET_MULTIPLEX; null
+ * args, pool, probes, oligo_id or probe_id with n_pool > 0, or cap without out; n_pool > PCR_POOL_MAX_PAIRS; a negative
+ * concentration (probe_strand_conc included); salt outside [1e-6, 1]; a primer that is empty, has a hole between its ends,
+ * more than PCR_SITE_MAX_EXPANSIONS expansions or a zero strand concentration; the same for each probe (from
+ * probe_strand_conc / degeneracy and template_strand); too many distinct oligos; a tm_floor that is not finite; a
+ * probe_tm_floor that is not finite; then a null handle.  PCR_ERR_STATE without a word DB; PCR_ERR_CAPACITY for 2^31 or
+ * more sites, (site, expansion) jobs, products or hits; PCR_ERR_RANGE if a trace-back fails inside the engine.  Changes
+ * nothing other calls read.  On a handle with a target shard attached, sequence indices are local to the rank's block and no
+ * collective is made (as pcr_pool_products). */
+int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, const pcr_word128 *probes, uint32_t n_pool,
+	float threshold, int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float probe_strand_conc, float template_strand,
+	float tm_floor, float probe_tm_floor, uint32_t *oligo_id, uint32_t *probe_id, pcr_probe_hit *out, uint64_t cap,
+	uint64_t *detected);
+
 /* ---- The multiplex compatibility filter of the trial loop (main.cpp:744-803), batched over the trial assays */
 
 typedef struct {

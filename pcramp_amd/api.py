@@ -86,6 +86,14 @@ PRODUCT_TM_DTYPE = np.dtype([("plus_oligo", np.uint32), ("minus_oligo", np.uint3
                              ("tm_plus", np.float32), ("tm_minus", np.float32), ("flags", np.uint32), ("reserved", np.uint32)])
 PRODUCT_PLUS_NO_TM, PRODUCT_MINUS_NO_TM = 1, 2   # PCR_PRODUCT_*_NO_TM
 
+# pcr_probe_hit: one probe site inside one product (Screener.probe_hits)
+PROBE_HIT_DTYPE = np.dtype([("plus_oligo", np.uint32), ("minus_oligo", np.uint32), ("probe", np.uint32), ("sequence", np.uint32),
+                            ("begin", np.int32), ("end", np.int32), ("inner_start", np.int32), ("inner_length", np.int32),
+                            ("probe_loc5", np.int32), ("probe_loc3", np.int32), ("probe_strand", np.uint32), ("intended", np.uint32),
+                            ("tm_plus", np.float32), ("tm_minus", np.float32), ("tm_probe", np.float32), ("flags", np.uint32)])
+HIT_PRODUCT_INTENDED, HIT_PROBE_INTENDED, HIT_PROBE_NO_TM = 1, 2, 4   # PCR_HIT_*
+NO_PROBE = 0xFFFFFFFF                         # PCR_NO_PROBE
+
 
 class SamplerArgs(C.Structure):
     _fields_ = [("primer_min", C.c_int32), ("primer_max", C.c_int32), ("amp_min", C.c_int32), ("amp_max", C.c_int32),
@@ -142,7 +150,7 @@ ABI_SYMBOLS = [
     "pcr_thermo", "pcr_valid_words", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers",
-    "pcr_pool_products_tm",
+    "pcr_pool_products_tm", "pcr_pool_probe_hits",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats", "pcr_live_resources",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -240,6 +248,10 @@ def load_library():
     L.pcr_pool_products_tm.restype = C.c_int64
     L.pcr_pool_products_tm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
                                        C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.pcr_pool_probe_hits.restype = C.c_int64
+    L.pcr_pool_probe_hits.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32,
+                                      C.POINTER(ThermoArgs), C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_uint64, C.c_void_p]
     L.pcr_pool_dimers.restype = C.c_int64
     L.pcr_pool_dimers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ThermoArgs), C.c_int, C.c_float, C.c_void_p,
                                   C.c_void_p, C.c_uint64]
@@ -877,6 +889,53 @@ class Screener:
             if n <= cap:
                 rec = out[:n].copy()
                 return (ids[:2 * len(pool)].copy(), rec, fr, rf) if bits else (ids[:2 * len(pool)].copy(), rec)
+            cap = int(n)                                                   # the count: one retry
+
+    def probe_hits(self, pool, probes, threshold=1.0, tm_floor=0.0, probe_tm_floor=0.0, salt=0.05, primer_strand=9e-7,
+                   probe_strand=2.5e-7, template_strand=0.0, amp_min=80, amp_max=200, which=TARGET, select=False,
+                   bits=False, cap=1 << 16):
+        """Which products of the pool a probe binds inside (pcr_pool_probe_hits) -> (oligo_id uint32[2 * len(pool)], probe_id
+        uint32[len(pool)], records: PROBE_HIT_DTYPE array sorted by (plus_oligo, minus_oligo, sequence, begin, end, probe,
+        probe_loc5, probe_strand)), and with bits=True also detected: uint64 [len(pool), bitset_words], pcr_amplify's layout.
+
+        probes[i] is the probe of pool[i] as a (w0, w1) word; None or (0, 0): the pair has none (probe_id NO_PROBE).  The
+        probes get ids of their own in order of first appearance.  The products are pool_products_tm's at tm_floor (primers at
+        primer_strand); a record is one site of any of the pool's probes strictly between a product's two primers, with
+        tm_probe the tm_max site_tm reports for it at probe_strand, kept if probe_tm_floor <= 0 or tm_probe >=
+        probe_tm_floor.  intended & HIT_PRODUCT_INTENDED: the two primers are a pool pair; & HIT_PROBE_INTENDED: and the probe
+        is that pair's.  detected[i]: the sequences on which pair i's primers (either orientation) form a kept product with
+        pair i's probe inside; for a pair without a probe, the sequences its primers amplify (pool_products_tm's fr | rf).
+        `select`: "all" first runs select_sites over the pool plus (P, P) per distinct probe -- the DB must hold the probes'
+        sites --, True the same with select_words (both REPLACE the set's word DB), False reads the DB as it stands."""
+        if len(probes) != len(pool):
+            raise ValueError("probe_hits: one probe entry (or None) per pool pair")
+        pr = np.zeros((max(len(pool), 1), 2), np.uint64)
+        for i, p in enumerate(probes):
+            if p is not None:
+                pr[i] = (p[0], p[1])
+        thr2 = float(np.float32(threshold) * np.float32(threshold))
+        if isinstance(select, str) or select:
+            if isinstance(select, str) and select != "all":
+                raise ValueError("probe_hits: select must be True, False or 'all'")
+            seen = dict.fromkeys((int(a), int(b)) for a, b in pr.tolist() if a or b)
+            panel = list(pool) + [(p, p) for p in seen]
+            (self.select_sites if isinstance(select, str) else self.select_words)(panel, thr2, which=which)
+        a = W.pairs_array(pool)
+        ids = np.zeros(max(2 * len(pool), 1), np.uint32)
+        pid = np.zeros(max(len(pool), 1), np.uint32)
+        args = self._targs(salt, primer_strand, 0.0, 0.0, 0.0, 0.0)
+        detected = np.zeros((len(pool), int(self.bitset_words(which))), np.uint64) if bits else None
+        while True:
+            out = np.zeros(max(cap, 1), PROBE_HIT_DTYPE)
+            n = self.L.pcr_pool_probe_hits(self.h, which, a.ctypes.data, pr.ctypes.data, len(pool), float(threshold), int(amp_min),
+                                           int(amp_max), C.byref(args), float(probe_strand), float(template_strand), float(tm_floor),
+                                           float(probe_tm_floor), ids.ctypes.data, pid.ctypes.data, out.ctypes.data, cap,
+                                           detected.ctypes.data if bits else None)
+            if n < 0:
+                raise PcrError(_err(self.L))
+            if n <= cap:
+                res = (ids[:2 * len(pool)].copy(), pid[:len(pool)].copy(), out[:n].copy())
+                return res + (detected,) if bits else res
             cap = int(n)                                                   # the count: one retry
 
     def pool_dimers(self, pool, salt=0.05, primer_strand=9e-7, rule="pool", tm_floor=0.0, cap=None):

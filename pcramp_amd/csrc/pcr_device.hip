@@ -30,6 +30,7 @@
 //   k_site_tm, k_site_reduce : the same engine over the binding sites of the word DB, jobs built on the device (pcr_site_tm.inc)
 //   k_pool_dimer, k_pool_dimer_reduce : the same engine over every ordered oligo pair of a pool, jobs derived from the job number (pcr_pool_dimers.inc)
 //   k_item_tm, k_products_join : k_site_tm's Tm per item, and k_pool_join's geometry with the two sites' Tm, the floor and the pool's bit rows (pcr_products_tm.inc)
+//   k_probe_products, k_probe_hits : the kept products of the primers compacted, then a wave per product over the probe items inside it (pcr_probe_hits.inc)
 // Host side in the same library: pcr_optimize.inc (optimize() batched over trial assays), pcr_sampler.inc, pcr_multiplex.inc,
 // pcr_multiplex_screen.inc, pcr_writers.inc; pcr_exchange.inc: the bitset all-gather over RCCL.
 #include <hip/hip_runtime.h>
@@ -833,6 +834,10 @@ struct pcr_ctx {
 	// per-job results, per-item Tm, the pool's bit rows, records, sort keys and order, error flag.  (After pdim_*, for the same reason.)
 	DevBuf<uint8_t> ptm_in, ptm_tmp; DevBuf<uint32_t> ptm_cnt, ptm_ord, ptm_flag; DevBuf<uint64_t> ptm_eoff, ptm_joff, ptm_ioff, ptm_keys, ptm_bits;
 	DevBuf<uint2> ptm_items; DevBuf<float4> ptm_res; DevBuf<uint2> ptm_item_tm; DevBuf<pcr_product_tm> ptm_rec;
+	// pcr_pool_probe_hits (pcr_probe_hits.inc): the same over primers + probes, then the kept products (two item indices and two DB slots each), the hit
+	// counts and offsets per product, the detected rows, hit records, sort keys and order.  (After ptm_*, for the same reason.)
+	DevBuf<uint8_t> pph_in, pph_tmp; DevBuf<uint32_t> pph_cnt, pph_hcnt, pph_ord, pph_flag; DevBuf<uint64_t> pph_eoff, pph_joff, pph_ioff, pph_hoff, pph_keys, pph_bits;
+	DevBuf<uint2> pph_items; DevBuf<float4> pph_res; DevBuf<uint2> pph_item_tm; DevBuf<uint4> pph_prod; DevBuf<pcr_probe_hit> pph_rec;
 };
 
 namespace {
@@ -2153,4 +2158,5 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_site_tm.inc"
 #include "pcr_pool_dimers.inc"
 #include "pcr_products_tm.inc"
+#include "pcr_probe_hits.inc"
 #include "pcr_writers.inc"

@@ -1,0 +1,476 @@
+// Which products of a pool a probe binds inside, and which sequences each (F, R, probe) assay detects (pcr_pool_probe_hits;
+// included by pcr_device.hip after pcr_products_tm.inc, whose item, job and Tm kernels it launches as they are).
+//
+// One oligo table holds the pool's distinct primers (pcr_pool_products' ids 0 .. n_prim - 1) and then its distinct probes
+// (table entry n_prim + probe id); SiteOligoX::log_strand carries each oligo's own concentration.  The (entry, oligo) items,
+// their jobs and item_tm[] are then pcr_pool_products_tm's steps 1-3 over that table.  From there:
+//   4. k_probe_products<false> / <true>: k_products_join's walk, geometry and floor, with primer items only in either role.
+//      The count pass also ORs the bit of every kept product of a pool pair WITHOUT a probe into that pair's row (its row is
+//      pcr_pool_products_tm's fr | rf); the emit pass compacts the kept products: {plus item, minus item, plus slot, minus slot}.
+//   5. k_probe_hits<false> / <true>: one wave per kept product.  A probe site inside it (p3 < loc5, loc3 < m5) lies on an entry
+//      with p3 - 31 < loc < m5 + 31, whichever slots the three oligos occupy in their words; the entries of a segment are sorted
+//      by loc and the items are a CSR over the entries, so those entries' items are ONE contiguous run, found by two bisections.
+//      The lanes stride over the run and test the items that are probes: a product with a dense bucket between its primers costs
+//      its wave more steps, not one thread a cubic loop.  The count pass ORs the bit of every hit of an intended (plus, minus,
+//      probe) into that assay's row; the emit pass places each hit by a ballot prefix at the scanned offset (no atomics: where a
+//      record lands does not depend on scheduling).
+//   6. The record order: three stable radix sorts, least significant key first -- (probe, probe_loc5, probe_strand), (begin, end),
+//      (plus_oligo, minus_oligo, sequence) -- and a gather.
+// The call owns its scratch (pcr_ctx::pph_*); the dG table is the handle's (th_dg, keyed by its salt as for every thermo call).
+
+namespace {
+
+struct ProbeAssay { uint64_t key; uint32_t row, pad; };                        // key = (plus*n_prim + minus) << 32 | probe (PCR_NO_PROBE: none) -> the first pool pair that is it, in either orientation
+constexpr int PPH_WAVES = 4;                                                    // waves per block of k_probe_hits
+constexpr uint32_t PPH_NO_ROW = 0xFFFFFFFFu;
+
+// tab[lo].key <= key < tab[above].key -> the row, or PPH_NO_ROW
+__device__ __forceinline__ uint32_t probe_assay_row(const ProbeAssay *__restrict__ tab, uint32_t n_tab, uint64_t key)
+{
+	if(n_tab == 0) return PPH_NO_ROW;
+	uint32_t lo = 0, above = n_tab;
+	while(above - lo > 1u){
+		const uint32_t mid = lo + (above - lo)/2u;
+		if(tab[mid].key <= key) lo = mid; else above = mid;
+	}
+	const ProbeAssay a = tab[lo];
+	return (a.key == key) ? a.row : PPH_NO_ROW;
+}
+
+// k_products_join over the primer items (oligo < n_prim) of a table that also lists probes.  <false>: count[k], and with
+// bits != NULL the bit of every kept product whose (plus, minus) is a pool pair without a probe; <true>: the kept products at
+// prod_off[k] .. as {k, t, plus slot, minus slot}.
+template<bool EMIT>
+__global__ __launch_bounds__(POOL_THREADS) void k_probe_products(const DevEntry *__restrict__ db, uint32_t cap, const uint32_t *__restrict__ touched,
+	const uint32_t *__restrict__ seg_hi, const uint2 *__restrict__ items, uint32_t n_items, const uint64_t *__restrict__ item_off,
+	const PoolOligo *__restrict__ oligos, uint32_t n_ol, uint32_t n_prim, const uint4 *__restrict__ planes, const uint64_t *__restrict__ blk_off,
+	const uint64_t *__restrict__ len, const uint8_t *__restrict__ has_eos, int32_t amp_min, int32_t amp_max,
+	const ItemTm *__restrict__ item_tm, float tm_floor, const uint32_t *__restrict__ intended, const ProbeAssay *__restrict__ tab,
+	uint32_t n_tab, unsigned long long *__restrict__ bits, uint32_t words,
+	uint32_t *__restrict__ count, const uint64_t *__restrict__ prod_off, uint4 *__restrict__ prod)
+{
+	__shared__ int2 ss[POOL_MAX_OLIGOS];                                        // Word::start() / stop()
+	for(uint32_t o = threadIdx.x;o < n_ol;o += blockDim.x) ss[o] = make_int2(oligos[o].start, oligos[o].stop);
+	__syncthreads();
+	const uint32_t k = blockIdx.x*blockDim.x + threadIdx.x;
+	if(k >= n_items) return;
+	const uint2 it = items[k];
+	const uint32_t g = it.x, x = it.y;
+	uint32_t c = 0;
+	uint64_t w = EMIT ? prod_off[k] : 0;
+	if(x < n_prim){                                                             // (a probe takes no primer role)
+		const uint32_t i = touched[g/cap]*cap + g % cap;
+		const DevEntry ei = db[i];
+		if(ei.strand == 1){
+			const uint32_t hi = seg_hi[ei.seq];
+			const int32_t L = (int32_t)len[ei.seq];
+			const uint64_t blk_base = blk_off[ei.seq];
+			const bool eos = has_eos[ei.seq] != 0;
+			const int2 P = ss[x];
+			const int32_t p5 = ei.loc + P.x, p3 = ei.loc + P.y;                  // template_loc5/3, sequence.h:57-75
+			const ItemTm tp = item_tm[k];
+			const bool floored = tm_floor > 0.0f;
+			if(!(floored && tp.tm < tm_floor)){                                  // (a plus site below the floor keeps no product)
+				for(uint32_t j = i + 1;j < hi;++j){
+					const DevEntry ej = db[j];
+					if(ej.loc - ei.loc > amp_max + 128) break;
+					if(ej.strand != 2) continue;
+					const uint32_t gj = g + (j - i);                             // same segment: consecutive DB threads
+					const uint64_t t_end = item_off[gj + 1];
+					for(uint64_t t = item_off[gj];t < t_end;++t){
+						const uint32_t y = items[t].y;
+						if(y >= n_prim) continue;
+						const int2 M = ss[y];
+						const int32_t m5 = ej.loc - M.y, m3 = ej.loc - M.x;
+						if(p3 >= m5) continue;                                   // pcr_assay.cpp:468-471
+						const int32_t amp_len = m3 - p5 + 1;
+						if(amp_len < amp_min || amp_len > amp_max) continue;     // :477-484
+						const int32_t in_start = p3 + 1 - 4;                     // :489-490
+						const int32_t in_len = m5 - in_start + 8;                // :492-494
+						if(in_start < 0 || in_len < 0 || in_start + in_len > L) continue;
+						if(eos && has_split(planes, blk_base, in_start, in_len)) continue;   // :504-521
+						const ItemTm tm = item_tm[t];
+						if(floored && !(((tp.tm < tm.tm) ? tp.tm : tm.tm) >= tm_floor)) continue;   // min(tm_plus, tm_minus) >= tm_floor
+						if(EMIT) prod[w++] = make_uint4(k, (uint32_t)t, i, j);
+						else{
+							++c;
+							const uint32_t b = x*n_prim + y;
+							if(bits && ((intended[b >> 5] >> (b & 31)) & 1u)){
+								const uint32_t row = probe_assay_row(tab, n_tab, ((uint64_t)b << 32) | PCR_NO_PROBE);
+								if(row != PPH_NO_ROW) atomicOr(bits + (size_t)row*words + (ei.seq >> 6), 1ull << (ei.seq & 63u));
+							}
+						}
+					}
+				}
+			}
+		}
+	}
+	if(!EMIT) count[k] = c;
+}
+
+// first slot of [lo, hi) whose loc >= v (the entries of a segment are sorted by loc)
+__device__ __forceinline__ uint32_t probe_lower_bound(const DevEntry *__restrict__ db, uint32_t lo, uint32_t hi, int32_t v)
+{
+	while(lo < hi){
+		const uint32_t mid = lo + (hi - lo)/2u;
+		if(db[mid].loc < v) lo = mid + 1u; else hi = mid;
+	}
+	return lo;
+}
+
+// One wave per kept product p = {k, t, i, j}: the probe items on the entries with p3 - 31 < loc < m5 + 31 of its segment.
+// <false>: count[p], and with bits != NULL the bit of every hit whose (plus, minus, probe) is an assay of the pool;
+// <true>: the records, their first sort key and identity indices at rec_off[p] ..
+template<bool EMIT>
+__global__ __launch_bounds__(64*PPH_WAVES) void k_probe_hits(const DevEntry *__restrict__ db, uint32_t cap, const uint32_t *__restrict__ seg_hi,
+	const uint2 *__restrict__ items, const uint64_t *__restrict__ item_off, const PoolOligo *__restrict__ oligos, uint32_t n_ol, uint32_t n_prim,
+	const uint4 *__restrict__ prod, uint32_t n_prod, const ItemTm *__restrict__ item_tm, float probe_tm_floor,
+	const uint32_t *__restrict__ intended, const ProbeAssay *__restrict__ tab, uint32_t n_tab, unsigned long long *__restrict__ bits, uint32_t words,
+	uint32_t *__restrict__ count, const uint64_t *__restrict__ rec_off, pcr_probe_hit *__restrict__ rec, uint64_t *__restrict__ key,
+	uint32_t *__restrict__ ord)
+{
+	__shared__ int2 ss[POOL_MAX_OLIGOS];                                        // Word::start() / stop()
+	for(uint32_t o = threadIdx.x;o < n_ol;o += blockDim.x) ss[o] = make_int2(oligos[o].start, oligos[o].stop);
+	__syncthreads();
+	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;   // (uniform: the product's loads and both bisections run once per wave)
+	const unsigned long long below = (1ull << lane) - 1ull;
+	for(uint32_t p = blockIdx.x*PPH_WAVES + wave;p < n_prod;p += gridDim.x*PPH_WAVES){   // uniform per wave
+		const uint4 pr = prod[p];
+		const uint2 ik = items[pr.x], itm = items[pr.y];
+		const uint32_t x = ik.y, y = itm.y;
+		const DevEntry ei = db[pr.z], ej = db[pr.w];
+		const int2 P = ss[x], M = ss[y];
+		const int32_t p5 = ei.loc + P.x, p3 = ei.loc + P.y, m5 = ej.loc - M.y, m3 = ej.loc - M.x;
+		const uint32_t seg_lo = ei.seq*cap, hi = seg_hi[ei.seq];
+		// slots e_lo .. e_hi - 1: p3 - 31 < loc < m5 + 31; their items are item_off[g(e_lo)] .. item_off[g(e_hi)] - 1
+		const uint32_t e_lo = probe_lower_bound(db, seg_lo, hi, p3 - 30), e_hi = probe_lower_bound(db, e_lo, hi, m5 + 31);
+		const uint32_t g0 = ik.x - (pr.z - seg_lo);                               // DB thread of the segment's first slot
+		const uint64_t t_lo = item_off[g0 + (e_lo - seg_lo)], t_hi = item_off[g0 + (e_hi - seg_lo)];
+		const uint32_t b = x*n_prim + y;
+		uint32_t c = 0;
+		uint64_t w = EMIT ? rec_off[p] : 0;
+		for(uint64_t base = t_lo;base < t_hi;base += 64){                         // (uniform trip count: the ballots below are the whole wave's)
+			const uint64_t t = base + lane;
+			bool hit = false;
+			uint32_t q = 0, strand = 0;
+			int32_t loc5 = 0, loc3 = 0;
+			ItemTm tq; tq.tm = 0.0f; tq.no_tm = 0;
+			if(t < t_hi){
+				const uint2 iq = items[t];
+				if(iq.y >= n_prim){                                                // (a primer takes no probe role)
+					q = iq.y - n_prim;
+					const DevEntry e = db[seg_lo + (iq.x - g0)];
+					const int2 Q = ss[iq.y];
+					strand = e.strand;
+					loc5 = (strand == 1) ? e.loc + Q.x : e.loc - Q.y;               // sequence.h:57-75
+					loc3 = (strand == 1) ? e.loc + Q.y : e.loc - Q.x;
+					if(p3 < loc5 && loc3 < m5){
+						tq = item_tm[t];
+						hit = !(probe_tm_floor > 0.0f) || tq.tm >= probe_tm_floor;
+					}
+				}
+			}
+			const unsigned long long mask = __ballot(hit);
+			if(EMIT){
+				if(hit){
+					const uint64_t at = w + (uint64_t)__popcll(mask & below);
+					const ItemTm tp = item_tm[pr.x], tm = item_tm[pr.y];
+					pcr_probe_hit r;
+					r.plus_oligo = x; r.minus_oligo = y; r.probe = q; r.sequence = ei.seq;
+					r.begin = p5; r.end = m3; r.inner_start = p3 + 1 - 4; r.inner_length = m5 - r.inner_start + 8;
+					r.probe_loc5 = loc5; r.probe_loc3 = loc3; r.probe_strand = strand;
+					r.intended = (((intended[b >> 5] >> (b & 31)) & 1u) ? PCR_HIT_PRODUCT_INTENDED : 0u)
+						| ((probe_assay_row(tab, n_tab, ((uint64_t)b << 32) | q) != PPH_NO_ROW) ? PCR_HIT_PROBE_INTENDED : 0u);
+					r.tm_plus = tp.tm; r.tm_minus = tm.tm; r.tm_probe = tq.tm;
+					r.flags = (tp.no_tm ? PCR_PRODUCT_PLUS_NO_TM : 0u) | (tm.no_tm ? PCR_PRODUCT_MINUS_NO_TM : 0u) | (tq.no_tm ? PCR_HIT_PROBE_NO_TM : 0u);
+					rec[at] = r;
+					key[at] = ((uint64_t)q << 33) | ((uint64_t)((uint32_t)loc5 ^ 0x80000000u) << 1) | (strand - 1u);   // signed order
+					ord[at] = (uint32_t)at;
+				}
+				w += (uint64_t)__popcll(mask);
+			}
+			else{
+				c += (uint32_t)__popcll(mask);
+				if(hit && bits && ((intended[b >> 5] >> (b & 31)) & 1u)){
+					const uint32_t row = probe_assay_row(tab, n_tab, ((uint64_t)b << 32) | q);
+					if(row != PPH_NO_ROW) atomicOr(bits + (size_t)row*words + (ei.seq >> 6), 1ull << (ei.seq & 63u));
+				}
+			}
+		}
+		if(!EMIT && lane == 0) count[p] = c;
+	}
+}
+
+// the next sort key of the records in their present order; stage 1: (begin, end), stage 2: (plus_oligo, minus_oligo, sequence)
+__global__ void k_probe_key(const pcr_probe_hit *__restrict__ rec, const uint32_t *__restrict__ ord, uint32_t n, int stage, uint32_t seq_bits,
+	uint32_t oligo_bits, uint64_t *__restrict__ key)
+{
+	const uint32_t r = blockIdx.x*blockDim.x + threadIdx.x;
+	if(r >= n) return;
+	const uint32_t at = ord[r];
+	if(stage == 1) key[r] = ((uint64_t)((uint32_t)rec[at].begin ^ 0x80000000u) << 32) | ((uint32_t)rec[at].end ^ 0x80000000u);   // signed order
+	else key[r] = ((uint64_t)rec[at].plus_oligo << (oligo_bits + seq_bits)) | ((uint64_t)rec[at].minus_oligo << seq_bits) | rec[at].sequence;
+}
+
+__global__ void k_probe_gather(const pcr_probe_hit *__restrict__ rec, const uint32_t *__restrict__ ord, uint32_t n, pcr_probe_hit *__restrict__ out)
+{
+	const uint32_t r = blockIdx.x*blockDim.x + threadIdx.x;
+	if(r < n) out[r] = rec[ord[r]];
+}
+
+} // namespace
+
+extern "C" {
+
+int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, const pcr_word128 *probes, uint32_t n_pool,
+	float threshold, int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float probe_strand_conc, float template_strand,
+	float tm_floor, float probe_tm_floor, uint32_t *oligo_id, uint32_t *probe_id, pcr_probe_hit *out, uint64_t cap,
+	uint64_t *detected)
+{
+	static_assert(sizeof(pcr_probe_hit) == 64, "record layout");
+	static_assert(sizeof(ProbeAssay) == 16, "table layout");
+	// ---- the arguments, before the handle (pcr_pool_products_tm's checks in its order, the probes after the primers)
+	if(!set_ok(which)){ g_err = "pcr_pool_probe_hits: unknown sequence set"; return PCR_ERR_ARG; }
+	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = "pcr_pool_probe_hits: PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
+	if(!args || (n_pool && (!pool || !probes || !oligo_id || !probe_id)) || (cap && !out)){ g_err = "pcr_pool_probe_hits: bad argument"; return PCR_ERR_ARG; }
+	if(n_pool > PCR_POOL_MAX_PAIRS){ g_err = "pcr_pool_probe_hits: pool larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
+	if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f) || !(probe_strand_conc >= 0.0f)){ g_err = "pcr_pool_probe_hits: negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
+	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = "pcr_pool_probe_hits: salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
+	// the distinct primers in order of first appearance (as pcr_pool_products), then the distinct probes in theirs
+	std::vector<PoolOligo> ol;
+	std::vector<SiteOligoX> olx;
+	const float thr2 = threshold*threshold;                                      // pcr_assay.cpp:775-776
+	// one oligo of either kind -> its table entry; false: g_err says why it is refused
+	auto add_oligo = [&](const pcr_word128 &wd, float conc, const char *what) -> bool {
+		OligoDev d; fill_oligo(d, wd.w, thr2);
+		const uint32_t occ = pcrhost::planes_occupied(d.m);
+		if(!occ || __builtin_popcount(occ) != d.stop - d.start + 1){
+			g_err = std::string("pcr_pool_probe_hits: a ") + what + " is empty or has a hole between its ends (NucCruc::set_query throws)"; return false;
+		}
+		const double degen = pcrhost::planes_degeneracy(d.m);
+		if(degen > (double)PCR_SITE_MAX_EXPANSIONS){ g_err = std::string("pcr_pool_probe_hits: a ") + what + " has more than PCR_SITE_MAX_EXPANSIONS expansions"; return false; }
+		PoolOligo p; p.m = d.m; p.floor2 = d.floor2; p.start = d.start; p.stop = d.stop; p.pad = 0;
+		const float ca = (float)(conc/degen), cb = template_strand;
+		const float strand = (ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca;              // nuc_cruc.h:832-837
+		if(!(strand > 0.0f)){ g_err = std::string("pcr_pool_probe_hits: the strand concentration of a ") + what + "'s duplex is zero (its concentration / degeneracy and template_strand both 0)"; return false; }
+		SiteOligoX x; x.n_exp = (uint32_t)degen;
+		x.log_strand = logf(strand);
+		ol.push_back(p); olx.push_back(x);
+		return true;
+	};
+	std::map<std::pair<uint64_t, uint64_t>, uint32_t> id_of, probe_of;
+	for(uint32_t s = 0;s < 2*n_pool;++s){
+		const pcr_word128 &wd = (s & 1) ? pool[s/2].r : pool[s/2].f;
+		auto ins = id_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)id_of.size()));
+		if(ins.second && !add_oligo(wd, args->primer_strand, "primer")) return PCR_ERR_ARG;
+		oligo_id[s] = ins.first->second;
+	}
+	const uint32_t n_prim = (uint32_t)ol.size();
+	for(uint32_t i = 0;i < n_pool;++i){
+		const pcr_word128 &wd = probes[i];
+		if(!wd.w[0] && !wd.w[1]){ probe_id[i] = PCR_NO_PROBE; continue; }
+		auto ins = probe_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)probe_of.size()));
+		if(ins.second && !add_oligo(wd, probe_strand_conc, "probe")) return PCR_ERR_ARG;
+		probe_id[i] = ins.first->second;
+	}
+	if(ol.size() > POOL_MAX_OLIGOS){ g_err = "pcr_pool_probe_hits: too many distinct oligos (primers plus probes over 2*PCR_POOL_MAX_PAIRS)"; return PCR_ERR_ARG; }
+	if(!std::isfinite(tm_floor)){ g_err = "pcr_pool_probe_hits: tm_floor is not finite"; return PCR_ERR_ARG; }
+	if(!std::isfinite(probe_tm_floor)){ g_err = "pcr_pool_probe_hits: probe_tm_floor is not finite"; return PCR_ERR_ARG; }
+	if(!ctx){ g_err = "pcr_pool_probe_hits: null handle"; return PCR_ERR_ARG; }
+	{ const int drc = drain(ctx); if(drc != PCR_OK) return drc; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	SeqSet &S = ctx->sets[which];
+	if(!S.have_db){ g_err = "pcr_pool_probe_hits: no word DB (call pcr_select_sites over the pool and its probes first)"; return PCR_ERR_STATE; }
+	if(n_pool == 0) return 0;
+	const uint32_t words = (uint32_t)((S.n + 63)/64);
+	const size_t row_words = (size_t)n_pool*words;
+	// whatever the count, the rows asked for are written in full
+	auto zero_rows = [&](){ if(detected) memset(detected, 0, row_words*sizeof(uint64_t)); };
+	{ const int erc = ensure_touched(ctx, S); if(erc != PCR_OK) return erc; }
+	if(S.n_entries == 0 || S.n_touched == 0){ zero_rows(); return 0; }
+	const uint32_t n_ol = (uint32_t)ol.size();
+	// the intended bitmap over the primers, and (plus, minus, probe) -> the row of the first pool pair that is it in either orientation
+	std::vector<uint32_t> intended(((size_t)n_prim*n_prim + 31)/32, 0);
+	std::map<uint64_t, uint32_t> row_of;
+	std::vector<uint32_t> first_row(n_pool);
+	for(uint32_t i = 0;i < n_pool;++i){
+		const uint32_t f = oligo_id[2*i], r = oligo_id[2*i + 1];
+		for(uint32_t b : {f*n_prim + r, r*n_prim + f}){
+			intended[b >> 5] |= 1u << (b & 31);
+			first_row[i] = row_of.insert(std::make_pair(((uint64_t)b << 32) | probe_id[i], i)).first->second;   // (both orientations were inserted together: one row)
+		}
+	}
+	std::vector<ProbeAssay> tab;
+	tab.reserve(row_of.size());
+	for(const auto &kv : row_of){ ProbeAssay a; a.key = kv.first; a.row = kv.second; a.pad = 0; tab.push_back(a); }   // (key order)
+	int rc;
+	const size_t ol_bytes = ol.size()*sizeof(PoolOligo), tab_bytes = tab.size()*sizeof(ProbeAssay), olx_bytes = olx.size()*sizeof(SiteOligoX),
+		int_bytes = intended.size()*sizeof(uint32_t);
+	std::vector<uint8_t> blob(ol_bytes + tab_bytes + olx_bytes + int_bytes);     // 32-, 16-, 8- and 4-byte records, in that order: each is aligned
+	memcpy(blob.data(), ol.data(), ol_bytes);
+	memcpy(blob.data() + ol_bytes, tab.data(), tab_bytes);
+	memcpy(blob.data() + ol_bytes + tab_bytes, olx.data(), olx_bytes);
+	memcpy(blob.data() + ol_bytes + tab_bytes + olx_bytes, intended.data(), int_bytes);
+	if((rc = ctx->pph_in.ensure(blob.size())) != PCR_OK) return rc;
+	const PoolOligo *d_ol = (const PoolOligo *)ctx->pph_in.p;
+	const ProbeAssay *d_tab = (const ProbeAssay *)(ctx->pph_in.p + ol_bytes);
+	const SiteOligoX *d_olx = (const SiteOligoX *)(ctx->pph_in.p + ol_bytes + tab_bytes);
+	const uint32_t *d_intended = (const uint32_t *)(ctx->pph_in.p + ol_bytes + tab_bytes + olx_bytes);
+	const uint32_t n_tab = (uint32_t)tab.size();
+	HIP_TRY(hipMemcpyAsync(ctx->pph_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+	// ---- 1. the items (k_pool_entry_oligos: count, scan, fill)
+	const uint32_t n_db = S.n_touched*S.db_cap;
+	if((rc = ctx->pph_cnt.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
+	if((rc = ctx->pph_eoff.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->pph_cnt.p + n_db, 0, sizeof(uint32_t), ctx->stream));
+	size_t tmp = 0;
+	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pph_cnt.p, ctx->pph_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	if((rc = ctx->pph_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
+	const unsigned grid_e = std::min<unsigned>((n_db + POOL_THREADS - 1)/POOL_THREADS, ctx->n_cu*8);
+	hipLaunchKernelGGL(k_pool_entry_oligos<false>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
+		S.d_seg_hi, S.d_active.p, d_ol, n_ol, ctx->pph_cnt.p, (const uint64_t *)nullptr, (uint2 *)nullptr);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(rocprim::exclusive_scan(ctx->pph_tmp.p, tmp, ctx->pph_cnt.p, ctx->pph_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	uint64_t n_items = 0;
+	HIP_TRY(hipMemcpyAsync(&n_items, ctx->pph_eoff.p + n_db, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));                                   // (blob is read by now)
+	if(n_items >= POOL_MAX_ITEMS){ g_err = "pcr_pool_probe_hits: too many (entry, oligo) hits"; return PCR_ERR_CAPACITY; }
+	if(n_items == 0){ zero_rows(); return 0; }
+	if((rc = ctx->pph_items.ensure(n_items)) != PCR_OK) return rc;
+	hipLaunchKernelGGL(k_pool_entry_oligos<true>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
+		S.d_seg_hi, S.d_active.p, d_ol, n_ol, (uint32_t *)nullptr, (const uint64_t *)ctx->pph_eoff.p, ctx->pph_items.p);
+	HIP_TRY(hipGetLastError());
+	const uint32_t ni = (uint32_t)n_items;
+	const unsigned grid_i = (ni + POOL_THREADS - 1)/POOL_THREADS;
+	if((rc = ctx->pph_cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;         // (the entry counts are spent)
+	if((rc = ctx->pph_flag.ensure(1)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->pph_flag.p, 0, sizeof(uint32_t), ctx->stream));
+	// ---- 2. job offsets, the jobs (k_site_jobs, k_site_tm as they stand)
+	if((rc = ctx->pph_joff.ensure((size_t)ni + 1)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->pph_cnt.p + ni, 0, sizeof(uint32_t), ctx->stream));
+	hipLaunchKernelGGL(k_site_jobs, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint2 *)ctx->pph_items.p, ni, d_olx, ctx->pph_cnt.p);
+	HIP_TRY(hipGetLastError());
+	tmp = 0;
+	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pph_cnt.p, ctx->pph_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	if((rc = ctx->pph_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
+	HIP_TRY(rocprim::exclusive_scan(ctx->pph_tmp.p, tmp, ctx->pph_cnt.p, ctx->pph_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	uint64_t n_jobs64 = 0;
+	HIP_TRY(hipMemcpyAsync(&n_jobs64, ctx->pph_joff.p + ni, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if(n_jobs64 >= POOL_MAX_ITEMS){ g_err = "pcr_pool_probe_hits: too many (site, expansion) jobs"; return PCR_ERR_CAPACITY; }
+	const uint32_t n_jobs = (uint32_t)n_jobs64;
+	if((rc = ctx->th_dg.ensure(49*49)) != PCR_OK) return rc;
+	if(ctx->th_dg_salt != args->salt){                                             // the dG table depends on the salt only: the handle keeps it between calls
+		int dg[49*49];
+		build_dg_table(args->salt, dg);
+		HIP_TRY(hipMemcpyAsync(ctx->th_dg.p, dg, sizeof(dg), hipMemcpyHostToDevice, ctx->stream));
+		HIP_TRY(hipStreamSynchronize(ctx->stream));                                 // dg[] is a stack array
+		ctx->th_dg_salt = args->salt;
+	}
+	if(!ctx->site_attr_set){                                                       // (k_site_tm's own flag: the attribute is the kernel's)
+		HIP_TRY(hipFuncSetAttribute((const void *)k_site_tm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SITE_LDS));
+		ctx->site_attr_set = true;
+	}
+	if((rc = ctx->pph_res.ensure(n_jobs)) != PCR_OK) return rc;
+	if((rc = ctx->pph_item_tm.ensure(ni)) != PCR_OK) return rc;
+	// at most one block per CU (a block takes most of a CU's LDS), the waves striding over the jobs
+	const unsigned grid_j = std::max(1u, std::min<unsigned>((n_jobs + SITE_WAVES - 1)/SITE_WAVES, (unsigned)ctx->n_cu));
+	hipLaunchKernelGGL(k_site_tm, dim3(grid_j), dim3(SITE_THREADS), SITE_LDS, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
+		(const uint2 *)ctx->pph_items.p, ni, (const uint64_t *)ctx->pph_joff.p, n_jobs, d_ol, d_olx, (const int *)ctx->th_dg.p, logf(args->salt), ctx->pph_res.p);
+	HIP_TRY(hipGetLastError());
+	// ---- 3. Tm per item
+	hipLaunchKernelGGL(k_item_tm, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint64_t *)ctx->pph_joff.p, ni,
+		(const float4 *)ctx->pph_res.p, (ItemTm *)ctx->pph_item_tm.p, ctx->pph_flag.p);
+	HIP_TRY(hipGetLastError());
+	const ItemTm *d_item_tm = (const ItemTm *)ctx->pph_item_tm.p;                 // (the handle keeps it as uint2: the struct is pcr_products_tm.inc's)
+	// ---- 4. the kept products: count (and the rows of the pairs without a probe), scan, compact
+	unsigned long long *d_bits = nullptr;
+	if(detected){
+		if((rc = ctx->pph_bits.ensure(row_words)) != PCR_OK) return rc;
+		HIP_TRY(hipMemsetAsync(ctx->pph_bits.p, 0, row_words*sizeof(uint64_t), ctx->stream));
+		d_bits = (unsigned long long *)ctx->pph_bits.p;
+	}
+	if((rc = ctx->pph_ioff.ensure((size_t)ni + 1)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->pph_cnt.p + ni, 0, sizeof(uint32_t), ctx->stream));
+	hipLaunchKernelGGL(k_probe_products<false>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
+		ctx->pph_items.p, ni, (const uint64_t *)ctx->pph_eoff.p, d_ol, n_ol, n_prim, S.planes.p, S.d_blk_off.p, S.d_len.p, S.d_has_eos.p,
+		amp_min, amp_max, d_item_tm, tm_floor, d_intended, d_tab, n_tab, d_bits, words,
+		ctx->pph_cnt.p, (const uint64_t *)nullptr, (uint4 *)nullptr);
+	HIP_TRY(hipGetLastError());
+	tmp = 0;
+	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pph_cnt.p, ctx->pph_ioff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	if((rc = ctx->pph_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
+	HIP_TRY(rocprim::exclusive_scan(ctx->pph_tmp.p, tmp, ctx->pph_cnt.p, ctx->pph_ioff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	uint64_t n_prod64 = 0;
+	HIP_TRY(hipMemcpyAsync(&n_prod64, ctx->pph_ioff.p + ni, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if(n_prod64 >= POOL_MAX_ITEMS){ g_err = "pcr_pool_probe_hits: too many products"; return PCR_ERR_CAPACITY; }
+	const uint32_t np = (uint32_t)n_prod64;
+	uint64_t total = 0;
+	unsigned grid_p = 0;
+	if(np){
+		if((rc = ctx->pph_prod.ensure(np)) != PCR_OK) return rc;
+		hipLaunchKernelGGL(k_probe_products<true>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
+			ctx->pph_items.p, ni, (const uint64_t *)ctx->pph_eoff.p, d_ol, n_ol, n_prim, S.planes.p, S.d_blk_off.p, S.d_len.p, S.d_has_eos.p,
+			amp_min, amp_max, d_item_tm, tm_floor, d_intended, d_tab, n_tab, (unsigned long long *)nullptr, words,
+			(uint32_t *)nullptr, (const uint64_t *)ctx->pph_ioff.p, ctx->pph_prod.p);
+		HIP_TRY(hipGetLastError());
+		// ---- 5. the hits: a wave per product; count (and the rows of the pairs with a probe), scan
+		if((rc = ctx->pph_hcnt.ensure((size_t)np + 1)) != PCR_OK) return rc;
+		if((rc = ctx->pph_hoff.ensure((size_t)np + 1)) != PCR_OK) return rc;
+		HIP_TRY(hipMemsetAsync(ctx->pph_hcnt.p + np, 0, sizeof(uint32_t), ctx->stream));
+		grid_p = std::min<unsigned>((np + PPH_WAVES - 1)/PPH_WAVES, ctx->n_cu*8);
+		hipLaunchKernelGGL(k_probe_hits<false>, dim3(grid_p), dim3(64*PPH_WAVES), 0, ctx->stream, S.db.p, S.db_cap, S.d_seg_hi,
+			(const uint2 *)ctx->pph_items.p, (const uint64_t *)ctx->pph_eoff.p, d_ol, n_ol, n_prim, (const uint4 *)ctx->pph_prod.p, np, d_item_tm, probe_tm_floor,
+			d_intended, d_tab, n_tab, d_bits, words, ctx->pph_hcnt.p, (const uint64_t *)nullptr, (pcr_probe_hit *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr);
+		HIP_TRY(hipGetLastError());
+		tmp = 0;
+		HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pph_hcnt.p, ctx->pph_hoff.p, uint64_t(0), (size_t)np + 1, rocprim::plus<uint64_t>(), ctx->stream));
+		if((rc = ctx->pph_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
+		HIP_TRY(rocprim::exclusive_scan(ctx->pph_tmp.p, tmp, ctx->pph_hcnt.p, ctx->pph_hoff.p, uint64_t(0), (size_t)np + 1, rocprim::plus<uint64_t>(), ctx->stream));
+		HIP_TRY(hipMemcpyAsync(&total, ctx->pph_hoff.p + np, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	}
+	uint32_t bad = 0;
+	HIP_TRY(hipMemcpyAsync(&bad, ctx->pph_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	if(detected) HIP_TRY(hipMemcpyAsync(detected, ctx->pph_bits.p, row_words*sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if(bad & 1u){ g_err = "pcr_pool_probe_hits: internal trace-back error"; return PCR_ERR_RANGE; }
+	// a pool pair that repeats an earlier assay has that pair's row (the device filled the first copy only)
+	for(uint32_t i = 0;i < n_pool && detected;++i)
+		if(first_row[i] != i) memcpy(detected + (size_t)i*words, detected + (size_t)first_row[i]*words, words*sizeof(uint64_t));
+	if(total >= POOL_MAX_ITEMS){ g_err = "pcr_pool_probe_hits: too many hits"; return PCR_ERR_CAPACITY; }
+	if(total == 0 || total > cap) return (int64_t)total;                         // count only: out is left as it is
+	// ---- 5'. emit at the scanned offsets; 6. the key order
+	const uint32_t nr = (uint32_t)total;
+	if((rc = ctx->pph_rec.ensure(2*(size_t)nr)) != PCR_OK) return rc;
+	if((rc = ctx->pph_keys.ensure(2*(size_t)nr)) != PCR_OK) return rc;
+	if((rc = ctx->pph_ord.ensure(2*(size_t)nr)) != PCR_OK) return rc;
+	pcr_probe_hit *r0 = ctx->pph_rec.p, *r1 = r0 + nr;
+	uint64_t *k0 = ctx->pph_keys.p, *k1 = k0 + nr;
+	uint32_t *o0 = ctx->pph_ord.p, *o1 = o0 + nr;
+	hipLaunchKernelGGL(k_probe_hits<true>, dim3(grid_p), dim3(64*PPH_WAVES), 0, ctx->stream, S.db.p, S.db_cap, S.d_seg_hi,
+		(const uint2 *)ctx->pph_items.p, (const uint64_t *)ctx->pph_eoff.p, d_ol, n_ol, n_prim, (const uint4 *)ctx->pph_prod.p, np, d_item_tm, probe_tm_floor,
+		d_intended, d_tab, n_tab, (unsigned long long *)nullptr, words, (uint32_t *)nullptr, (const uint64_t *)ctx->pph_hoff.p, r0, k0, o0);
+	HIP_TRY(hipGetLastError());
+	const unsigned seq_bits = pool_bits(S.n), oligo_bits = pool_bits(n_prim), probe_bits = pool_bits(n_ol - n_prim);
+	size_t t0 = 0, t1 = 0, t2 = 0;
+	HIP_TRY(rocprim::radix_sort_pairs(nullptr, t0, k0, k1, o0, o1, nr, 0, 33 + probe_bits, ctx->stream));
+	HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, k0, k1, o1, o0, nr, 0, 64, ctx->stream));
+	HIP_TRY(rocprim::radix_sort_pairs(nullptr, t2, k0, k1, o0, o1, nr, 0, 2*oligo_bits + seq_bits, ctx->stream));
+	if((rc = ctx->pph_tmp.ensure(std::max(t0, std::max(t1, t2)) + 16)) != PCR_OK) return rc;
+	const unsigned grid_r = (nr + 255)/256;
+	HIP_TRY(rocprim::radix_sort_pairs(ctx->pph_tmp.p, t0, k0, k1, o0, o1, nr, 0, 33 + probe_bits, ctx->stream));
+	hipLaunchKernelGGL(k_probe_key, dim3(grid_r), dim3(256), 0, ctx->stream, (const pcr_probe_hit *)r0, (const uint32_t *)o1, nr, 1, seq_bits, oligo_bits, k0);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(rocprim::radix_sort_pairs(ctx->pph_tmp.p, t1, k0, k1, o1, o0, nr, 0, 64, ctx->stream));                        // (stable)
+	hipLaunchKernelGGL(k_probe_key, dim3(grid_r), dim3(256), 0, ctx->stream, (const pcr_probe_hit *)r0, (const uint32_t *)o0, nr, 2, seq_bits, oligo_bits, k0);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(rocprim::radix_sort_pairs(ctx->pph_tmp.p, t2, k0, k1, o0, o1, nr, 0, 2*oligo_bits + seq_bits, ctx->stream));   // (stable)
+	hipLaunchKernelGGL(k_probe_gather, dim3(grid_r), dim3(256), 0, ctx->stream, (const pcr_probe_hit *)r0, (const uint32_t *)o1, nr, r1);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out, r1, (size_t)nr*sizeof(pcr_probe_hit), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	return (int64_t)total;
+}
+
+} // extern "C"
