@@ -711,6 +711,57 @@ int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, c
 	float tm_floor, float probe_tm_floor, uint32_t *oligo_id, uint32_t *probe_id, pcr_probe_hit *out, uint64_t cap,
 	uint64_t *detected);
 
+/* ---- Amplicons: the bases of products, their length and G+C, and which records spell one and the same amplicon */
+
+/* What one product record spells (32 bytes). */
+typedef struct {
+	uint32_t length;        /* bases in the region */
+	uint32_t gc;            /* bases whose code is C, G or S (2, 4, 6): only C and/or G possible */
+	uint32_t other;         /* bases whose code is not A, C, G or T: ambiguity codes and EOS (0) */
+	uint32_t flags;         /* PCR_AMPLICON_REVERSED */
+	uint32_t amplicon;      /* class id, 0 .. n_classes-1, classes numbered by first appearance in input order */
+	uint32_t first;         /* index of the first input record of this class */
+	uint32_t copies;        /* input records in this class */
+	uint32_t sequences;     /* distinct `sequence` values among them */
+} pcr_amplicon_info;
+
+#define PCR_AMPLICON_REVERSED 1u
+#define PCR_REGION_PRODUCT 0   /* begin .. end: template bases under both primers included */
+#define PCR_REGION_INSERT  1   /* strictly between the primers: inner_start+4 .. inner_start+inner_length-9 (p3+1 .. m5-1); may be empty */
+#define PCR_REGION_INNER   2   /* inner_start .. inner_start+inner_length-1: the stretch PCR::extract_amplicon_seq cuts */
+
+/* The bases of n product records, read on the device from the loaded set as it stands after every split (no word DB is
+ * needed): per record its length, G+C and the class of records that spell the same bases; per class, on request, the bases.
+ *   Input.  n contiguous pcr_product records, of which only sequence, begin, end, inner_start and inner_length are read: the
+ * records of any of the product calls, of several calls, repeated, in any order, on active sequences or not.
+ *   Region.  The region of record k is an interval of its sequence, chosen by `region` (PCR_REGION_*).  Every position must lie
+ * in 0 .. length of the sequence - 1; only a PCR_REGION_INSERT may be empty (inner_length = 12: p3 + 1 = m5), wherever it is.
+ *   Spelling.  The region's 4-bit codes, 5' -> 3' on the plus strand.  With canonical != 0 it is the smaller of that and its
+ * reverse complement (A <-> T, C <-> G, hence R <-> Y, M <-> K, N -> N, EOS -> EOS), the two compared position by position with
+ * the codes as unsigned integers; flags has PCR_AMPLICON_REVERSED iff the reverse complement is strictly smaller.  length, gc
+ * and other do not depend on the strand.
+ *   Classes.  Two records are in one class iff their spellings are equal: same length, same codes.  Oligo and sequence ids
+ * play no part.  Classes are numbered by first appearance in input order.  The grouping is exact: records are grouped by a
+ * hash on the device, every record is then compared base by base with the first of its group, and those that differ are
+ * grouped by their bytes.  info[k] is written for every record; info may be NULL.
+ *   Unique amplicons.  class_length[c] and class_byte_offset[c] are written for every class if their number is at most
+ * class_cap.  packed4 (may be NULL) receives the spelling of each class -- that of its first record, canonical if asked -- two
+ * codes per byte, high nibble first, an odd tail padded with 0, each class from a byte boundary in class order, if the bytes
+ * needed are at most packed_cap: the triple pcr_load_sequences and pcr_multiplex_load take.  *packed_bytes (may be NULL)
+ * always receives the bytes needed.  Nothing is written past n_classes entries or past the bytes needed; with class_cap
+ * below n_classes, or packed_cap below the bytes needed, that output is left as it is.
+ *   Returns n_classes, or a negative error; info is complete whenever it returns >= 0.  n = 0 returns 0.
+ *   PCR_ERR_ARG, from the arguments alone and before the handle, in this order: unknown set or PCR_SET_MULTIPLEX; NULL
+ * products with n > 0, class_cap > 0 with a NULL class array, or packed_cap > 0 with NULL packed4; unknown region; n >= 2^31;
+ * then a null handle.  PCR_ERR_STATE if the set is not loaded.  With a handle, PCR_ERR_ARG naming the first record whose
+ * sequence or region lies outside the set: checked on the host against the set's lengths before any launch.
+ * PCR_ERR_CAPACITY if the packed output would reach 2^40 bytes.  Changes nothing other calls read.  On a handle with a target
+ * shard attached, sequence indices are local to the rank's block and no collective is made (as pcr_pool_products). */
+int64_t pcr_pool_amplicons(pcr_ctx *ctx, pcr_set which, const pcr_product *products, uint64_t n, int region, int canonical,
+	pcr_amplicon_info *info,
+	uint64_t *class_byte_offset, uint64_t *class_length, uint64_t class_cap,
+	uint8_t *packed4, uint64_t packed_cap, uint64_t *packed_bytes);
+
 /* ---- The multiplex compatibility filter of the trial loop (main.cpp:744-803), batched over the trial assays */
 
 typedef struct {

@@ -94,6 +94,12 @@ PROBE_HIT_DTYPE = np.dtype([("plus_oligo", np.uint32), ("minus_oligo", np.uint32
 HIT_PRODUCT_INTENDED, HIT_PROBE_INTENDED, HIT_PROBE_NO_TM = 1, 2, 4   # PCR_HIT_*
 NO_PROBE = 0xFFFFFFFF                         # PCR_NO_PROBE
 
+# pcr_amplicon_info: what one product record spells (Screener.product_amplicons)
+AMPLICON_INFO_DTYPE = np.dtype([("length", np.uint32), ("gc", np.uint32), ("other", np.uint32), ("flags", np.uint32),
+                                ("amplicon", np.uint32), ("first", np.uint32), ("copies", np.uint32), ("sequences", np.uint32)])
+AMPLICON_REVERSED = 1                         # PCR_AMPLICON_REVERSED
+REGION_PRODUCT, REGION_INSERT, REGION_INNER = 0, 1, 2   # PCR_REGION_*
+
 
 class SamplerArgs(C.Structure):
     _fields_ = [("primer_min", C.c_int32), ("primer_max", C.c_int32), ("amp_min", C.c_int32), ("amp_max", C.c_int32),
@@ -150,7 +156,7 @@ ABI_SYMBOLS = [
     "pcr_thermo", "pcr_valid_words", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers",
-    "pcr_pool_products_tm", "pcr_pool_probe_hits",
+    "pcr_pool_products_tm", "pcr_pool_probe_hits", "pcr_pool_amplicons",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats", "pcr_live_resources",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -252,6 +258,9 @@ def load_library():
     L.pcr_pool_probe_hits.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32,
                                       C.POINTER(ThermoArgs), C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_uint64, C.c_void_p]
+    L.pcr_pool_amplicons.restype = C.c_int64
+    L.pcr_pool_amplicons.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
     L.pcr_pool_dimers.restype = C.c_int64
     L.pcr_pool_dimers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ThermoArgs), C.c_int, C.c_float, C.c_void_p,
                                   C.c_void_p, C.c_uint64]
@@ -937,6 +946,48 @@ class Screener:
                 res = (ids[:2 * len(pool)].copy(), pid[:len(pool)].copy(), out[:n].copy())
                 return res + (detected,) if bits else res
             cap = int(n)                                                   # the count: one retry
+
+    def product_amplicons(self, products, region=REGION_PRODUCT, canonical=False, sequences=False, which=TARGET):
+        """What product records spell (pcr_pool_amplicons) -> info: AMPLICON_INFO_DTYPE array, one per record; with
+        sequences=True -> (info, the unique amplicons as IUPAC texts in class order).
+
+        `products` is any structured array with the fields sequence, begin, end, inner_start and inner_length: the records
+        of pool_products, pool_products_tm or probe_hits, from one call or several, repeated or not.  `region`:
+        REGION_PRODUCT is begin .. end, REGION_INSERT the bases strictly between the primers (may be empty), REGION_INNER
+        the stretch inner_start .. inner_start + inner_length - 1.  The bases are read from the set as loaded and split; no
+        word DB is needed.  info["amplicon"] is the class of records with equal bases (numbered by first appearance),
+        info["first"] its first record, "copies" its records, "sequences" the distinct sequences among them.  canonical=True
+        spells every region as the smaller of itself and its reverse complement (flags & AMPLICON_REVERSED: the latter), so
+        that one amplicon found on either strand is one class.  '-' in a text is an EOS."""
+        src = np.asarray(products)
+        if src.dtype == PRODUCT_DTYPE:
+            rec = np.ascontiguousarray(src)
+        else:
+            rec = np.zeros(len(src), PRODUCT_DTYPE)
+            for f in ("sequence", "begin", "end", "inner_start", "inner_length"):
+                rec[f] = src[f]
+        n = len(rec)
+        info = np.zeros(max(n, 1), AMPLICON_INFO_DTYPE)
+        need = C.c_uint64(0)
+        nc = self.L.pcr_pool_amplicons(self.h, which, rec.ctypes.data if n else None, n, int(region), int(bool(canonical)),
+                                       info.ctypes.data, None, None, 0, None, 0, C.byref(need))
+        if nc < 0:
+            e = PcrError(_err(self.L))
+            e.rc = int(nc)
+            raise e
+        info = info[:n]
+        if not sequences:
+            return info
+        nc, nb = int(nc), int(need.value)
+        off, ln = np.zeros(max(nc, 1), np.uint64), np.zeros(max(nc, 1), np.uint64)
+        packed = np.zeros(max(nb, 1), np.uint8)
+        got = self.L.pcr_pool_amplicons(self.h, which, rec.ctypes.data if n else None, n, int(region), int(bool(canonical)),
+                                        None, off.ctypes.data, ln.ctypes.data, nc, packed.ctypes.data, nb, None)
+        if got < 0:
+            raise PcrError(_err(self.L))
+        assert got == nc
+        texts = [W.text_from_codes(W.unpack_codes(packed[int(off[c]):int(off[c]) + (int(ln[c]) + 1) // 2], int(ln[c]))) for c in range(nc)]
+        return info, texts
 
     def pool_dimers(self, pool, salt=0.05, primer_strand=9e-7, rule="pool", tm_floor=0.0, cap=None):
         """Which oligos of the pool anneal to each other (pcr_pool_dimers) -> (oligo_id uint32[2 * len(pool)], records:

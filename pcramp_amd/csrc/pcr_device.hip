@@ -31,6 +31,7 @@
 //   k_pool_dimer, k_pool_dimer_reduce : the same engine over every ordered oligo pair of a pool, jobs derived from the job number (pcr_pool_dimers.inc)
 //   k_item_tm, k_products_join : k_site_tm's Tm per item, and k_pool_join's geometry with the two sites' Tm, the floor and the pool's bit rows (pcr_products_tm.inc)
 //   k_probe_products, k_probe_hits : the kept products of the primers compacted, then a wave per product over the probe items inside it (pcr_probe_hits.inc)
+//   k_amp_scan, k_amp_verify, k_amp_extract : eight lanes per product record over its bases: G+C, a hash of its spelling, equality with its group's first, the packed text (pcr_pool_amplicons.inc)
 // Host side in the same library: pcr_optimize.inc (optimize() batched over trial assays), pcr_sampler.inc, pcr_multiplex.inc,
 // pcr_multiplex_screen.inc, pcr_writers.inc; pcr_exchange.inc: the bitset all-gather over RCCL.
 #include <hip/hip_runtime.h>
@@ -838,6 +839,11 @@ struct pcr_ctx {
 	// counts and offsets per product, the detected rows, hit records, sort keys and order.  (After ptm_*, for the same reason.)
 	DevBuf<uint8_t> pph_in, pph_tmp; DevBuf<uint32_t> pph_cnt, pph_hcnt, pph_ord, pph_flag; DevBuf<uint64_t> pph_eoff, pph_joff, pph_ioff, pph_hoff, pph_keys, pph_bits;
 	DevBuf<uint2> pph_items; DevBuf<float4> pph_res; DevBuf<uint2> pph_item_tm; DevBuf<uint4> pph_prod; DevBuf<pcr_probe_hit> pph_rec;
+	// pcr_pool_amplicons (pcr_pool_amplicons.inc): the records' intervals, their {gc, other, reversed}, the u32 and u64 arrays carved from one buffer
+	// each (sort keys and order, run starts, representatives, counts, class tables), the info records, scan / sort scratch, the packed spellings.
+	// (After pph_*, for the same reason.)
+	DevBuf<uint4> pam_iv, pam_stat; DevBuf<uint32_t> pam_u32; DevBuf<uint64_t> pam_u64; DevBuf<pcr_amplicon_info> pam_info; DevBuf<uint8_t> pam_tmp, pam_packed;
+	uint32_t amp_dbg_hash_bits = 0;   // PCRAMP_DEBUG_AMP_HASH_BITS=<bits>: pcr_pool_amplicons groups by that many bits of its hash, so that unequal spellings share a key and its resolve path runs (tests)
 };
 
 namespace {
@@ -1490,6 +1496,7 @@ pcr_ctx *pcr_create(int device, void *hip_stream, const pcr_params *params)
 	if(const char *v = getenv("PCRAMP_DEBUG_EPOCH")) ctx->debug_epoch = (uint32_t)strtoul(v, nullptr, 0);   // test hook: start the pass counter near its wrap
 	if(const char *v = getenv("PCRAMP_OPT_PM")) ctx->opt_pm_global = v[0] == 'g';
 	if(const char *v = getenv("PCRAMP_DEBUG_OPT_TASKS")){ unsigned a = 0, b = 0; if(sscanf(v, "%u,%u", &a, &b) >= 1){ ctx->opt_dbg_wg_tasks = a; ctx->opt_dbg_task_cap = b; } }
+	if(const char *v = getenv("PCRAMP_DEBUG_AMP_HASH_BITS")) ctx->amp_dbg_hash_bits = (uint32_t)strtoul(v, nullptr, 0);
 	if(const char *v = getenv("PCRAMP_SEED")) ctx->force_seed1 = v[0] == '1';
 	if(const char *v = getenv("PCRAMP_SEED_TABLES")) ctx->host_seed_tables = v[0] == 'h';
 	if(const char *v = getenv("PCRAMP_S2DBG")) ctx->s2_dbg = (uint32_t)atoi(v);
@@ -2159,4 +2166,5 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_pool_dimers.inc"
 #include "pcr_products_tm.inc"
 #include "pcr_probe_hits.inc"
+#include "pcr_pool_amplicons.inc"
 #include "pcr_writers.inc"
