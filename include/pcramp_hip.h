@@ -762,6 +762,65 @@ int64_t pcr_pool_amplicons(pcr_ctx *ctx, pcr_set which, const pcr_product *produ
 	uint64_t *class_byte_offset, uint64_t *class_length, uint64_t class_cap,
 	uint8_t *packed4, uint64_t packed_cap, uint64_t *packed_bytes);
 
+/* ---- Probe candidates: the oligos that most sequences an assay amplifies hold between its primers */
+
+/* One proposed probe of one assay (64 bytes). */
+typedef struct {
+	pcr_word128 word;            /* the probe, centred as assay oligos are stored: first base at slot (33 - length)/2 */
+	uint32_t group;              /* the assay (caller's group id) */
+	uint32_t length;             /* bases, len_min .. len_max */
+	uint32_t gc;                 /* C + G bases */
+	uint32_t sequences;          /* distinct `sequence` values among the group's records whose insert holds the word */
+	uint32_t records;            /* distinct input records of the group whose insert holds it (twice in one insert: once) */
+	uint32_t first_record;       /* the occurrence lowest in (sequence, record index, loc5, strand): its record index, */
+	int32_t  first_loc5;         /*   the position in the sequence of the window's lowest base (loc3 = loc5 + length - 1), */
+	uint32_t first_strand;       /*   1: the word is the plus strand's text there, 2: its reverse complement is */
+	float tm, hairpin_tm, homodimer_tm, dG;   /* pcr_thermo's for this word; all 0 when args is NULL */
+} pcr_probe_candidate;
+
+#define PCR_PROBE_NO_5G   1u     /* the word's 5' base is not G */
+#define PCR_PROBE_C_GE_G  2u     /* the word has at least as many C as G (picks the strand, with strands = 3) */
+#define PCR_NO_GROUP 0xFFFFFFFFu /* group[] value of a record that takes no part */
+
+/* Per assay, the oligos that occur in the inserts of the products it forms, pass the usual rules of a hydrolysis probe and
+ * melt where a probe must: read on the device from the loaded set as it stands after every split (no word DB is needed).
+ *   Input.  n contiguous pcr_product records, of which only sequence, inner_start and inner_length are read.  group[k] <
+ * PCR_POOL_MAX_PAIRS is the assay of record k; PCR_NO_GROUP: the record takes no part and is not range-checked either; group =
+ * NULL: every record is in group 0.  The region of a record is its PCR_REGION_INSERT (inner_start + 4, inner_length - 12
+ * bases, may be empty), checked as that of the amplicon call above is.
+ *   Occurrences.  For every participating record, every L in len_min .. len_max and every start with the window of L bases
+ * inside the insert: a window all of whose codes are A, C, G or T is kept (one EOS or ambiguity code drops it).  A kept window
+ * gives a strand-1 occurrence of the word spelled as read if strands & 1, and a strand-2 occurrence of its reverse complement if
+ * strands & 2.
+ *   Rules, on the word as oriented (a window may pass on one strand only).  An occurrence counts iff gc_min <= (float)gc /
+ * (float)L <= gc_max compared in float, max_run == 0 or the longest run of one base is at most max_run, and the bits of `rules`
+ * hold (PCR_PROBE_NO_5G, PCR_PROBE_C_GE_G).
+ *   Candidates.  A candidate is a (group, word); occurrences on either strand, in any record of the group, belong to it.
+ * `sequences` and `records` count distinct values, so a reverse-palindromic window -- two occurrences in one record -- counts
+ * once.  A candidate is kept iff sequences >= min_sequences.
+ *   Thermodynamics.  With args != NULL, tm, hairpin_tm, homodimer_tm and dG are bit for bit those pcr_thermo gives for the word
+ * with the same check_homo_dimer and args (args->primer_strand is the probe's concentration), and the candidate is kept iff that
+ * call's `valid` is 1.
+ *   Records are the kept candidates sorted by group, and inside a group by (sequences descending, records descending, length
+ * ascending, text ascending with A < C < G < T); per_group > 0 keeps the first per_group of each group after all filters.
+ * Returns their number or a negative error; if it exceeds cap the contents of out are unspecified (cap = 0: count only).
+ * n = 0 returns 0.
+ *   PCR_ERR_ARG, from the arguments alone and before the handle, in this order: unknown set or PCR_SET_MULTIPLEX; NULL
+ * products with n > 0, or cap without out; n >= 2^31; lengths outside 1 <= len_min <= len_max <= 32; strands not in 1 .. 3;
+ * unknown bits in rules; gc_min or gc_max not finite, or gc_min > gc_max; with args: primer_strand <= 0, or salt outside
+ * [1e-6, 1]; then a null handle.  With a handle: PCR_ERR_ARG for a group value that is neither below PCR_POOL_MAX_PAIRS nor
+ * PCR_NO_GROUP; PCR_ERR_STATE if the set is not loaded (also with n = 0: the state is checked before the count, as in the
+ * amplicon call above); PCR_ERR_ARG naming the first participating record whose sequence or
+ * insert lies outside the set or whose insert is negative in length; PCR_ERR_CAPACITY if the windows to enumerate before the
+ * rules -- the sum over the records and L of max(0, insert - L + 1), times the strands asked for -- number 2^28 or more, added
+ * up on the host before anything is allocated; PCR_ERR_RANGE if a trace-back fails inside the engine.  Changes nothing other
+ * calls read.  On a handle with a target shard attached, sequence indices are local to the rank's block and no collective is
+ * made (as pcr_pool_products). */
+int64_t pcr_pool_probe_candidates(pcr_ctx *ctx, pcr_set which, const pcr_product *products, const uint32_t *group, uint64_t n,
+	uint32_t len_min, uint32_t len_max, uint32_t strands, uint32_t rules, uint32_t max_run, float gc_min, float gc_max,
+	uint32_t min_sequences, const pcr_thermo_args *args, int check_homo_dimer, uint32_t per_group,
+	pcr_probe_candidate *out, uint64_t cap);
+
 /* ---- The multiplex compatibility filter of the trial loop (main.cpp:744-803), batched over the trial assays */
 
 typedef struct {

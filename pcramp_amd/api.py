@@ -100,6 +100,14 @@ AMPLICON_INFO_DTYPE = np.dtype([("length", np.uint32), ("gc", np.uint32), ("othe
 AMPLICON_REVERSED = 1                         # PCR_AMPLICON_REVERSED
 REGION_PRODUCT, REGION_INSERT, REGION_INNER = 0, 1, 2   # PCR_REGION_*
 
+# pcr_probe_candidate: one proposed probe of one assay (Screener.probe_candidates)
+PROBE_CANDIDATE_DTYPE = np.dtype([("word", np.uint64, (2,)), ("group", np.uint32), ("length", np.uint32), ("gc", np.uint32),
+                                  ("sequences", np.uint32), ("records", np.uint32), ("first_record", np.uint32),
+                                  ("first_loc5", np.int32), ("first_strand", np.uint32), ("tm", np.float32),
+                                  ("hairpin_tm", np.float32), ("homodimer_tm", np.float32), ("dG", np.float32)])
+PROBE_NO_5G, PROBE_C_GE_G = 1, 2              # PCR_PROBE_*
+NO_GROUP = 0xFFFFFFFF                         # PCR_NO_GROUP
+
 
 class SamplerArgs(C.Structure):
     _fields_ = [("primer_min", C.c_int32), ("primer_max", C.c_int32), ("amp_min", C.c_int32), ("amp_max", C.c_int32),
@@ -156,7 +164,7 @@ ABI_SYMBOLS = [
     "pcr_thermo", "pcr_valid_words", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers",
-    "pcr_pool_products_tm", "pcr_pool_probe_hits", "pcr_pool_amplicons",
+    "pcr_pool_products_tm", "pcr_pool_probe_hits", "pcr_pool_amplicons", "pcr_pool_probe_candidates",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats", "pcr_live_resources",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -261,6 +269,10 @@ def load_library():
     L.pcr_pool_amplicons.restype = C.c_int64
     L.pcr_pool_amplicons.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.pcr_pool_probe_candidates.restype = C.c_int64
+    L.pcr_pool_probe_candidates.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.POINTER(ThermoArgs), C.c_int,
+                                            C.c_uint32, C.c_void_p, C.c_uint64]
     L.pcr_pool_dimers.restype = C.c_int64
     L.pcr_pool_dimers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ThermoArgs), C.c_int, C.c_float, C.c_void_p,
                                   C.c_void_p, C.c_uint64]
@@ -301,6 +313,17 @@ def load_library():
 
 def _err(L):
     return (L.pcr_last_error() or b"").decode()
+
+
+def best_probes(records, n_groups):
+    """The first record of every group of probe_candidates' records as a (w0, w1) word, None for a group without one: the
+    `probes` list probe_hits takes for a pool of n_groups pairs."""
+    out = [None] * int(n_groups)
+    for r in records:
+        g = int(r["group"])
+        if g < len(out) and out[g] is None:
+            out[g] = (int(r["word"][0]), int(r["word"][1]))
+    return out
 
 
 def live_resources():
@@ -988,6 +1011,60 @@ class Screener:
         assert got == nc
         texts = [W.text_from_codes(W.unpack_codes(packed[int(off[c]):int(off[c]) + (int(ln[c]) + 1) // 2], int(ln[c]))) for c in range(nc)]
         return info, texts
+
+    def probe_candidates(self, products, group=None, pool=None, ids=None, len_min=20, len_max=30, strands=3, no_5g=True,
+                         c_ge_g=True, max_run=4, gc_min=0.3, gc_max=0.8, min_sequences=1, thermo=True, salt=0.05,
+                         probe_strand=2.5e-7, tm_min=65.0, tm_max=75.0, max_hairpin=40.0, max_dimer=40.0,
+                         check_homo_dimer=False, per_group=8, which=TARGET, cap=1 << 16):
+        """Probes proposed from the inserts of product records (pcr_pool_probe_candidates) -> PROBE_CANDIDATE_DTYPE array
+        sorted by group, and inside a group by (sequences descending, records descending, length, text).
+
+        `products` is any structured array with the fields sequence, inner_start and inner_length: the records of
+        pool_products, pool_products_tm or probe_hits.  `group` gives every record its assay (a value below POOL_MAX_PAIRS;
+        NO_GROUP: the record takes no part); with `pool` and `ids` as pool_products took and returned them, a record's
+        group is instead the first pool pair i with {ids[2i], ids[2i + 1]} = {plus_oligo, minus_oligo}, NO_GROUP if there
+        is none; with neither, every record is in group 0.  A candidate is a word of len_min .. len_max bases, all A, C, G
+        or T, that lies inside the insert (the bases strictly between the primers) of a record of the group, on the plus
+        strand (strands & 1) or as its reverse complement (strands & 2), and passes the rules as oriented: no G at the 5'
+        end (no_5g), at least as many C as G (c_ge_g), no run of one base longer than max_run (0: any), gc_min <= gc /
+        length <= gc_max.  `sequences` / `records` count the distinct sequences / records of the group whose insert holds
+        it; candidates with fewer than min_sequences are dropped.  thermo=True melts every candidate as is_valid does at
+        `salt` and probe_strand, fills tm, hairpin_tm, homodimer_tm (with check_homo_dimer) and dG, and keeps those is_valid
+        calls valid for tm_min .. tm_max, max_hairpin and max_dimer.  per_group > 0 keeps the first per_group of each
+        group.  best_probes() turns the result into the probes list of probe_hits.  No word DB is needed."""
+        src = np.asarray(products)
+        rec = np.zeros(len(src), PRODUCT_DTYPE)
+        for f in ("sequence", "inner_start", "inner_length"):
+            rec[f] = src[f]
+        n = len(rec)
+        if pool is not None or ids is not None:
+            if pool is None or ids is None or group is not None:
+                raise ValueError("probe_candidates: pool and ids go together, without group")
+            first = {}
+            for i in range(len(pool)):
+                first.setdefault(frozenset((int(ids[2 * i]), int(ids[2 * i + 1]))), i)
+            group = [first.get(frozenset((int(p), int(m))), NO_GROUP) for p, m in zip(src["plus_oligo"], src["minus_oligo"])]
+        grp = None
+        if group is not None:
+            grp = np.ascontiguousarray(np.asarray(group, np.uint32))
+            if len(grp) != n:
+                raise ValueError("probe_candidates: one group per record")
+        rules = (PROBE_NO_5G if no_5g else 0) | (PROBE_C_GE_G if c_ge_g else 0)
+        args = self._targs(salt, probe_strand, tm_min, tm_max, max_hairpin, max_dimer) if thermo else None
+        while True:
+            out = np.zeros(max(cap, 1), PROBE_CANDIDATE_DTYPE)
+            got = self.L.pcr_pool_probe_candidates(self.h, which, rec.ctypes.data if n else None,
+                                                   grp.ctypes.data if grp is not None and n else None, n, int(len_min), int(len_max),
+                                                   int(strands), rules, int(max_run), float(gc_min), float(gc_max), int(min_sequences),
+                                                   C.byref(args) if thermo else None, int(bool(check_homo_dimer)), int(per_group),
+                                                   out.ctypes.data, cap)
+            if got < 0:
+                e = PcrError(_err(self.L))
+                e.rc = int(got)
+                raise e
+            if got <= cap:
+                return out[:got].copy()
+            cap = int(got)                                                 # the count: one retry
 
     def pool_dimers(self, pool, salt=0.05, primer_strand=9e-7, rule="pool", tm_floor=0.0, cap=None):
         """Which oligos of the pool anneal to each other (pcr_pool_dimers) -> (oligo_id uint32[2 * len(pool)], records:

@@ -844,6 +844,10 @@ struct pcr_ctx {
 	// (After pph_*, for the same reason.)
 	DevBuf<uint4> pam_iv, pam_stat; DevBuf<uint32_t> pam_u32; DevBuf<uint64_t> pam_u64; DevBuf<pcr_amplicon_info> pam_info; DevBuf<uint8_t> pam_tmp, pam_packed;
 	uint32_t amp_dbg_hash_bits = 0;   // PCRAMP_DEBUG_AMP_HASH_BITS=<bits>: pcr_pool_amplicons groups by that many bits of its hash, so that unequal spellings share a key and its resolve path runs (tests)
+	// pcr_pool_probe_candidates (pcr_probe_candidates.inc): the records' inserts, the start positions' offsets + chunk counts and offsets + error flag,
+	// the u32 and u64 arrays carved from one buffer each (occurrences, sort keys and indices, flags and their scans), the candidate and the kept
+	// records, scan / sort scratch.  (After pam_*, for the same reason.)
+	DevBuf<uint4> ppc_iv; DevBuf<uint32_t> ppc_pos, ppc_u32; DevBuf<uint64_t> ppc_u64; DevBuf<pcr_probe_candidate> ppc_rec; DevBuf<uint8_t> ppc_tmp;
 };
 
 namespace {
@@ -2167,4 +2171,5 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_products_tm.inc"
 #include "pcr_probe_hits.inc"
 #include "pcr_pool_amplicons.inc"
+#include "pcr_probe_candidates.inc"
 #include "pcr_writers.inc"

@@ -409,6 +409,38 @@ void build_dg_table(float na, int *dg /* [49*49] */)
 	}
 }
 
+// The engine's dG table for `salt` in ctx->th_dg, which every launch of the engine's kernels reads.  It depends on the salt only: the
+// handle keeps it on the device between calls and rebuilds it when the salt changes.  st: the stream to work on (default: the handle's).
+int ensure_dg_table(pcr_ctx *ctx, float salt, hipStream_t st = nullptr)
+{
+	if(!st) st = ctx->stream;
+	const int rc = ctx->th_dg.ensure(49*49);
+	if(rc != PCR_OK) return rc;
+	if(ctx->th_dg_salt != salt){
+		int dg[49*49];
+		build_dg_table(salt, dg);
+		HIP_TRY(hipMemcpyAsync(ctx->th_dg.p, dg, sizeof(dg), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipStreamSynchronize(st));                                          // dg[] is a stack array
+		ctx->th_dg_salt = salt;
+	}
+	return PCR_OK;
+}
+
+// PCR::is_valid's verdict on one expansion's results, and NucCruc::delta_G of its perfect-match duplex: what pcr_thermo reports,
+// on the host and in the kernels that reduce the verdict on the device (pcr_probe_candidates.inc).  The library is built with
+// -ffp-contract=off: the product and the difference round separately on both sides.
+__host__ __device__ inline bool thermo_expansion_valid(const thermo::JobOut &o, const pcr_thermo_args &a, int check_homo_dimer)
+{
+	if(o.tm_pm < a.tm_min || o.tm_pm > a.tm_max) return false;                    // valid_pcr.cpp:19-23
+	if(o.tm_hairpin > a.max_hairpin) return false;                                // :27-31
+	if(check_homo_dimer && o.tm_dimer > a.max_dimer) return false;                // :34-41
+	return true;
+}
+__host__ __device__ inline float thermo_delta_g(const thermo::JobOut &o)
+{
+	return o.dH_pm - thermo::TARGET_T*o.dS_pm;                                     // nuc_cruc.h:1375-1378 (float product, float difference)
+}
+
 bool job_set(unsigned char *dst, unsigned char &len, const std::vector<uint8_t> &s)
 {
 	if(s.empty() || s.size() > (size_t)thermo::MAXL) return false;
@@ -479,15 +511,8 @@ int run_thermo_jobs(pcr_ctx *ctx, const std::vector<thermo::Job> &jobs_in, float
 	const std::vector<thermo::Job> &jobs = mirror ? jobs_in : split;
 	const size_t n_rec = jobs.size(), n_mirror = mirror ? n_in : 0, n = n_rec + n_mirror;
 	int rc;
-	if((rc = ctx->th_dg.ensure(49*49)) != PCR_OK) return rc;
 	if((rc = ctx->th_out.ensure(n + 1)) != PCR_OK) return rc;                      // + 1: return_to_host copies whole 16-byte units
-	if(ctx->th_dg_salt != salt){                                                   // the dG table depends on the salt only: keep it on the device between calls
-		int dg[49*49];
-		build_dg_table(salt, dg);
-		HIP_TRY(hipMemcpyAsync(ctx->th_dg.p, dg, sizeof(dg), hipMemcpyHostToDevice, ctx->stream));
-		HIP_TRY(hipStreamSynchronize(ctx->stream));                                 // dg[] is a stack array
-		ctx->th_dg_salt = salt;
-	}
+	if((rc = ensure_dg_table(ctx, salt)) != PCR_OK) return rc;
 	const thermo::Job *d_jobs = nullptr;
 	if(n_rec*sizeof(thermo::Job) <= (size_t(16) << 20)){                           // every wave reads its one 72-byte job over the bus
 		const void *p = nullptr;
@@ -552,17 +577,10 @@ int run_thermo_valid(pcr_ctx *ctx, const std::vector<thermo::Job> &recs, const s
 		}
 	}
 	int rc;
-	if((rc = ctx->th_dg.ensure(49*49)) != PCR_OK) return rc;
 	if((rc = ctx->th_jobs.ensure(n_rec)) != PCR_OK) return rc;
 	if((rc = ctx->th_map.ensure(n_jobs)) != PCR_OK) return rc;
 	if((rc = ctx->th_bad.ensure(n_rec + 4)) != PCR_OK) return rc;
-	if(ctx->th_dg_salt != a->salt){
-		int dg[49*49];
-		build_dg_table(a->salt, dg);
-		HIP_TRY(hipMemcpyAsync(ctx->th_dg.p, dg, sizeof(dg), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		ctx->th_dg_salt = a->salt;
-	}
+	if((rc = ensure_dg_table(ctx, a->salt, st)) != PCR_OK) return rc;
 	HIP_TRY(hipMemcpyAsync(ctx->th_jobs.p, recs.data(), n_rec*sizeof(thermo::Job), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(ctx->th_map.p, map.data(), n_jobs*sizeof(uint2), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemsetAsync(ctx->th_bad.p, 0, (n_rec + 4)*sizeof(uint32_t), st));
@@ -724,16 +742,11 @@ int pcr_thermo(pcr_ctx *ctx, const pcr_word128 *oligos, uint32_t n, int check_ho
 		pcr_thermo_result r; memset(&r, 0, sizeof(r));
 		r.n_expansions = first[i + 1] - first[i];
 		r.valid = 1;
-		for(uint32_t k = first[i];k < first[i + 1];++k){
-			const thermo::JobOut &o = res[k];
-			if(o.tm_pm < args->tm_min || o.tm_pm > args->tm_max) r.valid = 0;     // valid_pcr.cpp:19-23
-			if(o.tm_hairpin > args->max_hairpin) r.valid = 0;                     // :27-31
-			if(check_homo_dimer && o.tm_dimer > args->max_dimer) r.valid = 0;     // :34-41
-		}
+		for(uint32_t k = first[i];k < first[i + 1];++k){ if(!thermo_expansion_valid(res[k], *args, check_homo_dimer)) r.valid = 0; }
 		if(r.n_expansions){
 			const thermo::JobOut &o = res[first[i]];
 			r.tm = o.tm_pm; r.dH = o.dH_pm; r.dS = o.dS_pm; r.hairpin_tm = o.tm_hairpin; r.homodimer_tm = o.tm_dimer;
-			r.dG = o.dH_pm - thermo::TARGET_T*o.dS_pm;                            // nuc_cruc.h:1375-1378 (float product, float difference)
+			r.dG = thermo_delta_g(o);
 		}
 		out[i] = r;
 	}

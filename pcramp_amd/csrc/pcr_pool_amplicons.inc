@@ -243,6 +243,26 @@ __global__ __launch_bounds__(64*AMP_WAVES) void k_amp_extract(const uint4 *__res
 	}
 }
 
+// Record k's region as {sequence, start, length, 0} of the set S, checked against the set's lengths (an empty PCR_REGION_INSERT is
+// {sequence, 0, 0, 0} wherever it lies): the one place a product record becomes an interval a kernel may read.  `who` names the
+// entry point in the error text.
+int product_interval(const char *who, const SeqSet &S, const pcr_product &p, uint32_t k, int region, uint4 &iv)
+{
+	if(p.sequence >= S.n){ g_err = std::string(who) + ": record " + std::to_string(k) + ": sequence " + std::to_string(p.sequence) + " is not in the set"; return PCR_ERR_ARG; }
+	int64_t first, len;
+	if(region == PCR_REGION_PRODUCT){ first = p.begin; len = (int64_t)p.end - p.begin + 1; }
+	else if(region == PCR_REGION_INSERT){ first = (int64_t)p.inner_start + 4; len = (int64_t)p.inner_length - 12; }
+	else{ first = p.inner_start; len = p.inner_length; }
+	const bool empty_ok = region == PCR_REGION_INSERT && len == 0;
+	if(!empty_ok && (len <= 0 || first < 0 || (uint64_t)(first + len) > S.len[p.sequence])){
+		g_err = std::string(who) + ": record " + std::to_string(k) + ": region " + std::to_string(first) + " .. " + std::to_string(first + len - 1) +
+			" lies outside sequence " + std::to_string(p.sequence) + " (" + std::to_string(S.len[p.sequence]) + " bases)";
+		return PCR_ERR_ARG;
+	}
+	iv = make_uint4(p.sequence, empty_ok ? 0u : (uint32_t)first, (uint32_t)len, 0u);
+	return PCR_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -269,19 +289,8 @@ int64_t pcr_pool_amplicons(pcr_ctx *ctx, pcr_set which, const pcr_product *produ
 	const uint32_t nr = (uint32_t)n;
 	std::vector<uint4> iv(nr);
 	for(uint32_t k = 0;k < nr;++k){
-		const pcr_product &p = products[k];
-		if(p.sequence >= S.n){ g_err = "pcr_pool_amplicons: record " + std::to_string(k) + ": sequence " + std::to_string(p.sequence) + " is not in the set"; return PCR_ERR_ARG; }
-		int64_t first, len;
-		if(region == PCR_REGION_PRODUCT){ first = p.begin; len = (int64_t)p.end - p.begin + 1; }
-		else if(region == PCR_REGION_INSERT){ first = (int64_t)p.inner_start + 4; len = (int64_t)p.inner_length - 12; }
-		else{ first = p.inner_start; len = p.inner_length; }
-		const bool empty_ok = region == PCR_REGION_INSERT && len == 0;
-		if(!empty_ok && (len <= 0 || first < 0 || (uint64_t)(first + len) > S.len[p.sequence])){
-			g_err = "pcr_pool_amplicons: record " + std::to_string(k) + ": region " + std::to_string(first) + " .. " + std::to_string(first + len - 1) +
-				" lies outside sequence " + std::to_string(p.sequence) + " (" + std::to_string(S.len[p.sequence]) + " bases)";
-			return PCR_ERR_ARG;
-		}
-		iv[k] = make_uint4(p.sequence, empty_ok ? 0u : (uint32_t)first, (uint32_t)len, 0u);
+		const int irc = product_interval("pcr_pool_amplicons", S, products[k], k, region, iv[k]);
+		if(irc != PCR_OK) return irc;
 	}
 	// ---- scratch: u32 and u64 arrays carved from one buffer each
 	int rc;

@@ -275,14 +275,7 @@ int64_t pcr_pool_dimers(pcr_ctx *ctx, const pcr_pair *pool, uint32_t n_pool, con
 	P.log_off = (const float *)(ctx->pdim_in.p + ol_bytes + 2*pre_bytes);
 	P.log_diag = P.log_off + (size_t)n_cls*n_cls;
 	P.n = n; P.n_cls = n_cls;
-	if((rc = ctx->th_dg.ensure(49*49)) != PCR_OK) return rc;
-	if(ctx->th_dg_salt != args->salt){                                             // the dG table depends on the salt only: the handle keeps it between calls
-		int dg[49*49];
-		build_dg_table(args->salt, dg);
-		HIP_TRY(hipMemcpyAsync(ctx->th_dg.p, dg, sizeof(dg), hipMemcpyHostToDevice, ctx->stream));
-		HIP_TRY(hipStreamSynchronize(ctx->stream));                                 // dg[] is a stack array
-		ctx->th_dg_salt = args->salt;
-	}
+	if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
 	if(!ctx->pdim_attr_set){
 		HIP_TRY(hipFuncSetAttribute((const void *)k_pool_dimer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PDIM_LDS));
 		ctx->pdim_attr_set = true;

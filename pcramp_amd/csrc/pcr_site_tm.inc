@@ -329,14 +329,7 @@ int64_t pcr_site_tm(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t
 	if(n_jobs64 >= POOL_MAX_ITEMS){ g_err = "pcr_site_tm: too many (site, expansion) jobs"; return PCR_ERR_CAPACITY; }
 	const uint32_t n_jobs = (uint32_t)n_jobs64;
 	// ---- 3. the jobs
-	if((rc = ctx->th_dg.ensure(49*49)) != PCR_OK) return rc;
-	if(ctx->th_dg_salt != args->salt){                                             // the dG table depends on the salt only: the handle keeps it between calls
-		int dg[49*49];
-		build_dg_table(args->salt, dg);
-		HIP_TRY(hipMemcpyAsync(ctx->th_dg.p, dg, sizeof(dg), hipMemcpyHostToDevice, ctx->stream));
-		HIP_TRY(hipStreamSynchronize(ctx->stream));                                 // dg[] is a stack array
-		ctx->th_dg_salt = args->salt;
-	}
+	if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
 	if(!ctx->site_attr_set){
 		HIP_TRY(hipFuncSetAttribute((const void *)k_site_tm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SITE_LDS));
 		ctx->site_attr_set = true;
