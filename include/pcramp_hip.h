@@ -372,7 +372,14 @@ typedef struct {
  * each by sequence, plus site, minus site) an amplicon with an odd index >= the set's sequence count is
  * never scored.  With evaluate_all_amplicons = 0 that is reproduced bit for bit; with 1 every candidate
  * amplicon is scored.  (One case stays ours in both modes: an odd amplicon COUNT below num_seq makes the
- * reference score stale SSE lanes and index past its deque -- undefined there, no extra amplicon here.) */
+ * reference score stale SSE lanes and index past its deque -- undefined there, no extra amplicon here.)
+ * Pairs per call: the pairing kernel holds 8 bytes per pair in the LDS of a workgroup beside about 8 KB of its own,
+ * so a call takes at most (LDS a workgroup of the device may declare - the kernel's own) / 8 pairs: about 19 400
+ * on an MI355X (160 KiB).  More is refused before anything is launched with PCR_ERR_CAPACITY and
+ * "pcr_background_match: too many pairs in one call: at most <N> pairs ..."; bits is untouched and the handle
+ * stays usable.  Split a larger batch.
+ * With PCRAMP_DEBUG set, every attempt of a call writes one "[pcramp] background_match:" line to stderr (form of the
+ * pairing kernel, bucket slots, pairs, list and sub-list capacity, records emitted and kept, overflow, how it ended). */
 int pcr_background_match(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs,
 	const pcr_background_args *args, uint64_t *bits);
 

@@ -1142,6 +1142,20 @@ int orc_session_background_match(orc_session *s, const uint64_t pair[4], float b
 	catch(const char *e){ s->err = e; return -1; }
 }
 
+// The number of candidate amplicons PCR::collect_candidates forms for the pair at collect_threshold (the amp.size() of
+// orc_session_background_match, whose collect threshold is bg_threshold*bg_multiplier); -1: error.
+long orc_session_background_candidates(orc_session *s, const uint64_t pair[4], float collect_threshold, int amp_min, int amp_max)
+{
+	try{
+		const W F = load_word(pair), R = load_word(pair + 2);
+		std::vector<Amplicon> amp;
+		std::map<uint32_t, float> fi, ri;
+		if(!s->keys.empty()) collect_candidates(amp, fi, ri, F, R, *s, collect_threshold, amp_min, amp_max);   // assay.h:411-421
+		return (long)amp.size();
+	}
+	catch(const char *e){ s->err = e; return -1; }
+}
+
 int orc_session_multiplex_match(orc_session *s, const uint64_t pair[4], float bg_threshold, int use_taq_mama,
 	unsigned char *bits_out)
 {

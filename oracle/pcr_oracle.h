@@ -155,6 +155,9 @@ void orc_sw_align_words(const uint64_t q[2], const uint64_t t[2], orc_sw_result 
 // compiled reference); the product implements emulate_index_bug == 0.  See DESIGN.md.
 int orc_session_background_match(orc_session *s, const uint64_t pair[4], float bg_threshold, float bg_multiplier,
 	int amp_min, int amp_max, int use_taq_mama, int emulate_index_bug, unsigned char *bits_out);
+// The number of candidate amplicons PCR::collect_candidates (pcr_assay.cpp:12-69) forms for the pair at collect_threshold
+// (= bg_threshold*bg_multiplier of the call above): the amplicon count that call loops over.  -1: error.
+long orc_session_background_candidates(orc_session *s, const uint64_t pair[4], float collect_threshold, int amp_min, int amp_max);
 // PCR::find_multiplex_background_match (background_match.cpp:168-295): the four oligo
 // orientations against every sequence of the session (no DB needed).
 int orc_session_multiplex_match(orc_session *s, const uint64_t pair[4], float bg_threshold, int use_taq_mama,

@@ -843,6 +843,7 @@ struct pcr_ctx {
 	// each (sort keys and order, run starts, representatives, counts, class tables), the info records, scan / sort scratch, the packed spellings.
 	// (After pph_*, for the same reason.)
 	DevBuf<uint4> pam_iv, pam_stat; DevBuf<uint32_t> pam_u32; DevBuf<uint64_t> pam_u64; DevBuf<pcr_amplicon_info> pam_info; DevBuf<uint8_t> pam_tmp, pam_packed;
+	uint32_t bg_max_pairs = 0;        // pcr_background_match: the largest batch whose oligo geometry k_bg_emit's workgroup can hold in LDS (0: not asked yet)
 	uint32_t amp_dbg_hash_bits = 0;   // PCRAMP_DEBUG_AMP_HASH_BITS=<bits>: pcr_pool_amplicons groups by that many bits of its hash, so that unequal spellings share a key and its resolve path runs (tests)
 	// pcr_pool_probe_candidates (pcr_probe_candidates.inc): the records' inserts, the start positions' offsets + chunk counts and offsets + error flag,
 	// the u32 and u64 arrays carved from one buffer each (occurrences, sort keys and indices, flags and their scans), the candidate and the kept
@@ -1501,6 +1502,7 @@ pcr_ctx *pcr_create(int device, void *hip_stream, const pcr_params *params)
 	if(const char *v = getenv("PCRAMP_OPT_PM")) ctx->opt_pm_global = v[0] == 'g';
 	if(const char *v = getenv("PCRAMP_DEBUG_OPT_TASKS")){ unsigned a = 0, b = 0; if(sscanf(v, "%u,%u", &a, &b) >= 1){ ctx->opt_dbg_wg_tasks = a; ctx->opt_dbg_task_cap = b; } }
 	if(const char *v = getenv("PCRAMP_DEBUG_AMP_HASH_BITS")) ctx->amp_dbg_hash_bits = (uint32_t)strtoul(v, nullptr, 0);
+	if(const char *v = getenv("PCRAMP_DEBUG_AMP_CAP")) ctx->amp_cap = std::max<size_t>(16, (size_t)strtoull(v, nullptr, 0));   // test hook: a small candidate amplicon list, so that its overflow and the repeated pass run (at least one record per sub-list)
 	if(const char *v = getenv("PCRAMP_SEED")) ctx->force_seed1 = v[0] == '1';
 	if(const char *v = getenv("PCRAMP_SEED_TABLES")) ctx->host_seed_tables = v[0] == 'h';
 	if(const char *v = getenv("PCRAMP_S2DBG")) ctx->s2_dbg = (uint32_t)atoi(v);

@@ -155,6 +155,21 @@ int pcr_background_match(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uin
 	HIP_TRY(hipSetDevice(ctx->device));
 	SeqSet &S = ctx->sets[which];
 	if(!S.have_db){ g_err = "pcr_background_match: no word DB (call pcr_select_words first)"; return PCR_ERR_STATE; }
+	// k_bg_emit keeps the batch's oligo geometry in LDS, 8 bytes per pair beside its own arrays (a batch of more than 32 * BGE_MW oligos
+	// runs the <0> form): the batch must fit what a workgroup of this device may declare.  Asked of the runtime once per handle.
+	if(!ctx->bg_max_pairs){
+		int lds_max = 0;
+		hipFuncAttributes fa;
+		HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+		HIP_TRY(hipFuncGetAttributes(&fa, (const void *)k_bg_emit<0>));
+		if(lds_max <= 0 || (size_t)lds_max <= fa.sharedSizeBytes){ g_err = "pcr_background_match: the device reports too little LDS per workgroup"; return PCR_ERR_DEVICE; }
+		HIP_TRY(hipFuncSetAttribute((const void *)k_bg_emit<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)lds_max - fa.sharedSizeBytes)));
+		ctx->bg_max_pairs = (uint32_t)(((size_t)lds_max - fa.sharedSizeBytes)/(2*sizeof(uint32_t)));
+	}
+	if(n_pairs > ctx->bg_max_pairs){
+		g_err = "pcr_background_match: too many pairs in one call: at most " + std::to_string(ctx->bg_max_pairs) + " pairs (the LDS of a workgroup holds the batch's oligo geometry)";
+		return PCR_ERR_CAPACITY;
+	}
 	{ const int erc = ensure_touched(ctx, S); if(erc != PCR_OK) return erc; }
 	const uint64_t words = (S.n + 63)/64;
 	const size_t total = (size_t)n_pairs*words;
@@ -223,7 +238,10 @@ int pcr_background_match(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uin
 		const uint32_t *cnt = (const uint32_t *)back[1];
 		const uint32_t n_amp = cnt[3], flags = cnt[1], status = *(const uint32_t *)back[2];
 		if(status & 1u){ g_err = "Sequence::has_split: range is out of bounds"; return PCR_ERR_RANGE; }
-		if(n_amp > ctx->amp_cap || (cnt[2] & 1u)){
+		const bool repeat = n_amp > ctx->amp_cap || (cnt[2] & 1u);
+		if(ctx->debug_log) fprintf(stderr, "[pcramp] background_match: attempt %d, emit<%d>, %u-slot buckets, %u pairs, list of %zu records in sub-lists of %u, %u records emitted, %u kept, overflow %u: %s\n",
+			attempt, stage, S.db_cap, n_pairs, ctx->amp_cap, sub_cap, n_amp, cnt[0], (unsigned)(cnt[2] & 1u), repeat ? "repeated" : (flags & 2u) ? "ordered path" : "default path");
+		if(repeat){
 			if(n_amp > (1u << 29)){ g_err = "pcr_background_match: candidate amplicon list does not fit"; return PCR_ERR_CAPACITY; }
 			ctx->amp_cap = std::max<size_t>(2*ctx->amp_cap, 2*(size_t)n_amp);            // (a sub-list may overflow before the sum does: twice the room)
 			continue;
@@ -271,6 +289,8 @@ static int candidate_amplicons(pcr_ctx *ctx, SeqSet &S, const pcr_pair *pairs, u
 		HIP_TRY(hipMemcpyAsync(&n_amp, ctx->counters.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(hipMemcpyAsync(&status, ctx->status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(hipStreamSynchronize(ctx->stream));
+		if(ctx->debug_log) fprintf(stderr, "[pcramp] candidate_amplicons: attempt %d, %u pairs, list of %zu records, %u records emitted: %s\n",
+			attempt, n_pairs, ctx->amp_cap, n_amp, (n_amp <= ctx->amp_cap) ? "done" : "repeated");
 		if(n_amp <= ctx->amp_cap) break;
 		if(attempt >= 4 || n_amp > (1u << 29)){ g_err = "candidate amplicon list does not fit"; return PCR_ERR_CAPACITY; }
 		ctx->amp_cap = (size_t)n_amp + (n_amp >> 3);

@@ -239,6 +239,8 @@ class Oracle(_Lib):
         self.lib.orc_session_background_match.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int,
                                                           C.c_int, C.c_int, C.c_int, C.c_void_p]
         self.lib.orc_session_multiplex_match.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]
+        self.lib.orc_session_background_candidates.restype = C.c_long
+        self.lib.orc_session_background_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int]
 
     def sw_align_codes(self, q, t):
         """q, t: uint8 arrays of 4-bit codes -> SWResult."""
@@ -607,6 +609,16 @@ class Session:
         if n < 0:
             raise RuntimeError(self.f("session_error")(self.h))
         return bits, n
+
+    def background_candidates(self, pair, collect_threshold, amp_min=0, amp_max=2000):
+        """The number of candidate amplicons PCR::collect_candidates forms for the pair (oracle only): what
+        background_match loops over at bg_threshold * bg_multiplier == collect_threshold (a float32 product)."""
+        assert isinstance(self.L, Oracle)
+        a = pairs_array([pair])
+        n = self.L.lib.orc_session_background_candidates(self.h, a.ctypes.data, collect_threshold, amp_min, amp_max)
+        if n < 0:
+            raise RuntimeError(self.f("session_error")(self.h))
+        return int(n)
 
     def multiplex_match(self, pair, bg_threshold=0.8, use_taq_mama=0):
         a = pairs_array([pair])

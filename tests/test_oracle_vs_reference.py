@@ -740,3 +740,33 @@ def test_amplicon_edges(oracle, reference, k):
             assert (ob == rb).all()
             compared[w] = compared.get(w, 0) + 1
     assert len(compared) == 2, compared                # every amplicon window compared on at least one pair
+
+
+# ------------------------------------------------------------------------------------ candidate counts of the background screen
+@pytest.mark.parametrize("name", ["class64", "class128", "spill_13_1", "spill_64_5", "hist8192"])
+def test_background_candidate_count(oracle, reference, name):
+    """orc_session_background_candidates (the record count tests/test_gpu_background_lists.py holds the device to) equals the
+    amplicon count the reference's find_background_match loops over, on the rack sets of tests/background_lists.py --
+    wherever the reference returns one (an odd count below the sequence count is its out-of-bounds case); the bits too."""
+    import background_lists as BL
+    c = BL.cases(oracle)[name]
+    so, sr = _sessions(oracle, reference, c.seqs)
+    for s in (so, sr):
+        for i in c.inactive:
+            s.set_active(i, False)
+        for i, pos in c.splits:
+            s.split(i, pos)
+    thr = BL.collect_threshold()
+    assert so.select(c.select, threshold=thr, min_len_override=BL.MIN_LEN) == sr.select(c.select, threshold=thr, min_len_override=BL.MIN_LEN)
+    assert so.db_entries() == sr.db_entries()
+    compared = 0
+    for k, pair in enumerate(c.unique[:c.n_distinct + 40]):
+        rb, n_amp = sr.background_match(pair, BL.BT, BL.MULT, BL.AMP[0], BL.AMP[1], 0)
+        if rb is None:
+            continue
+        assert so.background_candidates(pair, thr, BL.AMP[0], BL.AMP[1]) == n_amp, (name, k)
+        if c.per_pair[k] is not None:
+            assert n_amp == c.per_pair[k], (name, k)
+        assert (so.background_match(pair, BL.BT, BL.MULT, BL.AMP[0], BL.AMP[1], 0, emulate_index_bug=1)[0] == rb).all(), (name, k)
+        compared += 1
+    assert compared >= c.n_distinct
