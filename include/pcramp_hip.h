@@ -558,6 +558,55 @@ typedef struct {
 int64_t pcr_site_tm(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs, float threshold,
 	const pcr_thermo_args *args, float template_strand, uint32_t *oligo_id, pcr_site *out, uint64_t cap);
 
+/* ---- A panel's binding sites grouped by what the template spells there */
+
+/* One distinct spelling of the template under (and beside) one oligo (80 bytes). */
+typedef struct {
+	pcr_word128 word;                   /* planes of the entry pcr_site_tm reads for the site, restricted to T (the oligo's slots and one
+	                                       flanking slot on either side, clipped to 0..31), as a Word: oligo-oriented on both strands */
+	uint32_t oligo;                     /* distinct-oligo id, pcr_pool_products' numbering */
+	uint32_t sites;                     /* sites (pcr_site_tm records) of this oligo that spell it */
+	uint32_t sequences;                 /* distinct `sequence` values among them */
+	uint32_t matches;                   /* as pcr_site.matches (the same for every member) */
+	uint32_t mismatch_mask;             /* bit i: the oligo's slot start+i (i = 0: its 5' base) matches no base of the word there */
+	uint32_t clamp3, clamp5;            /* consecutive matching slots counted from slot stop downwards / from slot start upwards */
+	uint32_t n_expansions;
+	uint32_t flags;                     /* PCR_SITE_NO_TM, pcr_site_tm's rule */
+	uint32_t first_sequence; int32_t first_loc5; uint32_t first_strand;   /* the member lowest in (sequence, loc5, strand) */
+	float    tm_max, tm_min, dH, dS;    /* pcr_site_tm's, bit for bit, for every member; all 0 with args == NULL or NO_TM */
+} pcr_site_variant;
+
+/* A census of a panel's binding sites by what the template spells at them: how many sites and sequences carry each spelling,
+ * where it mismatches the oligo, and -- melted once per spelling, not once per site -- its Tm.
+ *   Sites.  Exactly the records pcr_site_tm returns for the same handle state, `which`, panel and threshold, with the same
+ * entry read where several share a site; oligo_id[2*n_pairs] receives the same ids.
+ *   Variants.  The key of a site is (oligo, the read entry's planes & T), T as at pcr_site_tm.  DB words are oligo-oriented
+ * on both strands, so strand is no part of the key: a strand-1 and a strand-2 site with the same word are one variant.
+ * Two oligos never share a variant; an oligo that occurs several times in the panel is one oligo.  The grouping compares
+ * whole keys (radix sorts, no hash): it is exact.  pcr_site_tm spells both strands of a site's duplex from the oligo and
+ * from those planes alone, so tm_max, tm_min, dH, dS, matches and flags of a variant are, bit for bit, those of every
+ * pcr_site_tm record among its members.  clamp3 / clamp5 equal the oligo's length where nothing mismatches; a slot of the
+ * oligo over an empty slot of the word (a site hanging over a sequence end) counts as a mismatch.
+ *   Thermodynamics.  args != NULL: one duplex per (variant, expansion) by pcr_site_tm's rules (salt, primer_strand /
+ * degeneracy, template_strand, highest Tm with the lowest expansion on a tie).  args == NULL: none is run, the four floats
+ * are 0, template_strand is ignored and the salt and concentration checks are skipped; flags is still computed.
+ *   Records are sorted by oligo ascending, then sequences, sites and matches descending, then the word's slot masks
+ * (A, C, G, T) ascending: a total order.  Returns their number or a negative error; if it exceeds cap the contents of out
+ * are unspecified (cap = 0: count only, no thermodynamics is run).  n_pairs = 0 returns 0.
+ *   site_variant (may be NULL): entry r receives the index in out of the variant of the r-th record of pcr_site_tm's
+ * order (oligo, sequence, loc5, strand); written iff the variants fit cap and the sites fit site_cap.  counts (may be
+ * NULL): counts[0] = the number of sites, written by every successful call; counts[1] = the number of (variant,
+ * expansion) duplexes melted, the sum of n_expansions over the variants, or 0 where no thermodynamics ran.  counts[1] is
+ * at most the sum of n_expansions over pcr_site_tm's records, and equal to it iff no two sites share a variant.
+ *   PCR_ERR_ARG (checked before the handle): pcr_site_tm's refusals in its order, args == NULL being legal; then site_cap > 0
+ * with site_variant == NULL; then a null handle.  PCR_ERR_STATE without a word DB; PCR_ERR_CAPACITY for 2^31 or more sites
+ * or (variant, expansion) duplexes; PCR_ERR_RANGE for an internal trace-back failure.  Changes nothing other calls read.  On
+ * a handle with a target shard attached, sequence indices are local to the rank's block and no collective is made. */
+int64_t pcr_site_variants(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs, float threshold,
+	const pcr_thermo_args *args, float template_strand, uint32_t *oligo_id,
+	pcr_site_variant *out, uint64_t cap,
+	uint32_t *site_variant, uint64_t site_cap, uint64_t counts[2]);
+
 /* ---- Every oligo-by-oligo dimer of a primer pool */
 
 /* One cell of the pool's dimer matrix: an ordered pair of distinct-oligo ids, reduced over its duplexes (40 bytes). */

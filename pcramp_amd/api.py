@@ -72,6 +72,13 @@ SITE_DTYPE = np.dtype([("oligo", np.uint32), ("sequence", np.uint32), ("loc5", n
 SITE_NO_TM = 1                                # PCR_SITE_NO_TM
 SITE_MAX_EXPANSIONS = 256                     # PCR_SITE_MAX_EXPANSIONS
 
+# pcr_site_variant: one distinct spelling of the template under one oligo (Screener.site_variants)
+SITE_VARIANT_DTYPE = np.dtype([("word", np.uint64, (2,)), ("oligo", np.uint32), ("sites", np.uint32), ("sequences", np.uint32),
+                               ("matches", np.uint32), ("mismatch_mask", np.uint32), ("clamp3", np.uint32), ("clamp5", np.uint32),
+                               ("n_expansions", np.uint32), ("flags", np.uint32), ("first_sequence", np.uint32),
+                               ("first_loc5", np.int32), ("first_strand", np.uint32), ("tm_max", np.float32),
+                               ("tm_min", np.float32), ("dH", np.float32), ("dS", np.float32)])
+
 # pcr_pool_dimer: one ordered (query oligo, target oligo) cell of a pool's dimer matrix (Screener.pool_dimers)
 POOL_DIMER_DTYPE = np.dtype([("query_oligo", np.uint32), ("target_oligo", np.uint32), ("n_duplexes", np.uint32),
                              ("q_expansion", np.uint32), ("t_expansion", np.uint32), ("flags", np.uint32),
@@ -164,7 +171,7 @@ ABI_SYMBOLS = [
     "pcr_thermo", "pcr_valid_words", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers",
-    "pcr_pool_products_tm", "pcr_pool_probe_hits", "pcr_pool_amplicons", "pcr_pool_probe_candidates",
+    "pcr_pool_products_tm", "pcr_pool_probe_hits", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats", "pcr_live_resources",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -259,6 +266,9 @@ def load_library():
     L.pcr_site_tm.restype = C.c_int64
     L.pcr_site_tm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.POINTER(ThermoArgs), C.c_float, C.c_void_p,
                               C.c_void_p, C.c_uint64]
+    L.pcr_site_variants.restype = C.c_int64
+    L.pcr_site_variants.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.POINTER(ThermoArgs), C.c_float, C.c_void_p,
+                                    C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
     L.pcr_pool_products_tm.restype = C.c_int64
     L.pcr_pool_products_tm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
                                        C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
@@ -324,6 +334,77 @@ def best_probes(records, n_groups):
         if g < len(out) and out[g] is None:
             out[g] = (int(r["word"][0]), int(r["word"][1]))
     return out
+
+
+def variant_texts(variants):
+    """The oligo-oriented spelling of each site_variants record's word in IUPAC letters, lowest occupied slot to highest
+    (flanks included; read it beside the oligo's own text shifted by one where the 5' flank slot is occupied)."""
+    return [W.word_text((int(r["word"][0]), int(r["word"][1]))) for r in variants]
+
+
+def _slot_planes(slots):
+    return tuple(sum(((int(v) >> b) & 1) << k for k, v in enumerate(slots)) for b in range(4))
+
+
+def merge_variant_flanks(variants, oligos, site_variant=None, sites=None):
+    """site_variants' records with the flanking slots dropped from the key: variants of one oligo that spell the same bases
+    under the oligo's own slots become one record (host side; by then there are thousands of rows, and the device keeps the
+    flanks in its key because the thermodynamics read them).
+
+    oligos: the distinct oligo words indexed by oligo id, or the panel itself ([(F, R), ...]; ids are taken in order of
+    first appearance, as site_variants numbers them).  Per merged record: word = the members' word inside the oligo's slots;
+    sites summed; tm_max the highest with its dH / dS, tm_min the lowest, over the members that were melted; flags keeps
+    SITE_NO_TM only where no member was melted; first_* the lowest member's; matches, mismatch_mask, clamps and n_expansions
+    are the members' common values.  `sequences` cannot be merged from the members' counts (a sequence may carry two of
+    them): pass site_variant (site_variants(..., site_map=True)) and the site_tm records of the same call arguments, or
+    their `sequence` column, and it is counted exactly; without them it is the largest member's count, a lower bound.
+    Records come in site_variants' order."""
+    words = list(oligos)
+    if words and not np.isscalar(words[0][0]):
+        seen = {}
+        for f, r in words:
+            for w in ((int(f[0]), int(f[1])), (int(r[0]), int(r[1]))):
+                seen.setdefault(w, len(seen))
+        words = sorted(seen, key=seen.get)
+    inside = []
+    for w in words:
+        occ = W.slots_from_word(w) != 0
+        inside.append(occ)
+    groups, member_of = {}, np.zeros(len(variants), np.int64)
+    for i, r in enumerate(variants):
+        sl = W.slots_from_word((int(r["word"][0]), int(r["word"][1])))
+        sl = np.where(inside[int(r["oligo"])], sl, 0).astype(np.uint8)
+        key = (int(r["oligo"]), W.word_from_slots(sl))
+        member_of[i] = groups.setdefault(key, len(groups))
+    out = np.zeros(len(groups), SITE_VARIANT_DTYPE)
+    seqs = None
+    if site_variant is not None and sites is not None:
+        col = sites["sequence"] if getattr(sites, "dtype", None) is not None and sites.dtype.names else sites
+        seqs = [set() for _ in groups]
+        for v, s in zip(np.asarray(site_variant).tolist(), np.asarray(col).tolist()):
+            seqs[member_of[v]].add(s)
+    for (oligo, word), g in groups.items():
+        mem = variants[member_of == g]
+        m = out[g]
+        m["word"] = word
+        m["oligo"] = oligo
+        m["sites"] = int(mem["sites"].sum())
+        m["sequences"] = len(seqs[g]) if seqs is not None else int(mem["sequences"].max())
+        for f in ("matches", "mismatch_mask", "clamp3", "clamp5", "n_expansions"):
+            m[f] = mem[f][0]
+        first = min(mem, key=lambda r: (int(r["first_sequence"]), int(r["first_loc5"]), int(r["first_strand"])))
+        for f in ("first_sequence", "first_loc5", "first_strand"):
+            m[f] = first[f]
+        melted = mem[(mem["flags"] & SITE_NO_TM) == 0]
+        if len(melted) == 0:
+            m["flags"] = SITE_NO_TM
+        else:
+            top = melted[int(np.argmax(melted["tm_max"]))]
+            m["tm_max"], m["dH"], m["dS"] = top["tm_max"], top["dH"], top["dS"]
+            m["tm_min"] = melted["tm_min"].min()
+    order = sorted(range(len(out)), key=lambda g: (int(out[g]["oligo"]), -int(out[g]["sequences"]), -int(out[g]["sites"]),
+                                                   -int(out[g]["matches"]), _slot_planes(W.slots_from_word(out[g]["word"]))))
+    return out[order]
 
 
 def live_resources():
@@ -860,6 +941,53 @@ class Screener:
             if n <= cap:
                 return ids[:2 * len(panel)].copy(), out[:n].copy()
             cap = int(n)
+
+    def site_variants(self, panel, threshold=1.0, salt=0.05, primer_strand=9e-7, template_strand=0.0, which=TARGET, select=False,
+                      thermo=True, site_map=False, cap=1 << 16):
+        """site_tm's sites grouped by what the template spells at them (pcr_site_variants) -> (oligo_id uint32[2 *
+        len(panel)], variants: SITE_VARIANT_DTYPE array); with site_map also site_variant uint32[number of sites]: for the
+        r-th record site_tm returns for the same arguments, the index of its variant.
+
+        A variant is one (oligo, template bases under the oligo and on one flanking slot either side) -- both strands
+        together, the word oligo-oriented: `sites` and `sequences` count who carries it, matches / mismatch_mask / clamp3 /
+        clamp5 say where it differs from the oligo (bit i of the mask: the oligo's i-th base from its 5' end), first_* names
+        its lowest member, and tm_max / tm_min / dH / dS are, bit for bit, what site_tm reports for every member -- melted
+        once per variant.  thermo=False melts nothing: the floats are 0 and salt and the concentrations are not read.
+        Variants are sorted by oligo, then sequences, sites and matches descending, then slot masks.  `select` as for
+        site_tm.  variant_texts() spells the words; merge_variant_flanks() drops the flanks from the key."""
+        thr2 = float(np.float32(threshold) * np.float32(threshold))
+        if isinstance(select, str):
+            if select != "all":
+                raise ValueError("site_variants: select must be True, False or 'all'")
+            self.select_sites(panel, thr2, which=which)
+        elif select:
+            self.select_words(panel, thr2, which=which)
+        a = W.pairs_array(panel)
+        ids = np.zeros(max(2 * len(panel), 1), np.uint32)
+        args = C.byref(self._targs(salt, primer_strand, 0.0, 0.0, 0.0, 0.0)) if thermo else None
+        counts = np.zeros(2, np.uint64)
+
+        def call(out, cap, smap, site_cap):
+            n = self.L.pcr_site_variants(self.h, which, a.ctypes.data, len(panel), float(threshold), args, float(template_strand),
+                                         ids.ctypes.data, out.ctypes.data if out is not None else None, cap,
+                                         smap.ctypes.data if smap is not None else None, site_cap, counts.ctypes.data)
+            if n < 0:
+                raise PcrError(_err(self.L))
+            return int(n)
+
+        site_cap = 0
+        if site_map:                                    # the counts first (nothing is melted), so that one full call fits both
+            cap = max(cap, call(None, 0, None, 0))
+            site_cap = int(counts[0])
+        while True:
+            out = np.zeros(max(cap, 1), SITE_VARIANT_DTYPE)
+            smap = np.zeros(max(site_cap, 1), np.uint32) if site_map else None
+            n = call(out, cap, smap, site_cap)
+            if n <= cap and (not site_map or int(counts[0]) <= site_cap):
+                res = (ids[:2 * len(panel)].copy(), out[:n].copy())
+                return res + (smap[:int(counts[0])].copy(),) if site_map else res
+            cap = max(cap, n)
+            site_cap = int(counts[0]) if site_map else 0
 
     @staticmethod
     def product_tm(products, sites):

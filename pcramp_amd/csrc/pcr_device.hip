@@ -28,6 +28,7 @@
 //   k_sw, k_sw_words, k_bg_*, k_mx_* : SeqOverlap Smith-Waterman and the background / multiplex screens (pcr_sw.inc)
 //   thermo::k_thermo_wave  : NucCruc (pcr_thermo.inc)
 //   k_site_tm, k_site_reduce : the same engine over the binding sites of the word DB, jobs built on the device (pcr_site_tm.inc)
+//   k_sv_items, k_sv_heads, k_sv_tm : the sites grouped by (oligo, template planes in the window) with radix sorts over the whole key, one melt per group (pcr_site_variants.inc)
 //   k_pool_dimer, k_pool_dimer_reduce : the same engine over every ordered oligo pair of a pool, jobs derived from the job number (pcr_pool_dimers.inc)
 //   k_item_tm, k_products_join : k_site_tm's Tm per item, and k_pool_join's geometry with the two sites' Tm, the floor and the pool's bit rows (pcr_products_tm.inc)
 //   k_probe_products, k_probe_hits : the kept products of the primers compacted, then a wave per product over the probe items inside it (pcr_probe_hits.inc)
@@ -756,6 +757,10 @@ struct pcr_ctx {
 	// pcr_site_tm (pcr_site_tm.inc): oligo tables, per-entry counts and offsets, items, per-item job offsets, per-job results, sort keys and order, records
 	DevBuf<uint8_t> site_in, site_tmp; DevBuf<uint32_t> site_cnt, site_ord, site_flag; DevBuf<uint64_t> site_eoff, site_joff, site_keys; DevBuf<uint2> site_items; DevBuf<float4> site_res; DevBuf<pcr_site> site_rec;
 	bool site_attr_set = false;
+	// pcr_site_variants (pcr_site_variants.inc; it also uses site_*): what each item spells, the key order, each item's variant, variant starts,
+	// records (key order | record order), the variants' sort keys and orders (+ their rank), the site map
+	DevBuf<uint8_t> sv_item; DevBuf<uint32_t> sv_ord, sv_var, sv_start, sv_vord, sv_map; DevBuf<pcr_site_variant> sv_rec; DevBuf<uint64_t> sv_vkeys;
+	bool sv_attr_set = false;
 	// an attached target shard (pcr_shard_targets, pcr_shard.inc): PCR_SET_TARGET holds rows [shard_first, shard_first + n) of
 	// shard_n_total, and the local search combines target coverage over shard_comm; NULL = not sharded
 	pcr_comm *shard_comm = nullptr; uint64_t shard_first = 0, shard_n_total = 0; int shard_mode = 0;
@@ -2169,6 +2174,7 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_multiplex_screen.inc"
 #include "pcr_pool.inc"
 #include "pcr_site_tm.inc"
+#include "pcr_site_variants.inc"
 #include "pcr_pool_dimers.inc"
 #include "pcr_products_tm.inc"
 #include "pcr_probe_hits.inc"

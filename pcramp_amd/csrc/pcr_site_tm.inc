@@ -88,6 +88,84 @@ __global__ __launch_bounds__(POOL_THREADS) void k_site_jobs(const uint2 *__restr
 // rank of a slot in the odometer of Word::begin() / next() (word.h:525-647): slot 15 turns fastest, then 14 .. 0, then 31 .. 16
 __device__ __forceinline__ unsigned site_rank(unsigned k) { return (k < 16u) ? 15u - k : 47u - k; }
 
+// One duplex: expansion `expansion` of oligo o against the template the planes tw spell inside T.  Wave-uniform arguments; the
+// result (tm, dH, dS, status) is lane 0's.  false: the site cannot be spelled, no DP ran and no wave_sync was passed.
+// (pcr_site_variants melts a variant's planes & T through this: every slot read lies in T.)
+__device__ __forceinline__ bool site_melt(thermo::Engine<1> &e, thermo::WaveSlab &w, unsigned lane, const PoolOligo &o, float log_strand,
+	const Planes &tw, uint32_t T, unsigned expansion, float4 &out)
+{
+	using namespace thermo;
+	int lo, hi;
+	if(!site_stretch(tw, T, lo, hi)){                                              // no DP for a site that cannot be spelled
+		out = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(SITE_ST_NO_TM));
+		return false;
+	}
+	const int qlen = o.stop - o.start + 1, tlen = hi - lo + 1;                     // 1 .. 32 both (the host refuses oligos with holes)
+	e.log_strand = log_strand; e.qlen = qlen; e.tlen = tlen;
+	if(lane <= MAXL){
+		const int i = (int)lane;
+		unsigned char qc = (unsigned char)bE, tc = (unsigned char)bE;             // "one past the end" is the non-pairing code E
+		auto base_set = [&](unsigned s) -> unsigned { return ((o.m.a >> s) & 1u) | (((o.m.c >> s) & 1u) << 1) | (((o.m.g >> s) & 1u) << 2) | (((o.m.t >> s) & 1u) << 3); };
+		if(i < qlen){
+			// expansion index -> this slot's digit: mixed radix over the degenerate slots in the odometer's order, lowest base first
+			const unsigned s = (unsigned)(o.start + i), rk = site_rank(s);
+			unsigned div = 1;
+			for(unsigned p = 0;p < 32u;++p){
+				const unsigned d = (unsigned)__popc(base_set(p));
+				if(d > 1u && site_rank(p) < rk) div *= d;
+			}
+			unsigned set = base_set(s);
+			const unsigned d = max((unsigned)__popc(set), 1u);
+			for(unsigned skip = (expansion/div) % d;skip;--skip) set &= set - 1u;
+			qc = (unsigned char)(set ? (unsigned)__ffs(set) - 1u : 0u);
+		}
+		if(i < tlen){
+			// the complement of the template bases, highest slot first
+			const unsigned s = (unsigned)(hi - i);
+			const unsigned b = ((tw.c >> s) & 1u) | (((tw.g >> s) & 1u) << 1) | (((tw.t >> s) & 1u)*3u);
+			tc = (unsigned char)(3u - b);
+		}
+		w.q[i] = qc; w.t[i] = tc;
+	}
+	wave_sync();
+	const int mxs = e.fill_wave(e.q, e.qlen, e.t, e.qlen, e.tlen, 0);
+	wave_sync();
+	collect_rows(e, e.qlen, e.tlen, 0, mxs, w.rowmask);
+	wave_sync();
+	unsigned status = 0;
+	const float tm = enumerate_parallel<false>(e, w.par, w.rowmask, e.qlen, false, status);
+	if(lane == 0){
+		// enumerate_parallel reports the winner's Tm only; its energies are still in the lanes' slabs: the same merge again
+		// (lowest dG, earliest cell on a tie).  This is a copy of the rule at the end of enumerate_parallel (pcr_thermo.inc):
+		// the two must change together.
+		int win = -1;
+		float wdg = 0.0f, dH = 0.0f, dS = 0.0f;
+		for(int l = 0;l < WAVE_PAR;++l){
+			const ParLane &L = w.par[l];
+			if(L.win < 0) continue;
+			const float dgl = L.best.dH - TARGET_T*L.best.dS;
+			if(win < 0 || dgl < wdg || (dgl == wdg && L.win < win)){ win = L.win; wdg = dgl; dH = L.best.dH; dS = L.best.dS; }
+		}
+		out = make_float4(tm, dH, dS, __uint_as_float((status & 1u) ? SITE_ST_ERROR : 0u));
+	}
+	wave_sync();                                                                   // before the next job overwrites the sequences
+	return true;
+}
+
+// One LDS copy of the dG table and this wave's slab behind it: the engine every melting kernel of this file sets up.
+__device__ __forceinline__ thermo::WaveSlab &site_engine(int *lds, const int *__restrict__ dg_global, float log_na, unsigned wave, thermo::Engine<1> &e)
+{
+	using namespace thermo;
+	WaveSlab &w = ((WaveSlab *)(lds + 49*49))[wave];
+	for(int i = threadIdx.x;i < 49*49;i += SITE_THREADS) lds[i] = dg_global[i];
+	__syncthreads();                                                               // the only workgroup barrier
+	e.dg = lds; e.log_na = log_na;
+	e.q = w.q; e.t = w.t;
+	e.mx.M = w.si;
+	e.mx.tr = w.ss;
+	return w;
+}
+
 // Job j = expansion j - joff[k] of item k, joff[k] <= j < joff[k + 1]: (tm, dH, dS, status) -> res[j].
 __global__ __launch_bounds__(SITE_THREADS) void k_site_tm(const DevEntry *__restrict__ db, uint32_t cap, const uint32_t *__restrict__ touched,
 	const uint32_t *__restrict__ seg_hi, const uint2 *__restrict__ items, uint32_t n_items, const uint64_t *__restrict__ joff, uint32_t n_jobs,
@@ -95,82 +173,23 @@ __global__ __launch_bounds__(SITE_THREADS) void k_site_tm(const DevEntry *__rest
 {
 	using namespace thermo;
 	extern __shared__ int site_lds[];                                             // dg [49*49] | SITE_WAVES slabs
-	int *const dg = site_lds;
 	const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
-	WaveSlab &w = ((WaveSlab *)(site_lds + 49*49))[wave];
-	for(int i = threadIdx.x;i < 49*49;i += SITE_THREADS) dg[i] = dg_global[i];
-	__syncthreads();                                                               // the only workgroup barrier
 	Engine<1> e;
-	e.dg = dg; e.log_na = log_na;
-	e.q = w.q; e.t = w.t;
-	e.mx.M = w.si;
-	e.mx.tr = w.ss;
+	WaveSlab &w = site_engine(site_lds, dg_global, log_na, wave, e);
 	for(unsigned j = blockIdx.x*SITE_WAVES + wave;j < n_jobs;j += gridDim.x*SITE_WAVES){   // uniform per wave
 		unsigned k = 0, above = n_items;                                           // joff[k] <= j < joff[above]
 		while(above - k > 1u){
 			const unsigned mid = k + (above - k)/2u;
 			if(joff[mid] <= (uint64_t)j) k = mid; else above = mid;
 		}
-		const unsigned expansion = j - (unsigned)joff[k];
 		const uint2 it = items[k];
 		const PoolOligo o = oligos[it.y];
 		const uint32_t slot = site_slot(it.x, cap, touched);
 		const uint32_t T = site_window(o.start, o.stop);
 		const DevEntry en = site_pick(db, slot, seg_hi[db[slot].seq], o, T);
-		int lo, hi;
-		if(!site_stretch(en.w, T, lo, hi)){                                        // no DP for a site that cannot be spelled
-			if(lane == 0) res[j] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(SITE_ST_NO_TM));
-			continue;
-		}
-		const int qlen = o.stop - o.start + 1, tlen = hi - lo + 1;                 // 1 .. 32 both (the host refuses oligos with holes)
-		e.log_strand = ox[it.y].log_strand; e.qlen = qlen; e.tlen = tlen;
-		if(lane <= MAXL){
-			const int i = (int)lane;
-			unsigned char qc = (unsigned char)bE, tc = (unsigned char)bE;         // "one past the end" is the non-pairing code E
-			auto base_set = [&](unsigned s) -> unsigned { return ((o.m.a >> s) & 1u) | (((o.m.c >> s) & 1u) << 1) | (((o.m.g >> s) & 1u) << 2) | (((o.m.t >> s) & 1u) << 3); };
-			if(i < qlen){
-				// expansion index -> this slot's digit: mixed radix over the degenerate slots in the odometer's order, lowest base first
-				const unsigned s = (unsigned)(o.start + i), rk = site_rank(s);
-				unsigned div = 1;
-				for(unsigned p = 0;p < 32u;++p){
-					const unsigned d = (unsigned)__popc(base_set(p));
-					if(d > 1u && site_rank(p) < rk) div *= d;
-				}
-				unsigned set = base_set(s);
-				const unsigned d = max((unsigned)__popc(set), 1u);
-				for(unsigned skip = (expansion/div) % d;skip;--skip) set &= set - 1u;
-				qc = (unsigned char)(set ? (unsigned)__ffs(set) - 1u : 0u);
-			}
-			if(i < tlen){
-				// the complement of the template bases, highest slot first
-				const unsigned s = (unsigned)(hi - i);
-				const unsigned b = ((en.w.c >> s) & 1u) | (((en.w.g >> s) & 1u) << 1) | (((en.w.t >> s) & 1u)*3u);
-				tc = (unsigned char)(3u - b);
-			}
-			w.q[i] = qc; w.t[i] = tc;
-		}
-		wave_sync();
-		const int mxs = e.fill_wave(e.q, e.qlen, e.t, e.qlen, e.tlen, 0);
-		wave_sync();
-		collect_rows(e, e.qlen, e.tlen, 0, mxs, w.rowmask);
-		wave_sync();
-		unsigned status = 0;
-		const float tm = enumerate_parallel<false>(e, w.par, w.rowmask, e.qlen, false, status);
-		if(lane == 0){
-			// enumerate_parallel reports the winner's Tm only; its energies are still in the lanes' slabs: the same merge again
-			// (lowest dG, earliest cell on a tie).  This is a copy of the rule at the end of enumerate_parallel (pcr_thermo.inc):
-			// the two must change together.
-			int win = -1;
-			float wdg = 0.0f, dH = 0.0f, dS = 0.0f;
-			for(int l = 0;l < WAVE_PAR;++l){
-				const ParLane &L = w.par[l];
-				if(L.win < 0) continue;
-				const float dgl = L.best.dH - TARGET_T*L.best.dS;
-				if(win < 0 || dgl < wdg || (dgl == wdg && L.win < win)){ win = L.win; wdg = dgl; dH = L.best.dH; dS = L.best.dS; }
-			}
-			res[j] = make_float4(tm, dH, dS, __uint_as_float((status & 1u) ? SITE_ST_ERROR : 0u));
-		}
-		wave_sync();                                                               // before the next job overwrites the sequences
+		float4 v;
+		site_melt(e, w, lane, o, ox[it.y].log_strand, en.w, T, j - (unsigned)joff[k], v);
+		if(lane == 0) res[j] = v;
 	}
 }
 
