@@ -706,6 +706,61 @@ int64_t pcr_pool_products_tm(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, 
 	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor,
 	uint32_t *oligo_id, pcr_product_tm *out, uint64_t cap, uint64_t *bits_fr, uint64_t *bits_rf);
 
+/* ---- Annealing profile: what a pool amplifies at every temperature of a gradient, from one melt and one join */
+
+#define PCR_ANNEAL_MAX_TEMPS 256
+#define PCR_ANNEAL_NO_PRODUCT (-1.0f)     /* melt value of a cell / sequence without any product */
+
+typedef struct {                          /* one temperature of the profile (40 bytes) */
+	float    temperature;                 /* temps[t], as given */
+	uint32_t reserved;                    /* 0 */
+	uint64_t products_intended;           /* products kept at this floor with pcr_product.intended = 1 */
+	uint64_t products_spurious;           /* ... with intended = 0 */
+	uint64_t cells;                       /* sum over pool rows i of pair_sequences[i][t] */
+	uint64_t spurious_sequences;          /* sequences that carry at least one kept spurious product */
+} pcr_anneal_point;
+
+/* Which products of a pool form, and which sequences each pool pair amplifies, at every temperature of an ascending list:
+ * what n_temps calls of pcr_pool_products_tm with tm_floor = temps[t] answer, from one melt of the sites and one join.
+ *   Products.  Exactly the products pcr_pool_products_tm forms for the same handle state, pool, threshold, amplicon range,
+ * args and template_strand with no floor; oligo_id[2*n_pool] is the same numbering.  A product's melt value is
+ * v = min(tm_plus, tm_minus), both Tm bit for bit those of pcr_pool_products_tm (a PCR_SITE_NO_TM site gives 0).
+ *   Keeping rule (pcr_pool_products_tm's, restated).  A product is kept at temps[t] iff !(temps[t] > 0) || v >= temps[t],
+ * in float.
+ *   Melt matrices.  melt_fr / melt_rf, either may be NULL: n_pool x pcr_num_sequences(ctx, which) floats, row-major.
+ * melt_fr[i][s] is the maximum of v over the products with plus_oligo = id(F_i), minus_oligo = id(R_i) and sequence s,
+ * melt_rf[i][s] the same with the two oligos exchanged; PCR_ANNEAL_NO_PRODUCT where the cell has no product, +0.0f where its
+ * only products have v = 0.  For every finite floor f, bit s of row i of bits_fr of pcr_pool_products_tm at tm_floor = f
+ * is set iff melt_fr[i][s] >= 0 && (!(f > 0) || melt_fr[i][s] >= f), and likewise melt_rf and bits_rf.  Pool pairs with the
+ * same (F, R) get equal rows; a pair with F = R gets melt_fr = melt_rf.  melt_spurious, may be NULL:
+ * pcr_num_sequences(ctx, which) floats, the maximum of v over the products on s with intended = 0 ({plus, minus} is no pool
+ * pair in either orientation), PCR_ANNEAL_NO_PRODUCT where there is none.  Everything asked for is written in full whenever
+ * the call returns >= 0.  The maxima are reduced on the device with integer atomics on the floats' bit patterns (v >= +0):
+ * the bytes do not depend on the order the device works in.
+ *   Points.  points[t], n_temps records: products_intended + products_spurious is what pcr_pool_products_tm returns with
+ * tm_floor = temps[t] and cap = 0.  pair_sequences, may be NULL: n_pool x n_temps, row-major; pair_sequences[i][t] is the
+ * number of sequences s whose max(melt_fr[i][s], melt_rf[i][s]) is a product's and is kept at temps[t] -- the population of
+ * bits_fr[i] | bits_rf[i] at that floor.  cells sums it over the pool rows (a repeated pair counts again) and is written
+ * also without pair_sequences; spurious_sequences counts the sequences whose melt_spurious is kept at temps[t].
+ *   Returns the number of products with no floor (pcr_pool_products' count) or a negative error.  n_pool = 0 returns 0 and
+ * writes points with zero counts and the temperatures.
+ *   PCR_ERR_ARG, from the arguments alone and before the handle, in pcr_pool_products_tm's order: unknown set or
+ * PCR_SET_MULTIPLEX; a null args, temps or points, or a null pool or oligo_id with n_pool > 0; n_pool > PCR_POOL_MAX_PAIRS;
+ * a negative concentration; salt outside [1e-6, 1]; an oligo that is empty, has a hole between its ends, more than
+ * PCR_SITE_MAX_EXPANSIONS expansions or a zero strand concentration; then n_temps = 0 or n_temps > PCR_ANNEAL_MAX_TEMPS;
+ * then a temperature that is not finite or temps not strictly ascending; then a null handle.  PCR_ERR_STATE without a word
+ * DB; PCR_ERR_CAPACITY for 2^31 or more sites, (site, expansion) jobs or products, or when the melt rows of the pool's
+ * distinct (F, R) would not fit in free device memory; PCR_ERR_RANGE if a trace-back fails inside the engine.  Changes
+ * nothing other calls read.  The number of kernel launches and copies does not depend on n_temps.  On a handle with a
+ * target shard attached, sequence indices are local to the rank's block and no collective is made. */
+int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand,
+	const float *temps, uint32_t n_temps, uint32_t *oligo_id,
+	pcr_anneal_point *points,             /* n_temps */
+	uint32_t *pair_sequences,             /* n_pool x n_temps, row-major; may be NULL */
+	float *melt_fr, float *melt_rf,       /* n_pool x pcr_num_sequences(ctx, which) each; either may be NULL */
+	float *melt_spurious);                /* pcr_num_sequences(ctx, which); may be NULL */
+
 /* ---- Probe hits: which products of a pool a panel's hydrolysis probes bind inside, and which sequences each assay detects */
 
 /* One probe site inside one product (64 bytes). */

@@ -93,6 +93,12 @@ PRODUCT_TM_DTYPE = np.dtype([("plus_oligo", np.uint32), ("minus_oligo", np.uint3
                              ("tm_plus", np.float32), ("tm_minus", np.float32), ("flags", np.uint32), ("reserved", np.uint32)])
 PRODUCT_PLUS_NO_TM, PRODUCT_MINUS_NO_TM = 1, 2   # PCR_PRODUCT_*_NO_TM
 
+# pcr_anneal_point: one temperature of an annealing profile (Screener.anneal_profile)
+ANNEAL_POINT_DTYPE = np.dtype([("temperature", np.float32), ("reserved", np.uint32), ("products_intended", np.uint64),
+                               ("products_spurious", np.uint64), ("cells", np.uint64), ("spurious_sequences", np.uint64)])
+ANNEAL_MAX_TEMPS = 256                        # PCR_ANNEAL_MAX_TEMPS
+ANNEAL_NO_PRODUCT = np.float32(-1.0)          # PCR_ANNEAL_NO_PRODUCT
+
 # pcr_probe_hit: one probe site inside one product (Screener.probe_hits)
 PROBE_HIT_DTYPE = np.dtype([("plus_oligo", np.uint32), ("minus_oligo", np.uint32), ("probe", np.uint32), ("sequence", np.uint32),
                             ("begin", np.int32), ("end", np.int32), ("inner_start", np.int32), ("inner_length", np.int32),
@@ -171,7 +177,7 @@ ABI_SYMBOLS = [
     "pcr_thermo", "pcr_valid_words", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers",
-    "pcr_pool_products_tm", "pcr_pool_probe_hits", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants",
+    "pcr_pool_products_tm", "pcr_pool_anneal_profile", "pcr_pool_probe_hits", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats", "pcr_live_resources",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -272,6 +278,10 @@ def load_library():
     L.pcr_pool_products_tm.restype = C.c_int64
     L.pcr_pool_products_tm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
                                        C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.pcr_pool_anneal_profile.restype = C.c_int64
+    L.pcr_pool_anneal_profile.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
+                                          C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
     L.pcr_pool_probe_hits.restype = C.c_int64
     L.pcr_pool_probe_hits.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32,
                                       C.POINTER(ThermoArgs), C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
@@ -545,6 +555,34 @@ def bits_to_bool(words, n):
     w = np.ascontiguousarray(words, dtype=np.uint64)
     b = np.unpackbits(w.view(np.uint8), bitorder="little")
     return b[:n].astype(bool)
+
+
+def melt_to_bits(melt, tm_floor):
+    """Melt rows of Screener.anneal_profile, float32 [rows, n_seq] -> uint64 [rows, ceil(n_seq / 64)] in pcr_amplify's bit layout:
+    the rows pool_products_tm(tm_floor=tm_floor, bits=True) gives.  Bit s is set iff the cell has a product (melt >= 0) and
+    the keeping rule holds for it: not (tm_floor > 0) or melt >= tm_floor, in float32."""
+    m = np.asarray(melt, np.float32)
+    if m.ndim != 2:
+        raise ValueError("melt_to_bits: melt must be [rows, n_seq]")
+    f = np.float32(tm_floor)
+    keep = m >= 0
+    if f > 0:
+        keep &= m >= f
+    pad = (-m.shape[1]) % 64
+    if pad:
+        keep = np.concatenate([keep, np.zeros((m.shape[0], pad), bool)], axis=1)
+    return np.packbits(keep, axis=1, bitorder="little").view(np.uint64).reshape(m.shape[0], (m.shape[1] + 63) // 64).copy()
+
+
+def anneal_ceiling(points, pair_sequences, keep=1.0):
+    """Index of the highest temperature of an annealing profile at which every pool row i still amplifies at least
+    ceil(keep * pair_sequences[i][0]) sequences; -1 if not even index 0 does (never with keep <= 1)."""
+    ps = np.asarray(pair_sequences, np.int64)
+    if ps.ndim != 2 or ps.shape[1] != len(points):
+        raise ValueError("anneal_ceiling: pair_sequences must be [rows, len(points)]")
+    need = np.ceil(float(keep) * ps[:, 0]).astype(np.int64) if ps.shape[1] else np.zeros(len(ps), np.int64)
+    ok = np.nonzero((ps >= need[:, None]).all(axis=0))[0]
+    return int(ok[-1]) if len(ok) else -1
 
 
 # ---------------------------------------------------------------------------- assay-list writers (host only)
@@ -1050,6 +1088,44 @@ class Screener:
                 rec = out[:n].copy()
                 return (ids[:2 * len(pool)].copy(), rec, fr, rf) if bits else (ids[:2 * len(pool)].copy(), rec)
             cap = int(n)                                                   # the count: one retry
+
+    def anneal_profile(self, pool, temps, threshold=1.0, salt=0.05, primer_strand=9e-7, template_strand=0.0,
+                       amp_min=80, amp_max=200, which=TARGET, select=False, melt=False):
+        """What the pool amplifies at every temperature of an annealing gradient (pcr_pool_anneal_profile) -> (oligo_id uint32
+        [2 * len(pool)], points: ANNEAL_POINT_DTYPE array of len(temps), pair_sequences uint32 [len(pool), len(temps)]), and
+        with melt=True also (melt_fr, melt_rf, melt_spurious): float32 [len(pool), n_seq], [len(pool), n_seq] and [n_seq].
+
+        `temps` is strictly ascending, at most ANNEAL_MAX_TEMPS long.  points[t] counts the products pool_products_tm keeps
+        at tm_floor = temps[t], by their `intended` flag; pair_sequences[i][t] is the number of sequences pair i amplifies
+        there (the population of pool_products_tm's fr[i] | rf[i]).  melt_fr[i][s] is the highest min(tm_plus, tm_minus) of
+        the products of (F_i, R_i) on sequence s, ANNEAL_NO_PRODUCT where there is none: melt_to_bits(melt_fr, T) is
+        pool_products_tm's fr at the floor T, for any T.  melt_spurious[s] is the same over the products on s that are no
+        pool pair's.  The sites are melted once and joined once, whatever len(temps).  `select` as for pool_products_tm."""
+        thr2 = float(np.float32(threshold) * np.float32(threshold))
+        if isinstance(select, str):
+            if select != "all":
+                raise ValueError("anneal_profile: select must be True, False or 'all'")
+            self.select_sites(pool, thr2, which=which)
+        elif select:
+            self.select_words(pool, thr2, which=which)
+        a = W.pairs_array(pool)
+        t = np.ascontiguousarray(temps, dtype=np.float32).reshape(-1)
+        ids = np.zeros(max(2 * len(pool), 1), np.uint32)
+        args = self._targs(salt, primer_strand, 0.0, 0.0, 0.0, 0.0)
+        n_seq = int(self.num_sequences(which))
+        points = np.zeros(max(len(t), 1), ANNEAL_POINT_DTYPE)
+        pair_seq = np.zeros((len(pool), len(t)), np.uint32)
+        fr = np.zeros((len(pool), n_seq), np.float32) if melt else None
+        rf = np.zeros((len(pool), n_seq), np.float32) if melt else None
+        sp = np.zeros(n_seq, np.float32) if melt else None
+        n = self.L.pcr_pool_anneal_profile(self.h, which, a.ctypes.data, len(pool), float(threshold), int(amp_min), int(amp_max),
+                                           C.byref(args), float(template_strand), t.ctypes.data, len(t), ids.ctypes.data,
+                                           points.ctypes.data, pair_seq.ctypes.data, fr.ctypes.data if melt else None,
+                                           rf.ctypes.data if melt else None, sp.ctypes.data if melt else None)
+        if n < 0:
+            raise PcrError(_err(self.L))
+        out = (ids[:2 * len(pool)].copy(), points[:len(t)].copy(), pair_seq)
+        return out + (fr, rf, sp) if melt else out
 
     def probe_hits(self, pool, probes, threshold=1.0, tm_floor=0.0, probe_tm_floor=0.0, salt=0.05, primer_strand=9e-7,
                    probe_strand=2.5e-7, template_strand=0.0, amp_min=80, amp_max=200, which=TARGET, select=False,

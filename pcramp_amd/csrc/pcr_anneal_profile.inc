@@ -1,0 +1,373 @@
+// What a primer pool amplifies at every temperature of an annealing gradient, from one melt and one join
+// (pcr_pool_anneal_profile; included by pcr_device.hip after pcr_products_tm.inc, whose steps 1-3 it launches as they are).
+//
+// The Tm of a site does not depend on the floor pcr_pool_products_tm applies, only the comparison does.  A product with
+// v = min(tm_plus, tm_minus) is kept at temps[t] iff !(temps[t] > 0) || v >= temps[t]; temps is strictly ascending, so the kept
+// temperatures are a prefix 0 .. u - 1 and u is all a product contributes to the counts.  Per (pool pair, sequence) the highest
+// v of the cell's products decides the bit of pcr_pool_products_tm at every floor.
+//   1-3. the items, the jobs, k_site_tm, k_item_tm -> item_tm[] (pcr_products_tm.inc's steps, on this call's own scratch).
+//   4. k_anneal_join: k_products_join's geometry and tests, no floor.  Per product: u by a binary search in an LDS copy of temps,
+//      hist[intended][u] += 1 in LDS (flushed once per block with 64-bit atomic adds), and the cell's melt value raised with an
+//      integer atomicMax on the float's bits: v >= +0 (the engine clamps a Tm at 0; v + 0.0f turns a -0 into +0), non-negative
+//      floats order like their bit patterns read as int32, and the sentinel -1.0f is a negative int32.  A maximum does not depend
+//      on the order of its operands, so the matrices are the same bytes whatever order the threads arrive in.
+//      The melt rows are keyed by (plus, minus): row r of `melt` belongs to key_tab[r], the sorted distinct F*n_ol + R and
+//      R*n_ol + F of the pool.  melt_fr of pool row i is the row of (F_i, R_i), melt_rf that of (R_i, F_i): pairs that repeat or
+//      exchange an earlier one share its rows, F = R has one row for both.  The last row is the spurious vector.
+//   5. k_anneal_rows: one workgroup per pool row (and one for the spurious row) streams the row's two melt rows, takes u of
+//      max(fr, rf) per sequence into an LDS histogram, and writes the suffix sums: pair_sequences[i][t], cells[t] (atomics),
+//      spurious_sequences[t].
+//   6. The host turns hist into the points' product counts (products at t = sum of hist[.][u] over u > t).
+// The number of launches and copies does not depend on n_temps.  The call owns its scratch (pcr_ctx::anp_*).
+
+namespace {
+
+constexpr uint32_t ANP_BINS = PCR_ANNEAL_MAX_TEMPS + 1;                         // u = 0 .. n_temps
+constexpr uint32_t ANP_ROW_THREADS = 256;
+// the small results, one u64 array copied back at once: hist[2][ANP_BINS] | cells[MAX_TEMPS] | spurious_sequences[MAX_TEMPS]
+constexpr uint32_t ANP_OUT_CELLS = 2*ANP_BINS, ANP_OUT_SPUR = ANP_OUT_CELLS + PCR_ANNEAL_MAX_TEMPS, ANP_OUT_WORDS = ANP_OUT_SPUR + PCR_ANNEAL_MAX_TEMPS;
+
+// The keeping rule, and the number of temperatures of the ascending ts[0 .. n) at which a product with min-Tm v is kept.
+__device__ __forceinline__ bool anneal_kept(float v, float t) { return !(t > 0.0f) || v >= t; }
+__device__ __forceinline__ uint32_t anneal_prefix(const float *ts, uint32_t n, float v)
+{
+	uint32_t lo = 0, hi = n;                                                     // kept at every t < lo, at no t >= hi
+	while(lo < hi){
+		const uint32_t mid = lo + (hi - lo)/2u;
+		if(anneal_kept(v, ts[mid])) lo = mid + 1u; else hi = mid;
+	}
+	return lo;
+}
+
+// k_products_join<false> without a floor: one thread per item k, a plus-strand item (i, x) against the minus-strand items (j, y)
+// of its segment.  Every product: hist[intended][u], and its cell of `melt` (intended: the row of its key) or of the last row
+// (spurious) raised to v.
+__global__ __launch_bounds__(POOL_THREADS) void k_anneal_join(const DevEntry *__restrict__ db, uint32_t cap, const uint32_t *__restrict__ touched,
+	const uint32_t *__restrict__ seg_hi, const uint2 *__restrict__ items, uint32_t n_items, const uint64_t *__restrict__ item_off,
+	const PoolOligo *__restrict__ oligos, uint32_t n_ol, const uint4 *__restrict__ planes, const uint64_t *__restrict__ blk_off,
+	const uint64_t *__restrict__ len, const uint8_t *__restrict__ has_eos, int32_t amp_min, int32_t amp_max,
+	const ItemTm *__restrict__ item_tm, const uint32_t *__restrict__ intended, const uint32_t *__restrict__ key_tab, uint32_t n_tab,
+	const float *__restrict__ temps, uint32_t n_temps, int *__restrict__ melt, uint32_t n_seq, unsigned long long *__restrict__ out)
+{
+	__shared__ int2 ss[POOL_MAX_OLIGOS];                                        // Word::start() / stop()
+	__shared__ float ts[PCR_ANNEAL_MAX_TEMPS];
+	__shared__ uint32_t hist[2*ANP_BINS];
+	for(uint32_t o = threadIdx.x;o < n_ol;o += blockDim.x) ss[o] = make_int2(oligos[o].start, oligos[o].stop);
+	for(uint32_t t = threadIdx.x;t < n_temps;t += blockDim.x) ts[t] = temps[t];
+	for(uint32_t b = threadIdx.x;b < 2*ANP_BINS;b += blockDim.x) hist[b] = 0;
+	__syncthreads();
+	const uint32_t k = blockIdx.x*blockDim.x + threadIdx.x;
+	if(k < n_items){
+		const uint2 it = items[k];
+		const uint32_t g = it.x, x = it.y;
+		const uint32_t i = touched[g/cap]*cap + g % cap;
+		const DevEntry ei = db[i];
+		if(ei.strand == 1){
+			const uint32_t hi = seg_hi[ei.seq];
+			const int32_t L = (int32_t)len[ei.seq];
+			const uint64_t blk_base = blk_off[ei.seq];
+			const bool eos = has_eos[ei.seq] != 0;
+			const int2 P = ss[x];
+			const int32_t p5 = ei.loc + P.x, p3 = ei.loc + P.y;                      // template_loc5/3, sequence.h:57-75
+			const ItemTm tp = item_tm[k];
+			for(uint32_t j = i + 1;j < hi;++j){
+				const DevEntry ej = db[j];
+				if(ej.loc - ei.loc > amp_max + 128) break;
+				if(ej.strand != 2) continue;
+				const uint32_t gj = g + (j - i);                                     // same segment: consecutive DB threads
+				const uint64_t t_end = item_off[gj + 1];
+				for(uint64_t t = item_off[gj];t < t_end;++t){
+					const uint32_t y = items[t].y;
+					const int2 M = ss[y];
+					const int32_t m5 = ej.loc - M.y, m3 = ej.loc - M.x;
+					if(p3 >= m5) continue;                                           // pcr_assay.cpp:468-471
+					const int32_t amp_len = m3 - p5 + 1;
+					if(amp_len < amp_min || amp_len > amp_max) continue;             // :477-484
+					const int32_t in_start = p3 + 1 - 4;                             // :489-490
+					const int32_t in_len = m5 - in_start + 8;                        // :492-494
+					if(in_start < 0 || in_len < 0 || in_start + in_len > L) continue;
+					if(eos && has_split(planes, blk_base, in_start, in_len)) continue;   // :504-521
+					const ItemTm tm = item_tm[t];
+					const float v = ((tp.tm < tm.tm) ? tp.tm : tm.tm) + 0.0f;        // k_products_join's min; + 0.0f: -0 -> +0 (contraction is off)
+					const uint32_t u = anneal_prefix(ts, n_temps, v);
+					const uint32_t b = x*n_ol + y;
+					size_t row = n_tab;                                              // the spurious row
+					const bool is_intended = (intended[b >> 5] >> (b & 31)) & 1u;
+					if(is_intended){
+						uint32_t lo = 0, above = n_tab;                              // key_tab[lo] <= b < key_tab[above]; an intended b is in the table
+						while(above - lo > 1u){
+							const uint32_t mid = lo + (above - lo)/2u;
+							if(key_tab[mid] <= b) lo = mid; else above = mid;
+						}
+						row = lo;
+					}
+					atomicAdd(&hist[(is_intended ? ANP_BINS : 0u) + u], 1u);
+					atomicMax(melt + row*n_seq + ei.seq, __float_as_int(v));
+				}
+			}
+		}
+	}
+	__syncthreads();
+	for(uint32_t b = threadIdx.x;b < 2*ANP_BINS;b += blockDim.x){
+		const uint32_t c = hist[b];
+		if(c) atomicAdd(out + b, (unsigned long long)c);
+	}
+}
+
+// Workgroup i < n_pool: pool row i, whose melt_fr / melt_rf are rows row_map[i].x / .y of melt; workgroup n_pool: the spurious
+// row n_tab.  u of max(fr, rf) per sequence with a product -> LDS histogram -> suffix sums over u.
+__global__ __launch_bounds__(ANP_ROW_THREADS) void k_anneal_rows(const int *__restrict__ melt, uint32_t n_seq, const uint2 *__restrict__ row_map,
+	uint32_t n_pool, uint32_t n_tab, const float *__restrict__ temps, uint32_t n_temps, uint32_t *__restrict__ pair_seq,
+	unsigned long long *__restrict__ out)
+{
+	__shared__ float ts[PCR_ANNEAL_MAX_TEMPS];
+	__shared__ uint32_t hist[ANP_BINS];
+	for(uint32_t t = threadIdx.x;t < n_temps;t += blockDim.x) ts[t] = temps[t];
+	for(uint32_t b = threadIdx.x;b < ANP_BINS;b += blockDim.x) hist[b] = 0;
+	__syncthreads();
+	const uint32_t i = blockIdx.x;
+	const bool spurious = i >= n_pool;
+	const uint2 rows = spurious ? make_uint2(n_tab, n_tab) : row_map[i];
+	const int *fr = melt + (size_t)rows.x*n_seq, *rf = melt + (size_t)rows.y*n_seq;
+	for(uint32_t s = threadIdx.x;s < n_seq;s += blockDim.x){
+		const int a = fr[s], b = rf[s];
+		const int m = (a > b) ? a : b;                                           // the order of the floats: see the head of this file
+		if(m < 0) continue;                                                      // -1.0f: no product in the cell
+		atomicAdd(&hist[anneal_prefix(ts, n_temps, __int_as_float(m))], 1u);
+	}
+	__syncthreads();
+	for(uint32_t t = threadIdx.x;t < n_temps;t += blockDim.x){
+		uint32_t c = 0;
+		for(uint32_t u = t + 1;u <= n_temps;++u) c += hist[u];                   // kept at t: u > t
+		if(spurious) out[ANP_OUT_SPUR + t] = c;
+		else{
+			pair_seq[(size_t)i*n_temps + t] = c;
+			if(c) atomicAdd(out + ANP_OUT_CELLS + t, (unsigned long long)c);
+		}
+	}
+}
+
+} // namespace
+
+extern "C" {
+
+int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand,
+	const float *temps, uint32_t n_temps, uint32_t *oligo_id, pcr_anneal_point *points, uint32_t *pair_sequences,
+	float *melt_fr, float *melt_rf, float *melt_spurious)
+{
+	static_assert(sizeof(pcr_anneal_point) == 40, "record layout");
+	static_assert(sizeof(PoolOligo) == 32 && sizeof(SiteOligoX) == 8, "table layout");
+	// ---- the arguments, before the handle (pcr_pool_products_tm's checks in its order, then the temperatures)
+	if(!set_ok(which)){ g_err = "pcr_pool_anneal_profile: unknown sequence set"; return PCR_ERR_ARG; }
+	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = "pcr_pool_anneal_profile: PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
+	if(!args || !temps || !points || (n_pool && (!pool || !oligo_id))){ g_err = "pcr_pool_anneal_profile: bad argument"; return PCR_ERR_ARG; }
+	if(n_pool > PCR_POOL_MAX_PAIRS){ g_err = "pcr_pool_anneal_profile: pool larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
+	if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f)){ g_err = "pcr_pool_anneal_profile: negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
+	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = "pcr_pool_anneal_profile: salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
+	// the distinct oligos, in order of first appearance (as pcr_pool_products_tm)
+	std::vector<PoolOligo> ol;
+	std::vector<SiteOligoX> olx;
+	std::map<std::pair<uint64_t, uint64_t>, uint32_t> id_of;
+	const float thr2 = threshold*threshold;                                      // pcr_assay.cpp:775-776
+	for(uint32_t s = 0;s < 2*n_pool;++s){
+		const pcr_word128 &wd = (s & 1) ? pool[s/2].r : pool[s/2].f;
+		auto ins = id_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)ol.size()));
+		if(ins.second){
+			OligoDev d; fill_oligo(d, wd.w, thr2);
+			const uint32_t occ = pcrhost::planes_occupied(d.m);
+			if(!occ || __builtin_popcount(occ) != d.stop - d.start + 1){
+				g_err = "pcr_pool_anneal_profile: an oligo is empty or has a hole between its ends (NucCruc::set_query throws)"; return PCR_ERR_ARG;
+			}
+			const double degen = pcrhost::planes_degeneracy(d.m);
+			if(degen > (double)PCR_SITE_MAX_EXPANSIONS){ g_err = "pcr_pool_anneal_profile: an oligo has more than PCR_SITE_MAX_EXPANSIONS expansions"; return PCR_ERR_ARG; }
+			PoolOligo p; p.m = d.m; p.floor2 = d.floor2; p.start = d.start; p.stop = d.stop; p.pad = 0;
+			ol.push_back(p);
+			const float ca = (float)(args->primer_strand/degen), cb = template_strand;
+			const float strand = (ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca;          // nuc_cruc.h:832-837
+			if(!(strand > 0.0f)){ g_err = "pcr_pool_anneal_profile: the strand concentration of an oligo's duplex is zero (primer_strand / degeneracy and template_strand both 0)"; return PCR_ERR_ARG; }
+			SiteOligoX x; x.n_exp = (uint32_t)degen;
+			x.log_strand = logf(strand);
+			olx.push_back(x);
+		}
+		oligo_id[s] = ins.first->second;
+	}
+	if(n_temps == 0 || n_temps > PCR_ANNEAL_MAX_TEMPS){ g_err = "pcr_pool_anneal_profile: n_temps is 0 or larger than PCR_ANNEAL_MAX_TEMPS"; return PCR_ERR_ARG; }
+	for(uint32_t t = 0;t < n_temps;++t){
+		if(!std::isfinite(temps[t])){ g_err = "pcr_pool_anneal_profile: a temperature is not finite"; return PCR_ERR_ARG; }
+		if(t && !(temps[t] > temps[t - 1])){ g_err = "pcr_pool_anneal_profile: temps is not strictly ascending"; return PCR_ERR_ARG; }
+	}
+	if(!ctx){ g_err = "pcr_pool_anneal_profile: null handle"; return PCR_ERR_ARG; }
+	{ const int drc = drain(ctx); if(drc != PCR_OK) return drc; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	SeqSet &S = ctx->sets[which];
+	if(!S.have_db){ g_err = "pcr_pool_anneal_profile: no word DB (call pcr_select_words or pcr_select_sites first)"; return PCR_ERR_STATE; }
+	const size_t n_seq = S.n;
+	// whatever the count, everything asked for is written in full: no product anywhere
+	auto write_empty = [&](){
+		for(uint32_t t = 0;t < n_temps;++t){ pcr_anneal_point p; memset(&p, 0, sizeof p); p.temperature = temps[t]; points[t] = p; }
+		if(pair_sequences) memset(pair_sequences, 0, (size_t)n_pool*n_temps*sizeof(uint32_t));
+		if(melt_fr) std::fill(melt_fr, melt_fr + (size_t)n_pool*n_seq, PCR_ANNEAL_NO_PRODUCT);
+		if(melt_rf) std::fill(melt_rf, melt_rf + (size_t)n_pool*n_seq, PCR_ANNEAL_NO_PRODUCT);
+		if(melt_spurious) std::fill(melt_spurious, melt_spurious + n_seq, PCR_ANNEAL_NO_PRODUCT);
+	};
+	if(n_pool == 0){ write_empty(); return 0; }
+	{ const int erc = ensure_touched(ctx, S); if(erc != PCR_OK) return erc; }
+	if(S.n_entries == 0 || S.n_touched == 0){ write_empty(); return 0; }
+	const uint32_t n_ol = (uint32_t)ol.size();
+	// the intended bitmap; the sorted distinct (plus, minus) keys of the pool, one melt row each; each pool row's two rows
+	std::vector<uint32_t> intended(((size_t)n_ol*n_ol + 31)/32, 0);
+	std::vector<uint32_t> key_tab;
+	key_tab.reserve(2*(size_t)n_pool);
+	for(uint32_t i = 0;i < n_pool;++i){
+		const uint32_t f = oligo_id[2*i], r = oligo_id[2*i + 1];
+		for(uint32_t b : {f*n_ol + r, r*n_ol + f}){ intended[b >> 5] |= 1u << (b & 31); key_tab.push_back(b); }
+	}
+	std::sort(key_tab.begin(), key_tab.end());
+	key_tab.erase(std::unique(key_tab.begin(), key_tab.end()), key_tab.end());
+	const uint32_t n_tab = (uint32_t)key_tab.size();
+	std::vector<uint2> row_map(n_pool);
+	for(uint32_t i = 0;i < n_pool;++i){
+		const uint32_t f = oligo_id[2*i], r = oligo_id[2*i + 1];
+		row_map[i].x = (uint32_t)(std::lower_bound(key_tab.begin(), key_tab.end(), f*n_ol + r) - key_tab.begin());
+		row_map[i].y = (uint32_t)(std::lower_bound(key_tab.begin(), key_tab.end(), r*n_ol + f) - key_tab.begin());
+	}
+	int rc;
+	// the melt rows (+ the spurious row) must fit beside what the device already holds: refuse before hipMalloc would fail
+	const size_t melt_elems = ((size_t)n_tab + 1)*n_seq;
+	if(melt_elems > ctx->anp_melt.cap){
+		size_t free_b = 0, total_b = 0;
+		HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+		const size_t have = free_b + ctx->anp_melt.cap*sizeof(float);             // (ensure gives the old buffer back first)
+		const size_t headroom = size_t(256) << 20;
+		if(have < headroom || melt_elems*sizeof(float) > have - headroom){
+			g_err = "pcr_pool_anneal_profile: the melt rows of the pool's distinct (F, R) would not fit in device memory"; return PCR_ERR_CAPACITY;
+		}
+	}
+	if((rc = ctx->anp_melt.ensure(melt_elems)) != PCR_OK) return rc;
+	const size_t ol_bytes = ol.size()*sizeof(PoolOligo), olx_bytes = olx.size()*sizeof(SiteOligoX), map_bytes = row_map.size()*sizeof(uint2),
+		tab_bytes = key_tab.size()*sizeof(uint32_t), int_bytes = intended.size()*sizeof(uint32_t), temp_bytes = (size_t)n_temps*sizeof(float);
+	std::vector<uint8_t> blob(ol_bytes + olx_bytes + map_bytes + tab_bytes + int_bytes + temp_bytes);   // 32-, 8-, 8-, 4-, 4- and 4-byte records, in that order: each is aligned
+	memcpy(blob.data(), ol.data(), ol_bytes);
+	memcpy(blob.data() + ol_bytes, olx.data(), olx_bytes);
+	memcpy(blob.data() + ol_bytes + olx_bytes, row_map.data(), map_bytes);
+	memcpy(blob.data() + ol_bytes + olx_bytes + map_bytes, key_tab.data(), tab_bytes);
+	memcpy(blob.data() + ol_bytes + olx_bytes + map_bytes + tab_bytes, intended.data(), int_bytes);
+	memcpy(blob.data() + ol_bytes + olx_bytes + map_bytes + tab_bytes + int_bytes, temps, temp_bytes);
+	if((rc = ctx->anp_in.ensure(blob.size())) != PCR_OK) return rc;
+	const PoolOligo *d_ol = (const PoolOligo *)ctx->anp_in.p;
+	const SiteOligoX *d_olx = (const SiteOligoX *)(ctx->anp_in.p + ol_bytes);
+	const uint2 *d_map = (const uint2 *)(ctx->anp_in.p + ol_bytes + olx_bytes);
+	const uint32_t *d_tab = (const uint32_t *)(ctx->anp_in.p + ol_bytes + olx_bytes + map_bytes);
+	const uint32_t *d_intended = (const uint32_t *)(ctx->anp_in.p + ol_bytes + olx_bytes + map_bytes + tab_bytes);
+	const float *d_temps = (const float *)(ctx->anp_in.p + ol_bytes + olx_bytes + map_bytes + tab_bytes + int_bytes);
+	HIP_TRY(hipMemcpyAsync(ctx->anp_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+	// ---- 1. the items (k_pool_entry_oligos: count, scan, fill)
+	const uint32_t n_db = S.n_touched*S.db_cap;
+	if((rc = ctx->anp_cnt.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
+	if((rc = ctx->anp_eoff.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->anp_cnt.p + n_db, 0, sizeof(uint32_t), ctx->stream));
+	size_t tmp = 0;
+	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->anp_cnt.p, ctx->anp_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	if((rc = ctx->anp_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
+	const unsigned grid_e = std::min<unsigned>((n_db + POOL_THREADS - 1)/POOL_THREADS, ctx->n_cu*8);
+	hipLaunchKernelGGL(k_pool_entry_oligos<false>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
+		S.d_seg_hi, S.d_active.p, d_ol, n_ol, ctx->anp_cnt.p, (const uint64_t *)nullptr, (uint2 *)nullptr);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(rocprim::exclusive_scan(ctx->anp_tmp.p, tmp, ctx->anp_cnt.p, ctx->anp_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	uint64_t n_items = 0;
+	HIP_TRY(hipMemcpyAsync(&n_items, ctx->anp_eoff.p + n_db, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));                                   // (blob is read by now)
+	if(n_items >= POOL_MAX_ITEMS){ g_err = "pcr_pool_anneal_profile: too many (entry, oligo) hits"; return PCR_ERR_CAPACITY; }
+	if(n_items == 0){ write_empty(); return 0; }
+	if((rc = ctx->anp_items.ensure(n_items)) != PCR_OK) return rc;
+	hipLaunchKernelGGL(k_pool_entry_oligos<true>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
+		S.d_seg_hi, S.d_active.p, d_ol, n_ol, (uint32_t *)nullptr, (const uint64_t *)ctx->anp_eoff.p, ctx->anp_items.p);
+	HIP_TRY(hipGetLastError());
+	const uint32_t ni = (uint32_t)n_items;
+	const unsigned grid_i = (ni + POOL_THREADS - 1)/POOL_THREADS;
+	if((rc = ctx->anp_cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;         // (the entry counts are spent)
+	if((rc = ctx->anp_flag.ensure(1)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->anp_flag.p, 0, sizeof(uint32_t), ctx->stream));
+	// ---- 2. job offsets, the jobs (k_site_jobs, k_site_tm as they stand)
+	if((rc = ctx->anp_joff.ensure((size_t)ni + 1)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->anp_cnt.p + ni, 0, sizeof(uint32_t), ctx->stream));
+	hipLaunchKernelGGL(k_site_jobs, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint2 *)ctx->anp_items.p, ni, d_olx, ctx->anp_cnt.p);
+	HIP_TRY(hipGetLastError());
+	tmp = 0;
+	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->anp_cnt.p, ctx->anp_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	if((rc = ctx->anp_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
+	HIP_TRY(rocprim::exclusive_scan(ctx->anp_tmp.p, tmp, ctx->anp_cnt.p, ctx->anp_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	uint64_t n_jobs64 = 0;
+	HIP_TRY(hipMemcpyAsync(&n_jobs64, ctx->anp_joff.p + ni, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if(n_jobs64 >= POOL_MAX_ITEMS){ g_err = "pcr_pool_anneal_profile: too many (site, expansion) jobs"; return PCR_ERR_CAPACITY; }
+	const uint32_t n_jobs = (uint32_t)n_jobs64;
+	if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
+	if(!ctx->site_attr_set){                                                   // (k_site_tm's own flag: the attribute is the kernel's)
+		HIP_TRY(hipFuncSetAttribute((const void *)k_site_tm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SITE_LDS));
+		ctx->site_attr_set = true;
+	}
+	if((rc = ctx->anp_res.ensure(n_jobs)) != PCR_OK) return rc;
+	if((rc = ctx->anp_item_tm.ensure(ni)) != PCR_OK) return rc;
+	// at most one block per CU (a block takes most of a CU's LDS), the waves striding over the jobs
+	const unsigned grid_j = std::max(1u, std::min<unsigned>((n_jobs + SITE_WAVES - 1)/SITE_WAVES, (unsigned)ctx->n_cu));
+	hipLaunchKernelGGL(k_site_tm, dim3(grid_j), dim3(SITE_THREADS), SITE_LDS, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
+		(const uint2 *)ctx->anp_items.p, ni, (const uint64_t *)ctx->anp_joff.p, n_jobs, d_ol, d_olx, (const int *)ctx->th_dg.p, logf(args->salt), ctx->anp_res.p);
+	HIP_TRY(hipGetLastError());
+	// ---- 3. Tm per item
+	hipLaunchKernelGGL(k_item_tm, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint64_t *)ctx->anp_joff.p, ni,
+		(const float4 *)ctx->anp_res.p, (ItemTm *)ctx->anp_item_tm.p, ctx->anp_flag.p);
+	HIP_TRY(hipGetLastError());
+	// ---- 4. the join: histograms and melt rows
+	if((rc = ctx->anp_out.ensure(ANP_OUT_WORDS)) != PCR_OK) return rc;
+	if((rc = ctx->anp_pairseq.ensure((size_t)n_pool*n_temps)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->anp_out.p, 0, ANP_OUT_WORDS*sizeof(uint64_t), ctx->stream));
+	HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ctx->anp_melt.p, (int)0xBF800000u, melt_elems, ctx->stream));   // -1.0f
+	hipLaunchKernelGGL(k_anneal_join, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
+		ctx->anp_items.p, ni, (const uint64_t *)ctx->anp_eoff.p, d_ol, n_ol, S.planes.p, S.d_blk_off.p, S.d_len.p, S.d_has_eos.p,
+		amp_min, amp_max, (const ItemTm *)ctx->anp_item_tm.p, d_intended, d_tab, n_tab, d_temps, n_temps, (int *)ctx->anp_melt.p,
+		(uint32_t)n_seq, (unsigned long long *)ctx->anp_out.p);
+	HIP_TRY(hipGetLastError());
+	// ---- 5. the rows' histograms
+	hipLaunchKernelGGL(k_anneal_rows, dim3(n_pool + 1), dim3(ANP_ROW_THREADS), 0, ctx->stream, (const int *)ctx->anp_melt.p, (uint32_t)n_seq,
+		d_map, n_pool, n_tab, d_temps, n_temps, ctx->anp_pairseq.p, (unsigned long long *)ctx->anp_out.p);
+	HIP_TRY(hipGetLastError());
+	uint64_t small[ANP_OUT_WORDS];
+	uint32_t bad = 0;
+	const bool want_rows = melt_fr || melt_rf;
+	std::vector<float> host_melt;                                               // the keyed rows (+ the spurious row), when a matrix is asked for
+	HIP_TRY(hipMemcpyAsync(small, ctx->anp_out.p, sizeof small, hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipMemcpyAsync(&bad, ctx->anp_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	if(pair_sequences) HIP_TRY(hipMemcpyAsync(pair_sequences, ctx->anp_pairseq.p, (size_t)n_pool*n_temps*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	if(want_rows){
+		host_melt.resize(melt_elems);
+		HIP_TRY(hipMemcpyAsync(host_melt.data(), ctx->anp_melt.p, melt_elems*sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+	}
+	else if(melt_spurious) HIP_TRY(hipMemcpyAsync(melt_spurious, ctx->anp_melt.p + (size_t)n_tab*n_seq, n_seq*sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if(bad & 1u){ g_err = "pcr_pool_anneal_profile: internal trace-back error"; return PCR_ERR_RANGE; }
+	uint64_t total = 0;
+	for(uint32_t b = 0;b < 2*ANP_BINS;++b) total += small[b];
+	if(total >= POOL_MAX_ITEMS){ g_err = "pcr_pool_anneal_profile: too many products"; return PCR_ERR_CAPACITY; }
+	// ---- 6. the points: a product with u kept temperatures counts at every t < u
+	uint64_t kept[2] = {0, 0};
+	for(uint32_t t = n_temps;t-- > 0;){
+		for(int c = 0;c < 2;++c) kept[c] += small[c*ANP_BINS + t + 1];
+		pcr_anneal_point p;
+		p.temperature = temps[t]; p.reserved = 0;
+		p.products_spurious = kept[0]; p.products_intended = kept[1];
+		p.cells = small[ANP_OUT_CELLS + t]; p.spurious_sequences = small[ANP_OUT_SPUR + t];
+		points[t] = p;
+	}
+	if(want_rows){
+		for(uint32_t i = 0;i < n_pool;++i){
+			if(melt_fr) memcpy(melt_fr + (size_t)i*n_seq, host_melt.data() + (size_t)row_map[i].x*n_seq, n_seq*sizeof(float));
+			if(melt_rf) memcpy(melt_rf + (size_t)i*n_seq, host_melt.data() + (size_t)row_map[i].y*n_seq, n_seq*sizeof(float));
+		}
+		if(melt_spurious) memcpy(melt_spurious, host_melt.data() + (size_t)n_tab*n_seq, n_seq*sizeof(float));
+	}
+	return (int64_t)total;
+}
+
+} // extern "C"

@@ -31,6 +31,7 @@
 //   k_sv_items, k_sv_heads, k_sv_tm : the sites grouped by (oligo, template planes in the window) with radix sorts over the whole key, one melt per group (pcr_site_variants.inc)
 //   k_pool_dimer, k_pool_dimer_reduce : the same engine over every ordered oligo pair of a pool, jobs derived from the job number (pcr_pool_dimers.inc)
 //   k_item_tm, k_products_join : k_site_tm's Tm per item, and k_pool_join's geometry with the two sites' Tm, the floor and the pool's bit rows (pcr_products_tm.inc)
+//   k_anneal_join, k_anneal_rows : the same join without a floor: per (pool pair, sequence) the highest min-Tm by integer atomicMax, LDS histograms over an ascending temperature list (pcr_anneal_profile.inc)
 //   k_probe_products, k_probe_hits : the kept products of the primers compacted, then a wave per product over the probe items inside it (pcr_probe_hits.inc)
 //   k_amp_scan, k_amp_verify, k_amp_extract : eight lanes per product record over its bases: G+C, a hash of its spelling, equality with its group's first, the packed text (pcr_pool_amplicons.inc)
 // Host side in the same library: pcr_optimize.inc (optimize() batched over trial assays), pcr_sampler.inc, pcr_multiplex.inc,
@@ -854,6 +855,11 @@ struct pcr_ctx {
 	// the u32 and u64 arrays carved from one buffer each (occurrences, sort keys and indices, flags and their scans), the candidate and the kept
 	// records, scan / sort scratch.  (After pam_*, for the same reason.)
 	DevBuf<uint4> ppc_iv; DevBuf<uint32_t> ppc_pos, ppc_u32; DevBuf<uint64_t> ppc_u64; DevBuf<pcr_probe_candidate> ppc_rec; DevBuf<uint8_t> ppc_tmp;
+	// pcr_pool_anneal_profile (pcr_anneal_profile.inc): oligo tables + row map + key table + intended bitmap + temperatures, per-entry / per-item counts
+	// and offsets, items, job offsets, per-job results, per-item Tm, error flag, the melt rows of the pool's distinct (plus, minus) keys + the spurious row,
+	// the histograms and per-temperature sums, pair_sequences.  (After ppc_*, for the same reason.)
+	DevBuf<uint8_t> anp_in, anp_tmp; DevBuf<uint32_t> anp_cnt, anp_flag, anp_pairseq; DevBuf<uint64_t> anp_eoff, anp_joff, anp_out;
+	DevBuf<uint2> anp_items; DevBuf<float4> anp_res; DevBuf<uint2> anp_item_tm; DevBuf<float> anp_melt;
 };
 
 namespace {
@@ -2177,6 +2183,7 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_site_variants.inc"
 #include "pcr_pool_dimers.inc"
 #include "pcr_products_tm.inc"
+#include "pcr_anneal_profile.inc"
 #include "pcr_probe_hits.inc"
 #include "pcr_pool_amplicons.inc"
 #include "pcr_probe_candidates.inc"
