@@ -761,6 +761,59 @@ int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *poo
 	float *melt_fr, float *melt_rf,       /* n_pool x pcr_num_sequences(ctx, which) each; either may be NULL */
 	float *melt_spurious);                /* pcr_num_sequences(ctx, which); may be NULL */
 
+/* ---- Pool conflicts: which assays of a pool cannot share a tube */
+
+typedef struct {                          /* one unordered pair of pool rows (48 bytes) */
+	uint32_t row_a, row_b;                /* pool rows, row_a <= row_b; equal: the assay against itself */
+	uint64_t products;                    /* spurious products attributed to the cell and kept at tm_floor */
+	uint32_t sequences;                   /* distinct `sequence` values among them */
+	float    melt;                        /* max of v = min(tm_plus, tm_minus) over them; PCR_ANNEAL_NO_PRODUCT if products = 0 */
+	uint32_t melt_sequence;               /* the lowest sequence among the products attaining melt; 0 if products = 0 */
+	float    dimer_tm;                    /* max tm_max over the cell's dimer cells; 0 when dimers are not asked for */
+	uint32_t dimer_query, dimer_target;   /* distinct-oligo ids of the dimer cell attaining it, lowest (q, t) on a tie; 0, 0 without dimers */
+	uint32_t flags;                       /* PCR_CONFLICT_PRODUCT: products > 0; PCR_CONFLICT_DIMER: dimers asked for and dimer_tm >= dimer_floor */
+	uint32_t reserved;                    /* 0 */
+} pcr_pool_conflict;
+
+#define PCR_CONFLICT_PRODUCT 1u
+#define PCR_CONFLICT_DIMER   2u
+#define PCR_CONFLICT_NO_DIMERS (-1)       /* dimer_rule: run no dimer thermodynamics */
+
+/* Which pairs of assays (pool rows) of a pool conflict: pcr_pool_products_tm's spurious products and pcr_pool_dimers' cells,
+ * reduced on the device to the unordered pairs of pool rows.  No reference counterpart beyond multiplex_compatible.
+ *   Products.  Exactly the products pcr_pool_products_tm forms for the same handle state, pool, threshold, amplicon range,
+ * args, template_strand and tm_floor: the same oligo numbering (oligo_id[2*n_pool]), tm_plus and tm_minus bit for bit, the
+ * same keeping rule !(tm_floor > 0) || v >= tm_floor with v = min(tm_plus, tm_minus) + 0.0f (no -0 appears).  Only products
+ * with intended = 0 take part.
+ *   Attribution.  O(i) = {id(F_i), id(R_i)}.  A spurious product with plus oligo x and minus oligo y belongs to the set of
+ * unordered row pairs {i, j}, i = j allowed, with (x in O(i) and y in O(j)) or (x in O(j) and y in O(i)), and counts once in
+ * each cell of that set however many ways the cell arises.  Repeated and exchanged pool rows are separate rows: an F-F
+ * product of a primer shared by rows i and j belongs to {i,i}, {i,j} and {j,j}, once each.
+ *   Dimers.  Only with dimer_rule = PCR_DIMER_RULE_POOL or PCR_DIMER_RULE_ASSAY.  The dimer cells of {a, b} are the ordered
+ * pcr_pool_dimers cells (q, t) with (q in O(a), t in O(b)) or (q in O(b), t in O(a)), the homodimer cell where q = t, out
+ * of the full matrix of pcr_pool_dimers for the same pool, args and rule with tm_floor = 0, bit for bit; dimer_tm is the
+ * highest tm_max among them.  With PCR_DIMER_RULE_POOL, pcr_multiplex_compatible(a, b) and (b, a) both hold iff
+ * dimer_tm < max_dimer.  With PCR_CONFLICT_NO_DIMERS no dimer thermodynamics run, the three dimer fields are 0 and nothing
+ * pcr_pool_dimers alone asks for is needed.
+ *   Records.  One for every cell with products > 0 and, with a dimer rule, for every cell with dimer_tm >= dimer_floor
+ * (dimer_floor <= 0: all n_pool(n_pool + 1)/2 cells), sorted by (row_a, row_b).  The reduction is a sort by (cell, sequence)
+ * and a segmented reduction over integers: the bytes do not depend on the order the device works in.
+ *   Returns the number of records or a negative error; if it exceeds cap the contents of out are unspecified (cap = 0:
+ * count only).  n_pool = 0 returns 0.
+ *   PCR_ERR_ARG, from the arguments alone and before the handle, in pcr_pool_products_tm's order (unknown set or
+ * PCR_SET_MULTIPLEX; null pointers or cap without out; n_pool > PCR_POOL_MAX_PAIRS; a negative concentration; salt outside
+ * [1e-6, 1]; an oligo that is empty, has a hole between its ends, more than PCR_SITE_MAX_EXPANSIONS expansions or a zero
+ * strand concentration; a tm_floor that is not finite); then a dimer_rule that is none of the three values; then a
+ * dimer_floor that is not finite; then, with a dimer rule, primer_strand <= 0 or primer_strand / degeneracy underflowing to
+ * zero (pcr_pool_dimers' refusals); then a null handle.  PCR_ERR_STATE without a word DB, also when only dimers would
+ * produce records: the call is about a pool on a set.  PCR_ERR_CAPACITY for 2^31 or more sites, (site, expansion) jobs or
+ * (product, cell) attributions, and with a dimer rule for 2^31 or more duplexes; PCR_ERR_RANGE if a trace-back fails inside
+ * the engine.  Changes nothing other calls read.  On a handle with a target shard attached, sequence indices are local to
+ * the rank's block and no collective is made. */
+int64_t pcr_pool_conflicts(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor,
+	int dimer_rule, float dimer_floor, uint32_t *oligo_id, pcr_pool_conflict *out, uint64_t cap);
+
 /* ---- Probe hits: which products of a pool a panel's hydrolysis probes bind inside, and which sequences each assay detects */
 
 /* One probe site inside one product (64 bytes). */

@@ -99,6 +99,13 @@ ANNEAL_POINT_DTYPE = np.dtype([("temperature", np.float32), ("reserved", np.uint
 ANNEAL_MAX_TEMPS = 256                        # PCR_ANNEAL_MAX_TEMPS
 ANNEAL_NO_PRODUCT = np.float32(-1.0)          # PCR_ANNEAL_NO_PRODUCT
 
+# pcr_pool_conflict (48 bytes)
+POOL_CONFLICT_DTYPE = np.dtype([("row_a", np.uint32), ("row_b", np.uint32), ("products", np.uint64), ("sequences", np.uint32),
+                                ("melt", np.float32), ("melt_sequence", np.uint32), ("dimer_tm", np.float32), ("dimer_query", np.uint32),
+                                ("dimer_target", np.uint32), ("flags", np.uint32), ("reserved", np.uint32)])
+CONFLICT_PRODUCT, CONFLICT_DIMER = 1, 2       # PCR_CONFLICT_PRODUCT, PCR_CONFLICT_DIMER
+CONFLICT_NO_DIMERS = -1                       # PCR_CONFLICT_NO_DIMERS
+
 # pcr_probe_hit: one probe site inside one product (Screener.probe_hits)
 PROBE_HIT_DTYPE = np.dtype([("plus_oligo", np.uint32), ("minus_oligo", np.uint32), ("probe", np.uint32), ("sequence", np.uint32),
                             ("begin", np.int32), ("end", np.int32), ("inner_start", np.int32), ("inner_length", np.int32),
@@ -177,7 +184,7 @@ ABI_SYMBOLS = [
     "pcr_thermo", "pcr_valid_words", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers",
-    "pcr_pool_products_tm", "pcr_pool_anneal_profile", "pcr_pool_probe_hits", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants",
+    "pcr_pool_products_tm", "pcr_pool_anneal_profile", "pcr_pool_conflicts", "pcr_pool_probe_hits", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats", "pcr_live_resources",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -282,6 +289,9 @@ def load_library():
     L.pcr_pool_anneal_profile.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
                                           C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]
+    L.pcr_pool_conflicts.restype = C.c_int64
+    L.pcr_pool_conflicts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
+                                     C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64]
     L.pcr_pool_probe_hits.restype = C.c_int64
     L.pcr_pool_probe_hits.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32,
                                       C.POINTER(ThermoArgs), C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
@@ -583,6 +593,54 @@ def anneal_ceiling(points, pair_sequences, keep=1.0):
     need = np.ceil(float(keep) * ps[:, 0]).astype(np.int64) if ps.shape[1] else np.zeros(len(ps), np.int64)
     ok = np.nonzero((ps >= need[:, None]).all(axis=0))[0]
     return int(ok[-1]) if len(ok) else -1
+
+
+def conflict_matrix(conflicts, n_pool, anneal=None, max_dimer=None):
+    """Screener.pool_conflicts' records -> bool [n_pool, n_pool], symmetric: which pairs of pool rows conflict.  A cell is set
+    iff it has products and (anneal is None or melt >= anneal, in float32), or max_dimer is not None and the record carries
+    CONFLICT_DIMER and dimer_tm >= max_dimer.  The diagonal is an assay against itself."""
+    n = int(n_pool)
+    m = np.zeros((n, n), bool)
+    c = np.asarray(conflicts)
+    if len(c) == 0:
+        return m
+    hit = c["products"] > 0
+    if anneal is not None:
+        hit &= c["melt"] >= np.float32(anneal)
+    if max_dimer is not None:
+        hit |= ((c["flags"] & CONFLICT_DIMER) != 0) & (c["dimer_tm"] >= np.float32(max_dimer))
+    a, b = c["row_a"][hit].astype(np.int64), c["row_b"][hit].astype(np.int64)
+    m[a, b] = True
+    m[b, a] = True
+    return m
+
+
+def assign_tubes(conflict, max_tubes=None):
+    """A conflict matrix (bool [n, n], read as symmetric: a pair conflicts if either order is set) -> (tube int32 [n],
+    self_conflict bool [n]): a split of the pool into tubes none of which holds a conflicting pair.  Greedy and
+    deterministic: the rows are taken in order of (off-diagonal degree descending, index ascending) and each goes into the
+    lowest-numbered tube that holds no row it conflicts with.  A conflict of a row with itself (the diagonal) cannot be
+    split away: it changes nothing in the assignment and is reported in self_conflict.  With max_tubes, a row that fits
+    none of the first max_tubes tubes raises ValueError naming it."""
+    m = np.asarray(conflict, bool)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError("assign_tubes: conflict must be a square matrix")
+    n = m.shape[0]
+    self_conflict = m.diagonal().copy()
+    off = m | m.T
+    off[np.arange(n), np.arange(n)] = False
+    degree = off.sum(axis=1)
+    order = sorted(range(n), key=lambda i: (-int(degree[i]), i))
+    tube = np.full(n, -1, np.int32)
+    for i in order:
+        taken = set(tube[np.nonzero(off[i])[0]].tolist())
+        t = 0
+        while t in taken:
+            t += 1
+        if max_tubes is not None and t >= int(max_tubes):
+            raise ValueError("assign_tubes: row %d does not fit into %d tubes" % (i, int(max_tubes)))
+        tube[i] = t
+    return tube, self_conflict
 
 
 # ---------------------------------------------------------------------------- assay-list writers (host only)
@@ -1126,6 +1184,51 @@ class Screener:
             raise PcrError(_err(self.L))
         out = (ids[:2 * len(pool)].copy(), points[:len(t)].copy(), pair_seq)
         return out + (fr, rf, sp) if melt else out
+
+    def pool_conflicts(self, pool, threshold=1.0, tm_floor=0.0, salt=0.05, primer_strand=9e-7, template_strand=0.0,
+                       amp_min=80, amp_max=200, dimers="pool", dimer_floor=0.0, which=TARGET, select=False, cap=None):
+        """Which assays of the pool cannot share a tube (pcr_pool_conflicts) -> (oligo_id uint32[2 * len(pool)], conflicts:
+        POOL_CONFLICT_DTYPE array sorted by (row_a, row_b)).
+
+        A record is one unordered pair of pool rows (row_a == row_b: the assay against itself).  products / sequences count
+        the spurious products pool_products_tm keeps at tm_floor between the oligos of the two rows and the sequences they lie
+        on, melt is the highest min(tm_plus, tm_minus) among them (the annealing temperature up to which the pair still
+        conflicts) and melt_sequence the lowest sequence attaining it.  `dimers` = "pool" or "assay" also melts every oligo of
+        one row against every oligo of the other (pool_dimers' cells under that rule): dimer_tm is the highest tm_max, in cell
+        (dimer_query, dimer_target); with "pool", multiplex_compatible holds for the two assays in both orders iff dimer_tm <
+        max_dimer.  dimers=None runs no dimer thermodynamics.  Records: the cells with a product, and with dimers those with
+        dimer_tm >= dimer_floor (dimer_floor <= 0: every cell).  `select` as for pool_products_tm.  conflict_matrix and
+        assign_tubes turn the records into a split of the pool."""
+        rules = {"pool": DIMER_RULE_POOL, "assay": DIMER_RULE_ASSAY, None: CONFLICT_NO_DIMERS, DIMER_RULE_POOL: DIMER_RULE_POOL,
+                 DIMER_RULE_ASSAY: DIMER_RULE_ASSAY, CONFLICT_NO_DIMERS: CONFLICT_NO_DIMERS}
+        if dimers not in rules:
+            raise ValueError("pool_conflicts: dimers must be 'pool', 'assay' or None")
+        thr2 = float(np.float32(threshold) * np.float32(threshold))
+        if isinstance(select, str):
+            if select != "all":
+                raise ValueError("pool_conflicts: select must be True, False or 'all'")
+            self.select_sites(pool, thr2, which=which)
+        elif select:
+            self.select_words(pool, thr2, which=which)
+        a = W.pairs_array(pool)
+        ids = np.zeros(max(2 * len(pool), 1), np.uint32)
+        args = self._targs(salt, primer_strand, 0.0, 0.0, 0.0, 0.0)
+        call = lambda out, cap: self.L.pcr_pool_conflicts(self.h, which, a.ctypes.data, len(pool), float(threshold), int(amp_min),
+                                                          int(amp_max), C.byref(args), float(template_strand), float(tm_floor),
+                                                          rules[dimers], float(dimer_floor), ids.ctypes.data, out, cap)
+        if cap is None:                                                    # the count sizes the buffer
+            n = call(None, 0)
+            if n < 0:
+                raise PcrError(_err(self.L))
+            cap = int(n)
+        while True:
+            out = np.zeros(max(cap, 1), POOL_CONFLICT_DTYPE)
+            n = call(out.ctypes.data, cap)
+            if n < 0:
+                raise PcrError(_err(self.L))
+            if n <= cap:
+                return ids[:2 * len(pool)].copy(), out[:n].copy()
+            cap = int(n)                                                   # the count: one retry
 
     def probe_hits(self, pool, probes, threshold=1.0, tm_floor=0.0, probe_tm_floor=0.0, salt=0.05, primer_strand=9e-7,
                    probe_strand=2.5e-7, template_strand=0.0, amp_min=80, amp_max=200, which=TARGET, select=False,

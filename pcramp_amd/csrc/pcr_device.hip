@@ -860,6 +860,13 @@ struct pcr_ctx {
 	// the histograms and per-temperature sums, pair_sequences.  (After ppc_*, for the same reason.)
 	DevBuf<uint8_t> anp_in, anp_tmp; DevBuf<uint32_t> anp_cnt, anp_flag, anp_pairseq; DevBuf<uint64_t> anp_eoff, anp_joff, anp_out;
 	DevBuf<uint2> anp_items; DevBuf<float4> anp_res; DevBuf<uint2> anp_item_tm; DevBuf<float> anp_melt;
+	// pcr_pool_conflicts (pcr_pool_conflicts.inc): oligo tables + each row's oligos + intended bitmap + the rows of every oligo, per-entry / per-item counts
+	// and offsets, items, job offsets, per-job results, per-item Tm, error flags, attribution offsets, (cell, sequence) keys and melt bits, the cells with a
+	// product and their aggregates, the dense aggregates; pcr_pool_dimers' tables, per-duplex results, per-cell records and keep words, the dense tm_max
+	// matrix; the cells' records, keep words and their scan, the kept records.  (After anp_*, for the same reason.)
+	DevBuf<uint8_t> pcf_in, pcf_tmp, pcf_din; DevBuf<uint32_t> pcf_cnt, pcf_flag, pcf_vals, pcf_ucell, pcf_dkeep, pcf_keep, pcf_koff;
+	DevBuf<uint64_t> pcf_eoff, pcf_joff, pcf_aoff, pcf_keys; DevBuf<uint2> pcf_items, pcf_item_tm; DevBuf<float4> pcf_res, pcf_dres;
+	DevBuf<uint4> pcf_uagg, pcf_dense; DevBuf<pcr_pool_dimer> pcf_drec; DevBuf<float> pcf_dmat; DevBuf<pcr_pool_conflict> pcf_rec, pcf_out;
 };
 
 namespace {
@@ -2184,6 +2191,7 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_pool_dimers.inc"
 #include "pcr_products_tm.inc"
 #include "pcr_anneal_profile.inc"
+#include "pcr_pool_conflicts.inc"
 #include "pcr_probe_hits.inc"
 #include "pcr_pool_amplicons.inc"
 #include "pcr_probe_candidates.inc"

@@ -1,0 +1,571 @@
+// Which assays of a primer pool cannot share a tube: the pool's spurious products and its oligo-by-oligo dimers reduced to
+// unordered pairs of pool rows on the device (pcr_pool_conflicts; included by pcr_device.hip after pcr_anneal_profile.inc, whose
+// way of launching pcr_products_tm.inc's steps 1-3 it follows, and after pcr_pool_dimers.inc, whose plan and kernels it runs).
+//
+// A spurious product (plus oligo x, minus oligo y) belongs to every unordered row pair {i, j} with (x in O(i), y in O(j)) or
+// (x in O(j), y in O(i)): the unordered pairs of rows(x) x rows(y).  The ordered walk meets {i, j} twice exactly when (j, i) is
+// in rows(x) x rows(y) as well; the copy with i > j is dropped then, which needs the two rows' oligo ids and no memory.
+//   1-3. the items, the jobs, k_site_tm, k_item_tm -> item_tm[] (pcr_products_tm.inc's steps, on this call's own scratch).
+//   4. k_conflict_join<false> / <true>: k_products_join's geometry and tests with the floor; a kept product that is no pool pair's
+//      walks rows(x) x rows(y).  Count pass, scan, emit pass: one (cell << seq_bits | sequence, bits of v) pair per attribution.
+//   5. rocprim::radix_sort_pairs by (cell, sequence), then rocprim::reduce_by_key over the cells with {max of (v bits << 32 |
+//      ~sequence), count, count of (cell, sequence) run heads}: products, sequences, melt and melt_sequence of every cell with a
+//      product.  v >= +0 (v + 0.0f), so the floats order like their bits; every operand is an integer and the operator is
+//      associative and commutative: the bytes do not depend on the order the device works in, and no atomic is made.  A cell fed
+//      by every product of a large family is a long run of the sorted keys, reduced like any other run.
+//   6. k_conflict_scatter puts the aggregates into a dense array over the n_pool(n_pool + 1)/2 cells.
+//   7. With a dimer rule: pcr_pool_dimers' plan, k_pool_dimer and k_pool_dimer_reduce batch by batch as they stand;
+//      k_conflict_dimer_store keeps tm_max of every cell in a dense n_ol x n_ol matrix on the device.
+//   8. k_conflict_cells: a thread per cell a <= b joins the aggregate with the maximum of the cell's (up to eight) dimer cells,
+//      the lowest (q, t) on a tie, and sets the flags and the keep word; an exclusive scan and k_conflict_compact put the kept
+//      cells into (row_a, row_b) order.
+// The call owns its scratch (pcr_ctx::pcf_*); the dG table is the handle's (th_dg, keyed by its salt).
+
+#include <rocprim/device/device_reduce_by_key.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+namespace {
+
+constexpr uint32_t PCF_CELL_BITS = 20;
+static_assert((uint64_t)PCR_POOL_MAX_PAIRS*(PCR_POOL_MAX_PAIRS + 1)/2 <= (1ull << PCF_CELL_BITS), "a cell index fits PCF_CELL_BITS");
+constexpr uint64_t PCF_MAX_ATTRIBUTIONS = 1ull << 31;
+
+// what the cells of a run of attributions reduce to: best = bits of v << 32 | ~sequence (the highest v, then the lowest sequence)
+struct alignas(16) ConflictAgg { unsigned long long best; uint32_t products, sequences; };
+
+// the index of the unordered row pair a <= b among the n(n + 1)/2 cells, in (a, b) order
+__host__ __device__ inline uint32_t pcf_cell(uint32_t a, uint32_t b, uint32_t n) { return a*n - (a*(a - 1u))/2u + (b - a); }
+
+struct PcfCellOf {
+	uint32_t shift;
+	__host__ __device__ uint32_t operator()(const uint64_t &k) const { return (uint32_t)(k >> shift); }
+};
+struct PcfAggOf {
+	const uint64_t *key; const uint32_t *val; uint64_t seq_mask;
+	__host__ __device__ ConflictAgg operator()(const uint32_t &i) const
+	{
+		const uint64_t k = key[i];
+		ConflictAgg a;
+		a.best = ((unsigned long long)val[i] << 32) | (uint32_t)~(uint32_t)(k & seq_mask);
+		a.products = 1u;
+		a.sequences = (i == 0u || key[i - 1u] != k) ? 1u : 0u;                      // the first attribution of its (cell, sequence)
+		return a;
+	}
+};
+struct PcfMerge {
+	__host__ __device__ ConflictAgg operator()(const ConflictAgg &a, const ConflictAgg &b) const
+	{
+		ConflictAgg r;
+		r.best = (a.best > b.best) ? a.best : b.best;
+		r.products = a.products + b.products;
+		r.sequences = a.sequences + b.sequences;
+		return r;
+	}
+};
+
+// k_products_join with the floor, over the spurious kept products only: one thread per item k, a plus-strand item (i, x) against
+// the minus-strand items (j, y) of its segment.  Every attribution of a product to a cell: <false> counts it, <true> writes its
+// key and the bits of v at att_off[k] ..
+template<bool EMIT>
+__global__ __launch_bounds__(POOL_THREADS) void k_conflict_join(const DevEntry *__restrict__ db, uint32_t cap, const uint32_t *__restrict__ touched,
+	const uint32_t *__restrict__ seg_hi, const uint2 *__restrict__ items, uint32_t n_items, const uint64_t *__restrict__ item_off,
+	const PoolOligo *__restrict__ oligos, uint32_t n_ol, const uint4 *__restrict__ planes, const uint64_t *__restrict__ blk_off,
+	const uint64_t *__restrict__ len, const uint8_t *__restrict__ has_eos, int32_t amp_min, int32_t amp_max,
+	const ItemTm *__restrict__ item_tm, float tm_floor, const uint32_t *__restrict__ intended, const uint32_t *__restrict__ rows_off,
+	const uint32_t *__restrict__ rows, const uint2 *__restrict__ row_ol, uint32_t n_pool, uint32_t seq_bits,
+	uint32_t *__restrict__ count, const uint64_t *__restrict__ att_off, uint64_t *__restrict__ key, uint32_t *__restrict__ val)
+{
+	__shared__ int2 ss[POOL_MAX_OLIGOS];                                        // Word::start() / stop()
+	for(uint32_t o = threadIdx.x;o < n_ol;o += blockDim.x) ss[o] = make_int2(oligos[o].start, oligos[o].stop);
+	__syncthreads();
+	const uint32_t k = blockIdx.x*blockDim.x + threadIdx.x;
+	if(k >= n_items) return;
+	const uint2 it = items[k];
+	const uint32_t g = it.x, x = it.y;
+	const uint32_t i = touched[g/cap]*cap + g % cap;
+	const DevEntry ei = db[i];
+	uint32_t c = 0;
+	uint64_t w = EMIT ? att_off[k] : 0;
+	if(ei.strand == 1){
+		const uint32_t hi = seg_hi[ei.seq];
+		const int32_t L = (int32_t)len[ei.seq];
+		const uint64_t blk_base = blk_off[ei.seq];
+		const bool eos = has_eos[ei.seq] != 0;
+		const int2 P = ss[x];
+		const int32_t p5 = ei.loc + P.x, p3 = ei.loc + P.y;                      // template_loc5/3, sequence.h:57-75
+		const ItemTm tp = item_tm[k];
+		const bool floored = tm_floor > 0.0f;
+		const uint32_t x0 = rows_off[x], x1 = rows_off[x + 1];
+		if(!(floored && tp.tm < tm_floor)){                                      // (a plus site below the floor keeps no product)
+			for(uint32_t j = i + 1;j < hi;++j){
+				const DevEntry ej = db[j];
+				if(ej.loc - ei.loc > amp_max + 128) break;
+				if(ej.strand != 2) continue;
+				const uint32_t gj = g + (j - i);                                     // same segment: consecutive DB threads
+				const uint64_t t_end = item_off[gj + 1];
+				for(uint64_t t = item_off[gj];t < t_end;++t){
+					const uint32_t y = items[t].y;
+					const int2 M = ss[y];
+					const int32_t m5 = ej.loc - M.y, m3 = ej.loc - M.x;
+					if(p3 >= m5) continue;                                           // pcr_assay.cpp:468-471
+					const int32_t amp_len = m3 - p5 + 1;
+					if(amp_len < amp_min || amp_len > amp_max) continue;             // :477-484
+					const int32_t in_start = p3 + 1 - 4;                             // :489-490
+					const int32_t in_len = m5 - in_start + 8;                        // :492-494
+					if(in_start < 0 || in_len < 0 || in_start + in_len > L) continue;
+					if(eos && has_split(planes, blk_base, in_start, in_len)) continue;   // :504-521
+					const uint32_t b = x*n_ol + y;
+					if((intended[b >> 5] >> (b & 31)) & 1u) continue;                // a pool pair's own product is no conflict
+					const ItemTm tm = item_tm[t];
+					const float v = ((tp.tm < tm.tm) ? tp.tm : tm.tm) + 0.0f;        // k_products_join's min; + 0.0f: -0 -> +0 (contraction is off)
+					if(floored && !(v >= tm_floor)) continue;
+					const uint32_t y0 = rows_off[y], y1 = rows_off[y + 1];
+					for(uint32_t ia = x0;ia < x1;++ia){
+						const uint32_t ri = rows[ia];
+						for(uint32_t ja = y0;ja < y1;++ja){
+							const uint32_t rj = rows[ja];
+							if(ri > rj){
+								// {rj, ri} arises again as (rj in rows(x), ri in rows(y)): that copy, with the lower row first, is the one kept
+								const uint2 oj = row_ol[rj], oi = row_ol[ri];
+								if((oj.x == x || oj.y == x) && (oi.x == y || oi.y == y)) continue;
+							}
+							if(EMIT){
+								const uint32_t cell = (ri <= rj) ? pcf_cell(ri, rj, n_pool) : pcf_cell(rj, ri, n_pool);
+								key[w] = ((uint64_t)cell << seq_bits) | ei.seq;
+								val[w] = __float_as_uint(v);
+								++w;
+							}
+							else ++c;
+						}
+					}
+				}
+			}
+		}
+	}
+	if(!EMIT) count[k] = c;
+}
+
+// the aggregates of the cells that have a product -> their places in the dense array (zero elsewhere)
+__global__ __launch_bounds__(POOL_THREADS) void k_conflict_scatter(const uint32_t *__restrict__ ucell, const ConflictAgg *__restrict__ uagg,
+	const uint32_t *__restrict__ n_unique, uint32_t n_cells, ConflictAgg *__restrict__ dense)
+{
+	const uint32_t n = *n_unique;
+	for(uint32_t u = blockIdx.x*blockDim.x + threadIdx.x;u < n;u += gridDim.x*blockDim.x){
+		const uint32_t c = ucell[u];
+		if(c < n_cells) dense[c] = uagg[u];
+	}
+}
+
+// tm_max of a batch's cells c0 .. c0 + n_cells - 1 (c = q*n_ol + t) into the dense matrix
+__global__ __launch_bounds__(POOL_THREADS) void k_conflict_dimer_store(const pcr_pool_dimer *__restrict__ rec, uint32_t n_cells, float *__restrict__ mat)
+{
+	const uint32_t k = blockIdx.x*blockDim.x + threadIdx.x;
+	if(k < n_cells) mat[k] = rec[k].tm_max;
+}
+
+// Cell {a, b}, a = blockIdx.y <= b: the record and its keep word.  dmat = NULL: no dimers were asked for.
+__global__ __launch_bounds__(POOL_THREADS) void k_conflict_cells(const ConflictAgg *__restrict__ dense, const float *__restrict__ dmat, uint32_t n_ol,
+	const uint2 *__restrict__ row_ol, uint32_t n_pool, float dimer_floor, pcr_pool_conflict *__restrict__ rec, uint32_t *__restrict__ keep)
+{
+	const uint32_t a = blockIdx.y, b = blockIdx.x*blockDim.x + threadIdx.x;
+	if(b >= n_pool || b < a) return;
+	const uint32_t c = pcf_cell(a, b, n_pool);
+	const ConflictAgg g = dense[c];
+	pcr_pool_conflict r;
+	r.row_a = a; r.row_b = b;
+	r.products = g.products; r.sequences = g.sequences;
+	r.melt = g.products ? __uint_as_float((uint32_t)(g.best >> 32)) : PCR_ANNEAL_NO_PRODUCT;
+	r.melt_sequence = g.products ? ~(uint32_t)g.best : 0u;
+	r.dimer_tm = 0.0f; r.dimer_query = r.dimer_target = 0u;
+	r.flags = g.products ? PCR_CONFLICT_PRODUCT : 0u;
+	r.reserved = 0u;
+	bool kept = g.products != 0u;
+	if(dmat){
+		const uint2 oa = row_ol[a], ob = row_ol[b];
+		// the (up to eight) ordered cells as q*n_ol + t, ascending: the first of the highest values is the lowest (q, t) on a tie
+		uint32_t cell[8] = {oa.x*n_ol + ob.x, oa.x*n_ol + ob.y, oa.y*n_ol + ob.x, oa.y*n_ol + ob.y,
+			ob.x*n_ol + oa.x, ob.y*n_ol + oa.x, ob.x*n_ol + oa.y, ob.y*n_ol + oa.y};
+		for(int i = 1;i < 8;++i){
+			for(int j = i;j > 0 && cell[j - 1] > cell[j];--j){ const uint32_t s = cell[j]; cell[j] = cell[j - 1]; cell[j - 1] = s; }
+		}
+		for(int i = 0;i < 8;++i){
+			const float tm = dmat[cell[i]];
+			if(i == 0 || tm > r.dimer_tm){ r.dimer_tm = tm; r.dimer_query = cell[i]/n_ol; r.dimer_target = cell[i] % n_ol; }
+		}
+		if(r.dimer_tm >= dimer_floor) r.flags |= PCR_CONFLICT_DIMER;
+		if(!(dimer_floor > 0.0f) || r.dimer_tm >= dimer_floor) kept = true;
+	}
+	rec[c] = r;
+	keep[c] = kept ? 1u : 0u;
+}
+
+// the kept cells, in cell order: off = exclusive scan of keep
+__global__ __launch_bounds__(POOL_THREADS) void k_conflict_compact(const pcr_pool_conflict *__restrict__ rec, const uint32_t *__restrict__ keep,
+	const uint32_t *__restrict__ off, uint32_t n_cells, pcr_pool_conflict *__restrict__ out)
+{
+	const uint32_t k = blockIdx.x*blockDim.x + threadIdx.x;
+	if(k < n_cells && keep[k]) out[off[k]] = rec[k];
+}
+
+// Steps 1-6: the aggregates of the spurious kept products in ctx->pcf_dense[0 .. n_cells) (zero where a cell has none).
+int conflict_products(pcr_ctx *ctx, SeqSet &S, const std::vector<PoolOligo> &ol, const std::vector<SiteOligoX> &olx, const uint32_t *oligo_id,
+	uint32_t n_pool, int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float tm_floor, uint32_t n_cells)
+{
+	int rc;
+	const uint32_t n_ol = (uint32_t)ol.size();
+	// the intended bitmap; the rows of every distinct oligo (a row with F = R once); each row's two oligos
+	std::vector<uint32_t> intended(((size_t)n_ol*n_ol + 31)/32, 0), rows_off(n_ol + 1, 0), rows;
+	std::vector<uint2> row_ol(n_pool);
+	for(uint32_t i = 0;i < n_pool;++i){
+		const uint32_t f = oligo_id[2*i], r = oligo_id[2*i + 1];
+		for(uint32_t b : {f*n_ol + r, r*n_ol + f}) intended[b >> 5] |= 1u << (b & 31);
+		row_ol[i] = make_uint2(f, r);
+		++rows_off[f + 1];
+		if(r != f) ++rows_off[r + 1];
+	}
+	for(uint32_t o = 0;o < n_ol;++o) rows_off[o + 1] += rows_off[o];
+	rows.resize(rows_off[n_ol]);
+	{
+		std::vector<uint32_t> at(rows_off.begin(), rows_off.end() - 1);
+		for(uint32_t i = 0;i < n_pool;++i){                                       // (ascending rows within an oligo)
+			const uint32_t f = oligo_id[2*i], r = oligo_id[2*i + 1];
+			rows[at[f]++] = i;
+			if(r != f) rows[at[r]++] = i;
+		}
+	}
+	const size_t ol_bytes = ol.size()*sizeof(PoolOligo), olx_bytes = olx.size()*sizeof(SiteOligoX), rol_bytes = row_ol.size()*sizeof(uint2),
+		int_bytes = intended.size()*sizeof(uint32_t), off_bytes = rows_off.size()*sizeof(uint32_t), rows_bytes = rows.size()*sizeof(uint32_t);
+	std::vector<uint8_t> blob(ol_bytes + olx_bytes + rol_bytes + int_bytes + off_bytes + rows_bytes);   // 32-, 8-, 8-, 4-, 4- and 4-byte records, in that order: each is aligned
+	memcpy(blob.data(), ol.data(), ol_bytes);
+	memcpy(blob.data() + ol_bytes, olx.data(), olx_bytes);
+	memcpy(blob.data() + ol_bytes + olx_bytes, row_ol.data(), rol_bytes);
+	memcpy(blob.data() + ol_bytes + olx_bytes + rol_bytes, intended.data(), int_bytes);
+	memcpy(blob.data() + ol_bytes + olx_bytes + rol_bytes + int_bytes, rows_off.data(), off_bytes);
+	memcpy(blob.data() + ol_bytes + olx_bytes + rol_bytes + int_bytes + off_bytes, rows.data(), rows_bytes);
+	if((rc = ctx->pcf_in.ensure(blob.size())) != PCR_OK) return rc;
+	const PoolOligo *d_ol = (const PoolOligo *)ctx->pcf_in.p;
+	const SiteOligoX *d_olx = (const SiteOligoX *)(ctx->pcf_in.p + ol_bytes);
+	const uint2 *d_row_ol = (const uint2 *)(ctx->pcf_in.p + ol_bytes + olx_bytes);
+	const uint32_t *d_intended = (const uint32_t *)(ctx->pcf_in.p + ol_bytes + olx_bytes + rol_bytes);
+	const uint32_t *d_rows_off = (const uint32_t *)(ctx->pcf_in.p + ol_bytes + olx_bytes + rol_bytes + int_bytes);
+	const uint32_t *d_rows = (const uint32_t *)(ctx->pcf_in.p + ol_bytes + olx_bytes + rol_bytes + int_bytes + off_bytes);
+	HIP_TRY(hipMemcpyAsync(ctx->pcf_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));                                   // (blob is this function's)
+	if(S.n_entries == 0 || S.n_touched == 0) return PCR_OK;
+	// ---- 1. the items (k_pool_entry_oligos: count, scan, fill)
+	const uint32_t n_db = S.n_touched*S.db_cap;
+	if((rc = ctx->pcf_cnt.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
+	if((rc = ctx->pcf_eoff.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->pcf_cnt.p + n_db, 0, sizeof(uint32_t), ctx->stream));
+	size_t tmp = 0;
+	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pcf_cnt.p, ctx->pcf_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	if((rc = ctx->pcf_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
+	const unsigned grid_e = std::min<unsigned>((n_db + POOL_THREADS - 1)/POOL_THREADS, ctx->n_cu*8);
+	hipLaunchKernelGGL(k_pool_entry_oligos<false>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
+		S.d_seg_hi, S.d_active.p, d_ol, n_ol, ctx->pcf_cnt.p, (const uint64_t *)nullptr, (uint2 *)nullptr);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(rocprim::exclusive_scan(ctx->pcf_tmp.p, tmp, ctx->pcf_cnt.p, ctx->pcf_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	uint64_t n_items = 0;
+	HIP_TRY(hipMemcpyAsync(&n_items, ctx->pcf_eoff.p + n_db, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if(n_items >= POOL_MAX_ITEMS){ g_err = "pcr_pool_conflicts: too many (entry, oligo) hits"; return PCR_ERR_CAPACITY; }
+	if(n_items == 0) return PCR_OK;
+	if((rc = ctx->pcf_items.ensure(n_items)) != PCR_OK) return rc;
+	hipLaunchKernelGGL(k_pool_entry_oligos<true>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
+		S.d_seg_hi, S.d_active.p, d_ol, n_ol, (uint32_t *)nullptr, (const uint64_t *)ctx->pcf_eoff.p, ctx->pcf_items.p);
+	HIP_TRY(hipGetLastError());
+	const uint32_t ni = (uint32_t)n_items;
+	const unsigned grid_i = (ni + POOL_THREADS - 1)/POOL_THREADS;
+	if((rc = ctx->pcf_cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;         // (the entry counts are spent)
+	// ---- 2. job offsets, the jobs (k_site_jobs, k_site_tm as they stand)
+	if((rc = ctx->pcf_joff.ensure((size_t)ni + 1)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->pcf_cnt.p + ni, 0, sizeof(uint32_t), ctx->stream));
+	hipLaunchKernelGGL(k_site_jobs, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint2 *)ctx->pcf_items.p, ni, d_olx, ctx->pcf_cnt.p);
+	HIP_TRY(hipGetLastError());
+	tmp = 0;
+	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pcf_cnt.p, ctx->pcf_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	if((rc = ctx->pcf_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
+	HIP_TRY(rocprim::exclusive_scan(ctx->pcf_tmp.p, tmp, ctx->pcf_cnt.p, ctx->pcf_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	uint64_t n_jobs64 = 0;
+	HIP_TRY(hipMemcpyAsync(&n_jobs64, ctx->pcf_joff.p + ni, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if(n_jobs64 >= POOL_MAX_ITEMS){ g_err = "pcr_pool_conflicts: too many (site, expansion) jobs"; return PCR_ERR_CAPACITY; }
+	const uint32_t n_jobs = (uint32_t)n_jobs64;
+	if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
+	if(!ctx->site_attr_set){                                                   // (k_site_tm's own flag: the attribute is the kernel's)
+		HIP_TRY(hipFuncSetAttribute((const void *)k_site_tm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SITE_LDS));
+		ctx->site_attr_set = true;
+	}
+	if((rc = ctx->pcf_res.ensure(n_jobs)) != PCR_OK) return rc;
+	if((rc = ctx->pcf_item_tm.ensure(ni)) != PCR_OK) return rc;
+	// at most one block per CU (a block takes most of a CU's LDS), the waves striding over the jobs
+	const unsigned grid_j = std::max(1u, std::min<unsigned>((n_jobs + SITE_WAVES - 1)/SITE_WAVES, (unsigned)ctx->n_cu));
+	hipLaunchKernelGGL(k_site_tm, dim3(grid_j), dim3(SITE_THREADS), SITE_LDS, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
+		(const uint2 *)ctx->pcf_items.p, ni, (const uint64_t *)ctx->pcf_joff.p, n_jobs, d_ol, d_olx, (const int *)ctx->th_dg.p, logf(args->salt), ctx->pcf_res.p);
+	HIP_TRY(hipGetLastError());
+	// ---- 3. Tm per item
+	hipLaunchKernelGGL(k_item_tm, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint64_t *)ctx->pcf_joff.p, ni,
+		(const float4 *)ctx->pcf_res.p, (ItemTm *)ctx->pcf_item_tm.p, ctx->pcf_flag.p);
+	HIP_TRY(hipGetLastError());
+	// ---- 4. the join: count, scan, emit
+	const uint32_t seq_bits = pool_bits(S.n);
+	if((rc = ctx->pcf_aoff.ensure((size_t)ni + 1)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->pcf_cnt.p + ni, 0, sizeof(uint32_t), ctx->stream));
+	hipLaunchKernelGGL(k_conflict_join<false>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
+		ctx->pcf_items.p, ni, (const uint64_t *)ctx->pcf_eoff.p, d_ol, n_ol, S.planes.p, S.d_blk_off.p, S.d_len.p, S.d_has_eos.p,
+		amp_min, amp_max, (const ItemTm *)ctx->pcf_item_tm.p, tm_floor, d_intended, d_rows_off, d_rows, d_row_ol, n_pool, seq_bits,
+		ctx->pcf_cnt.p, (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr);
+	HIP_TRY(hipGetLastError());
+	tmp = 0;
+	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pcf_cnt.p, ctx->pcf_aoff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	if((rc = ctx->pcf_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
+	HIP_TRY(rocprim::exclusive_scan(ctx->pcf_tmp.p, tmp, ctx->pcf_cnt.p, ctx->pcf_aoff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	uint64_t total = 0;
+	uint32_t bad = 0;
+	HIP_TRY(hipMemcpyAsync(&total, ctx->pcf_aoff.p + ni, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipMemcpyAsync(&bad, ctx->pcf_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if(bad & 1u){ g_err = "pcr_pool_conflicts: internal trace-back error"; return PCR_ERR_RANGE; }
+	if(total >= PCF_MAX_ATTRIBUTIONS){ g_err = "pcr_pool_conflicts: 2^31 or more (product, cell) attributions"; return PCR_ERR_CAPACITY; }
+	if(total == 0) return PCR_OK;
+	const uint32_t na = (uint32_t)total;
+	if((rc = ctx->pcf_keys.ensure(2*(size_t)na)) != PCR_OK) return rc;
+	if((rc = ctx->pcf_vals.ensure(2*(size_t)na)) != PCR_OK) return rc;
+	uint64_t *k0 = ctx->pcf_keys.p, *k1 = k0 + na;
+	uint32_t *v0 = ctx->pcf_vals.p, *v1 = v0 + na;
+	hipLaunchKernelGGL(k_conflict_join<true>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
+		ctx->pcf_items.p, ni, (const uint64_t *)ctx->pcf_eoff.p, d_ol, n_ol, S.planes.p, S.d_blk_off.p, S.d_len.p, S.d_has_eos.p,
+		amp_min, amp_max, (const ItemTm *)ctx->pcf_item_tm.p, tm_floor, d_intended, d_rows_off, d_rows, d_row_ol, n_pool, seq_bits,
+		(uint32_t *)nullptr, (const uint64_t *)ctx->pcf_aoff.p, k0, v0);
+	HIP_TRY(hipGetLastError());
+	// ---- 5. (cell, sequence) order, then one aggregate per cell
+	const uint32_t n_slots = std::min(na, n_cells);                              // the cells with a product
+	if((rc = ctx->pcf_ucell.ensure((size_t)n_slots + 1)) != PCR_OK) return rc;   // (+ the count)
+	if((rc = ctx->pcf_uagg.ensure(n_slots)) != PCR_OK) return rc;
+	uint32_t *d_n_unique = ctx->pcf_ucell.p + n_slots;
+	const auto cells_in = rocprim::make_transform_iterator((const uint64_t *)k1, PcfCellOf{seq_bits});
+	PcfAggOf agg_of; agg_of.key = k1; agg_of.val = v1; agg_of.seq_mask = (1ull << seq_bits) - 1ull;
+	const auto aggs_in = rocprim::make_transform_iterator(rocprim::make_counting_iterator(uint32_t(0)), agg_of);
+	size_t t1 = 0, t2 = 0;
+	HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, k0, k1, v0, v1, na, 0, seq_bits + PCF_CELL_BITS, ctx->stream));
+	HIP_TRY(rocprim::reduce_by_key(nullptr, t2, cells_in, aggs_in, na, ctx->pcf_ucell.p, (ConflictAgg *)ctx->pcf_uagg.p, d_n_unique,
+		PcfMerge(), rocprim::equal_to<uint32_t>(), ctx->stream));
+	if((rc = ctx->pcf_tmp.ensure(std::max(t1, t2) + 16)) != PCR_OK) return rc;
+	HIP_TRY(rocprim::radix_sort_pairs(ctx->pcf_tmp.p, t1, k0, k1, v0, v1, na, 0, seq_bits + PCF_CELL_BITS, ctx->stream));
+	HIP_TRY(rocprim::reduce_by_key(ctx->pcf_tmp.p, t2, cells_in, aggs_in, na, ctx->pcf_ucell.p, (ConflictAgg *)ctx->pcf_uagg.p, d_n_unique,
+		PcfMerge(), rocprim::equal_to<uint32_t>(), ctx->stream));
+	// ---- 6. into the dense array
+	const unsigned grid_u = std::max(1u, std::min<unsigned>((n_slots + POOL_THREADS - 1)/POOL_THREADS, ctx->n_cu*8));
+	hipLaunchKernelGGL(k_conflict_scatter, dim3(grid_u), dim3(POOL_THREADS), 0, ctx->stream, (const uint32_t *)ctx->pcf_ucell.p,
+		(const ConflictAgg *)ctx->pcf_uagg.p, (const uint32_t *)d_n_unique, n_cells, (ConflictAgg *)ctx->pcf_dense.p);
+	HIP_TRY(hipGetLastError());
+	return PCR_OK;
+}
+
+// Step 7: tm_max of every ordered cell of pcr_pool_dimers' matrix (tm_floor = 0) in ctx->pcf_dmat[n_ol*n_ol].  The plan is
+// pcr_pool_dimers', restated: the kernels read it as that call uploads it.
+int conflict_dimers(pcr_ctx *ctx, const pcr_thermo_args *args, const std::vector<DimerOligo> &ol, const std::vector<uint32_t> &pref, const std::vector<uint32_t> &row, const std::vector<float> &logs, uint32_t n_cls)
+{
+	int rc;
+	const uint32_t n = (uint32_t)ol.size();
+	const uint64_t n_cells = (uint64_t)n*n;
+	const size_t ol_bytes = (size_t)n*sizeof(DimerOligo), pre_bytes = (size_t)(n + 1)*sizeof(uint32_t), log_bytes = logs.size()*sizeof(float);
+	std::vector<uint8_t> blob(ol_bytes + 2*pre_bytes + log_bytes);
+	memcpy(blob.data(), ol.data(), ol_bytes);
+	memcpy(blob.data() + ol_bytes, pref.data(), pre_bytes);
+	memcpy(blob.data() + ol_bytes + pre_bytes, row.data(), pre_bytes);
+	memcpy(blob.data() + ol_bytes + 2*pre_bytes, logs.data(), log_bytes);
+	if((rc = ctx->pcf_din.ensure(blob.size())) != PCR_OK) return rc;
+	HIP_TRY(hipMemcpyAsync(ctx->pcf_din.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));                                   // (blob is this function's)
+	DimerPlan P;
+	P.ol = (const DimerOligo *)ctx->pcf_din.p;
+	P.pref = (const uint32_t *)(ctx->pcf_din.p + ol_bytes);
+	P.row = (const uint32_t *)(ctx->pcf_din.p + ol_bytes + pre_bytes);
+	P.log_off = (const float *)(ctx->pcf_din.p + ol_bytes + 2*pre_bytes);
+	P.log_diag = P.log_off + (size_t)n_cls*n_cls;
+	P.n = n; P.n_cls = n_cls;
+	if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
+	if(!ctx->pdim_attr_set){                                                   // (k_pool_dimer's own flag: the attribute is the kernel's)
+		HIP_TRY(hipFuncSetAttribute((const void *)k_pool_dimer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PDIM_LDS));
+		ctx->pdim_attr_set = true;
+	}
+	if((rc = ctx->pcf_dmat.ensure(n_cells)) != PCR_OK) return rc;
+	auto before = [&](uint64_t c) -> uint32_t {
+		if(c >= n_cells) return row[n];
+		const uint32_t q = (uint32_t)(c/n), t = (uint32_t)(c % n);
+		return pdim_before(row.data(), pref.data(), q, t, ol[q].n_exp);
+	};
+	const float log_na = logf(args->salt);
+	uint64_t c0 = 0;
+	while(c0 < n_cells){
+		// ---- a batch: cells c0 .. c1 - 1; it closes before the cell that would take it past POOL_DIMER_BATCH_JOBS duplexes
+		const uint32_t j0 = before(c0);
+		uint64_t c1 = c0 + 1, above = n_cells + 1;
+		while(above - c1 > 1){
+			const uint64_t mid = c1 + (above - c1)/2;
+			if(before(mid) - j0 <= POOL_DIMER_BATCH_JOBS) c1 = mid; else above = mid;
+		}
+		const uint32_t n_jobs = before(c1) - j0, nc = (uint32_t)(c1 - c0);
+		if((rc = ctx->pcf_dres.ensure(n_jobs)) != PCR_OK) return rc;
+		if((rc = ctx->pcf_drec.ensure(nc)) != PCR_OK) return rc;
+		if((rc = ctx->pcf_dkeep.ensure((size_t)nc + 1)) != PCR_OK) return rc;
+		const unsigned grid_j = std::max(1u, std::min<unsigned>((n_jobs + PDIM_WAVES - 1)/PDIM_WAVES, (unsigned)ctx->n_cu));
+		hipLaunchKernelGGL(k_pool_dimer, dim3(grid_j), dim3(PDIM_THREADS), PDIM_LDS, ctx->stream, P, j0, n_jobs, (const int *)ctx->th_dg.p, log_na, ctx->pcf_dres.p);
+		HIP_TRY(hipGetLastError());
+		const unsigned grid_c = (nc + POOL_THREADS - 1)/POOL_THREADS;
+		hipLaunchKernelGGL(k_pool_dimer_reduce, dim3(grid_c), dim3(POOL_THREADS), 0, ctx->stream, P, (uint32_t)c0, nc, j0, (const float4 *)ctx->pcf_dres.p,
+			0.0f, ctx->pcf_drec.p, ctx->pcf_dkeep.p, ctx->pcf_flag.p + 1);
+		HIP_TRY(hipGetLastError());
+		hipLaunchKernelGGL(k_conflict_dimer_store, dim3(grid_c), dim3(POOL_THREADS), 0, ctx->stream, (const pcr_pool_dimer *)ctx->pcf_drec.p, nc, ctx->pcf_dmat.p + c0);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(ctx->stream));                                 // the next batch reuses the scratch
+		c0 = c1;
+	}
+	uint32_t bad = 0;
+	HIP_TRY(hipMemcpyAsync(&bad, ctx->pcf_flag.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if(bad & 1u){ g_err = "pcr_pool_conflicts: internal trace-back error"; return PCR_ERR_RANGE; }
+	return PCR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int64_t pcr_pool_conflicts(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor,
+	int dimer_rule, float dimer_floor, uint32_t *oligo_id, pcr_pool_conflict *out, uint64_t cap)
+{
+	static_assert(sizeof(pcr_pool_conflict) == 48, "record layout");
+	static_assert(sizeof(ConflictAgg) == 16 && sizeof(uint4) == 16, "the dense array is kept as uint4");
+	// ---- the arguments, before the handle (pcr_pool_products_tm's checks in its order, then the dimer arguments)
+	if(!set_ok(which)){ g_err = "pcr_pool_conflicts: unknown sequence set"; return PCR_ERR_ARG; }
+	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = "pcr_pool_conflicts: PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
+	if(!args || (n_pool && (!pool || !oligo_id)) || (cap && !out)){ g_err = "pcr_pool_conflicts: bad argument"; return PCR_ERR_ARG; }
+	if(n_pool > PCR_POOL_MAX_PAIRS){ g_err = "pcr_pool_conflicts: pool larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
+	if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f)){ g_err = "pcr_pool_conflicts: negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
+	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = "pcr_pool_conflicts: salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
+	// the distinct oligos, in order of first appearance (as pcr_pool_products_tm and pcr_pool_dimers)
+	std::vector<PoolOligo> ol;
+	std::vector<SiteOligoX> olx;
+	std::vector<DimerOligo> dol;
+	std::map<std::pair<uint64_t, uint64_t>, uint32_t> id_of;
+	const float thr2 = threshold*threshold;                                      // pcr_assay.cpp:775-776
+	for(uint32_t s = 0;s < 2*n_pool;++s){
+		const pcr_word128 &wd = (s & 1) ? pool[s/2].r : pool[s/2].f;
+		auto ins = id_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)ol.size()));
+		if(ins.second){
+			OligoDev d; fill_oligo(d, wd.w, thr2);
+			const uint32_t occ = pcrhost::planes_occupied(d.m);
+			if(!occ || __builtin_popcount(occ) != d.stop - d.start + 1){
+				g_err = "pcr_pool_conflicts: an oligo is empty or has a hole between its ends (NucCruc::set_query throws)"; return PCR_ERR_ARG;
+			}
+			const double degen = pcrhost::planes_degeneracy(d.m);
+			if(degen > (double)PCR_SITE_MAX_EXPANSIONS){ g_err = "pcr_pool_conflicts: an oligo has more than PCR_SITE_MAX_EXPANSIONS expansions"; return PCR_ERR_ARG; }
+			PoolOligo p; p.m = d.m; p.floor2 = d.floor2; p.start = d.start; p.stop = d.stop; p.pad = 0;
+			ol.push_back(p);
+			const float ca = (float)(args->primer_strand/degen), cb = template_strand;
+			const float strand = (ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca;          // nuc_cruc.h:832-837
+			if(!(strand > 0.0f)){ g_err = "pcr_pool_conflicts: the strand concentration of an oligo's duplex is zero (primer_strand / degeneracy and template_strand both 0)"; return PCR_ERR_ARG; }
+			SiteOligoX x; x.n_exp = (uint32_t)degen;
+			x.log_strand = logf(strand);
+			olx.push_back(x);
+			DimerOligo q;                                                          // pcr_pool_dimers' record of the same oligo
+			q.m = pcrhost::planes_of_word(wd.w);
+			q.start = pcrhost::planes_start(q.m); q.stop = pcrhost::planes_stop(q.m);
+			q.n_exp = (uint32_t)degen; q.cls = 0;
+			dol.push_back(q);
+		}
+		oligo_id[s] = ins.first->second;
+	}
+	if(!std::isfinite(tm_floor)){ g_err = "pcr_pool_conflicts: tm_floor is not finite"; return PCR_ERR_ARG; }
+	if(dimer_rule != PCR_DIMER_RULE_POOL && dimer_rule != PCR_DIMER_RULE_ASSAY && dimer_rule != PCR_CONFLICT_NO_DIMERS){
+		g_err = "pcr_pool_conflicts: unknown dimer_rule (PCR_DIMER_RULE_POOL, PCR_DIMER_RULE_ASSAY or PCR_CONFLICT_NO_DIMERS)"; return PCR_ERR_ARG;
+	}
+	if(!std::isfinite(dimer_floor)){ g_err = "pcr_pool_conflicts: dimer_floor is not finite"; return PCR_ERR_ARG; }
+	const bool dimers = dimer_rule != PCR_CONFLICT_NO_DIMERS;
+	// with a dimer rule, what pcr_pool_dimers asks of the arguments: its strand concentrations, per pair of degeneracy classes
+	std::vector<uint32_t> cls_degen, pref, row;
+	std::vector<float> logs;
+	if(dimers){
+		if(!(args->primer_strand > 0.0f)){ g_err = "pcr_pool_conflicts: with a dimer rule primer_strand must be positive (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
+		for(DimerOligo &q : dol){
+			const auto at = std::find(cls_degen.begin(), cls_degen.end(), q.n_exp);
+			q.cls = (uint32_t)(at - cls_degen.begin());
+			if(at == cls_degen.end()) cls_degen.push_back(q.n_exp);
+		}
+		const uint32_t n_cls = (uint32_t)cls_degen.size();
+		logs.resize((size_t)n_cls*n_cls + n_cls);
+		for(uint32_t a = 0;a < n_cls;++a){
+			const float ca = (float)(args->primer_strand/(double)cls_degen[a]);
+			for(uint32_t b = 0;b < n_cls;++b){
+				const float cb = (float)(args->primer_strand/(double)cls_degen[b]);
+				const float strand = (dimer_rule == PCR_DIMER_RULE_POOL) ? args->primer_strand                  // pcr_assay.cpp:819-821
+					: ((ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca);                                            // pcr_assay.cpp:244, nuc_cruc.h:832-837
+				if(!(strand > 0.0f)){ g_err = "pcr_pool_conflicts: primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
+				logs[(size_t)a*n_cls + b] = logf(strand);
+			}
+			const float own = (dimer_rule == PCR_DIMER_RULE_POOL) ? args->primer_strand : ca;                   // valid_pcr.cpp:13
+			if(!(own > 0.0f)){ g_err = "pcr_pool_conflicts: primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
+			logs[(size_t)n_cls*n_cls + a] = logf(own);
+		}
+	}
+	if(!ctx){ g_err = "pcr_pool_conflicts: null handle"; return PCR_ERR_ARG; }
+	{ const int drc = drain(ctx); if(drc != PCR_OK) return drc; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	SeqSet &S = ctx->sets[which];
+	if(!S.have_db){ g_err = "pcr_pool_conflicts: no word DB (call pcr_select_words or pcr_select_sites first)"; return PCR_ERR_STATE; }
+	if(n_pool == 0) return 0;
+	const uint32_t n_ol = (uint32_t)ol.size();
+	if(dimers){
+		// pcr_pool_dimers' duplex numbering: pref[t] = expansions of the oligos before t; row[q] = duplexes of the rows before q
+		pref.assign(n_ol + 1, 0); row.assign(n_ol + 1, 0);
+		for(uint32_t t = 0;t < n_ol;++t) pref[t + 1] = pref[t] + dol[t].n_exp;
+		uint64_t total = 0;
+		for(uint32_t q = 0;q < n_ol;++q){
+			row[q] = (uint32_t)total;
+			total += (uint64_t)dol[q].n_exp*(pref[n_ol] - dol[q].n_exp) + dol[q].n_exp;
+			if(total >= (uint64_t(1) << 31)){ g_err = "pcr_pool_conflicts: the pool's duplexes number 2^31 or more"; return PCR_ERR_CAPACITY; }
+		}
+		row[n_ol] = (uint32_t)total;
+	}
+	{ const int erc = ensure_touched(ctx, S); if(erc != PCR_OK) return erc; }
+	int rc;
+	const uint32_t n_cells = n_pool*(n_pool + 1u)/2u;
+	if((rc = ctx->pcf_flag.ensure(2)) != PCR_OK) return rc;                      // [0]: k_item_tm's, [1]: k_pool_dimer_reduce's
+	HIP_TRY(hipMemsetAsync(ctx->pcf_flag.p, 0, 2*sizeof(uint32_t), ctx->stream));
+	if((rc = ctx->pcf_dense.ensure(n_cells)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->pcf_dense.p, 0, (size_t)n_cells*sizeof(uint4), ctx->stream));
+	if((rc = conflict_products(ctx, S, ol, olx, oligo_id, n_pool, amp_min, amp_max, args, tm_floor, n_cells)) != PCR_OK) return rc;
+	if(dimers && (rc = conflict_dimers(ctx, args, dol, pref, row, logs, (uint32_t)cls_degen.size())) != PCR_OK) return rc;
+	// ---- 8. the records, the kept ones in (row_a, row_b) order
+	const size_t ol_bytes = ol.size()*sizeof(PoolOligo), olx_bytes = olx.size()*sizeof(SiteOligoX);
+	const uint2 *d_row_ol = (const uint2 *)(ctx->pcf_in.p + ol_bytes + olx_bytes);   // (conflict_products' upload)
+	if((rc = ctx->pcf_rec.ensure(n_cells)) != PCR_OK) return rc;
+	if((rc = ctx->pcf_keep.ensure((size_t)n_cells + 1)) != PCR_OK) return rc;
+	if((rc = ctx->pcf_koff.ensure((size_t)n_cells + 1)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->pcf_keep.p + n_cells, 0, sizeof(uint32_t), ctx->stream));
+	hipLaunchKernelGGL(k_conflict_cells, dim3((n_pool + POOL_THREADS - 1)/POOL_THREADS, n_pool), dim3(POOL_THREADS), 0, ctx->stream,
+		(const ConflictAgg *)ctx->pcf_dense.p, dimers ? (const float *)ctx->pcf_dmat.p : (const float *)nullptr, n_ol, d_row_ol, n_pool, dimer_floor,
+		ctx->pcf_rec.p, ctx->pcf_keep.p);
+	HIP_TRY(hipGetLastError());
+	size_t tmp = 0;
+	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pcf_keep.p, ctx->pcf_koff.p, uint32_t(0), (size_t)n_cells + 1, rocprim::plus<uint32_t>(), ctx->stream));
+	if((rc = ctx->pcf_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
+	HIP_TRY(rocprim::exclusive_scan(ctx->pcf_tmp.p, tmp, ctx->pcf_keep.p, ctx->pcf_koff.p, uint32_t(0), (size_t)n_cells + 1, rocprim::plus<uint32_t>(), ctx->stream));
+	uint32_t kept = 0;
+	HIP_TRY(hipMemcpyAsync(&kept, ctx->pcf_koff.p + n_cells, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if(kept == 0 || kept > cap) return (int64_t)kept;                            // count only: out is left as it is
+	if((rc = ctx->pcf_out.ensure(kept)) != PCR_OK) return rc;
+	hipLaunchKernelGGL(k_conflict_compact, dim3((n_cells + POOL_THREADS - 1)/POOL_THREADS), dim3(POOL_THREADS), 0, ctx->stream,
+		(const pcr_pool_conflict *)ctx->pcf_rec.p, (const uint32_t *)ctx->pcf_keep.p, (const uint32_t *)ctx->pcf_koff.p, n_cells, ctx->pcf_out.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out, ctx->pcf_out.p, (size_t)kept*sizeof(pcr_pool_conflict), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	return (int64_t)kept;
+}
+
+} // extern "C"
