@@ -607,6 +607,67 @@ int64_t pcr_site_variants(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, ui
 	pcr_site_variant *out, uint64_t cap,
 	uint32_t *site_variant, uint64_t site_cap, uint64_t counts[2]);
 
+/* ---- Degenerate bases that win back a panel's eroded binding sites */
+
+#define PCR_REPAIR_MAX_STEPS      12     /* a plain oligo gains at most 12 (slot, base) bits within 256 expansions: 4*4*4*4 */
+#define PCR_REPAIR_MAX_CANDIDATES 4096
+#define PCR_REPAIR_COMPLETE   1u         /* every sequence with a site of the oligo is held */
+#define PCR_REPAIR_NO_GAIN    2u         /* the best candidate wins no sequence, or nothing can be unioned for another reason */
+#define PCR_REPAIR_DEGENERACY 4u         /* unheld single-base variants exist, but every union exceeds max_degeneracy */
+#define PCR_REPAIR_STEPS      8u         /* max_steps steps were taken */
+#define PCR_REPAIR_NO_VARIANT 0xFFFFFFFFu
+
+typedef struct {               /* one step of one oligo's repair; step 0 is the oligo as it is (72 bytes) */
+	pcr_word128 word;          /* the oligo after this step: same slots start..stop, bases only added */
+	uint32_t oligo;            /* distinct-oligo id, pcr_pool_products' numbering */
+	uint32_t step;
+	uint32_t variant;          /* index, in pcr_site_variants' record order for the same arguments, of the variant unioned in; step 0: PCR_REPAIR_NO_VARIANT */
+	uint32_t added_mask;       /* bit i: the oligo's slot start+i gained a base in this step; step 0: 0 */
+	uint32_t n_expansions;     /* Word::degeneracy() of word */
+	uint32_t candidates;       /* candidates weighed for this step; step 0: 0 */
+	uint32_t sequences_held, sites_held, variants_held;   /* after this step */
+	uint32_t sequences_total;  /* distinct sequences with any site of the oligo at the floor */
+	uint32_t gain;             /* sequences_held minus the previous step's; step 0: 0 */
+	uint32_t flags;            /* on an oligo's LAST record, why it stopped: one PCR_REPAIR_* reason; 0 on the others */
+	uint32_t valid;            /* pcr_thermo's `valid` for word; 0 with args == NULL */
+	uint32_t reserved;         /* 0: the record's size is a multiple of 8 either way, this names the last four bytes */
+} pcr_repair_step;
+
+/* Which bases to make degenerate to get back the sequences an oligo no longer binds, and what each one buys: a greedy
+ * union of observed template spellings into the oligo, one per step, every step reported.
+ *   Sites and variants.  Exactly pcr_site_variants' for the same handle state, `which`, panel and threshold: the same
+ * picked entry, the same key (flanks included), the same record order -- which does not depend on thermodynamics, so
+ * `variant` indexes what pcr_site_variants(args = NULL) returns.  The footprint of a variant is its word at the oligo's
+ * slots start..stop; the flanking slots play no part here.
+ *   Held.  A word W (the oligo, or the oligo after a step) holds a variant v if at most max_mismatch of the slots k in
+ * start..stop have (v[k] & W[k]) == 0 and the clamp3 slots stop-clamp3+1..stop all intersect (clamp3 above the oligo's
+ * length: nothing is held).  An empty slot of v is a mismatch; an ambiguity code of the template matches where it
+ * intersects (Word::operator&).  For W = the oligo this is popcount(mismatch_mask) <= max_mismatch && v.clamp3 >= clamp3.
+ * A sequence is held if any of its sites of this oligo belongs to a held variant.  sequences_held counts distinct
+ * sequences, sites_held sums `sites` over the held variants, variants_held counts them.
+ *   One step.  Candidates: the first max_candidates variants of the oligo in record order that W does not hold, that
+ * carry exactly one base in every footprint slot, and whose union W | footprint(v) has at most max_degeneracy
+ * expansions.  Each is weighed by everything its union would hold, not by v alone: gain = sequences held by the union
+ * and not by W.  The step takes the highest gain; ties go to the higher sites_held, then the fewer expansions, then the
+ * lower variant index.
+ *   Stopping.  The oligo's last record carries the reason: every sequence held (COMPLETE); max_steps steps taken
+ * (STEPS); no candidate although an unheld single-base variant exists, i.e. every such union exceeds max_degeneracy
+ * (DEGENERACY); the best gain is 0 or there is no candidate for another reason (NO_GAIN).  Where several apply:
+ * COMPLETE, STEPS, DEGENERACY, NO_GAIN.  An oligo without sites gets its step 0 with zeros and COMPLETE; one that has
+ * more than max_degeneracy expansions to begin with stops at step 0 by the same rules.
+ *   Thermodynamics.  args != NULL: the words of all steps of all oligos go through pcr_thermo in one batch with
+ * check_homo_dimer; `valid` is its verdict.  It is reported, not used as a gate.  args == NULL: valid = 0.
+ *   Records are sorted by (oligo, step): max_steps + 1 at most per distinct oligo.  Returns their number or a negative
+ * error; if it exceeds cap the contents of out are unspecified (cap = 0: count only, nothing is melted).  n_pairs = 0
+ * returns 0.  oligo_id[2*n_pairs] as pcr_site_variants.  The same bytes come out on every run.
+ *   PCR_ERR_ARG (checked before the handle): pcr_site_variants' refusals in its order (template_strand taken as 0);
+ * max_degeneracy 0 or above PCR_SITE_MAX_EXPANSIONS; clamp3 > 32; max_candidates 0 or above
+ * PCR_REPAIR_MAX_CANDIDATES; max_steps above PCR_REPAIR_MAX_STEPS (0 is legal: step 0 only); then a null handle.  The
+ * other errors as pcr_site_variants.  Changes nothing other calls read and makes no collective on a sharded handle. */
+int64_t pcr_site_repair(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs, float threshold,
+	uint32_t max_degeneracy, uint32_t max_mismatch, uint32_t clamp3, uint32_t max_candidates, uint32_t max_steps,
+	const pcr_thermo_args *args, int check_homo_dimer, uint32_t *oligo_id, pcr_repair_step *out, uint64_t cap);
+
 /* ---- Every oligo-by-oligo dimer of a primer pool */
 
 /* One cell of the pool's dimer matrix: an ordered pair of distinct-oligo ids, reduced over its duplexes (40 bytes). */

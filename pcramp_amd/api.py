@@ -79,6 +79,15 @@ SITE_VARIANT_DTYPE = np.dtype([("word", np.uint64, (2,)), ("oligo", np.uint32), 
                                ("first_loc5", np.int32), ("first_strand", np.uint32), ("tm_max", np.float32),
                                ("tm_min", np.float32), ("dH", np.float32), ("dS", np.float32)])
 
+# pcr_repair_step: one step of one oligo's repair (Screener.site_repair); 72 bytes
+REPAIR_STEP_DTYPE = np.dtype({"names": ["word", "oligo", "step", "variant", "added_mask", "n_expansions", "candidates", "sequences_held",
+                                        "sites_held", "variants_held", "sequences_total", "gain", "flags", "valid", "reserved"],
+                              "formats": [(np.uint64, (2,))] + [np.uint32] * 14,
+                              "offsets": [0] + [16 + 4 * i for i in range(14)], "itemsize": 72})
+REPAIR_COMPLETE, REPAIR_NO_GAIN, REPAIR_DEGENERACY, REPAIR_STEPS = 1, 2, 4, 8   # PCR_REPAIR_*: why an oligo's last step is its last
+REPAIR_MAX_STEPS, REPAIR_MAX_CANDIDATES = 12, 4096   # PCR_REPAIR_MAX_*
+REPAIR_NO_VARIANT = 0xFFFFFFFF                # PCR_REPAIR_NO_VARIANT
+
 # pcr_pool_dimer: one ordered (query oligo, target oligo) cell of a pool's dimer matrix (Screener.pool_dimers)
 POOL_DIMER_DTYPE = np.dtype([("query_oligo", np.uint32), ("target_oligo", np.uint32), ("n_duplexes", np.uint32),
                              ("q_expansion", np.uint32), ("t_expansion", np.uint32), ("flags", np.uint32),
@@ -184,7 +193,7 @@ ABI_SYMBOLS = [
     "pcr_thermo", "pcr_valid_words", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers",
-    "pcr_pool_products_tm", "pcr_pool_anneal_profile", "pcr_pool_conflicts", "pcr_pool_probe_hits", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants",
+    "pcr_pool_products_tm", "pcr_pool_anneal_profile", "pcr_pool_conflicts", "pcr_pool_probe_hits", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants", "pcr_site_repair",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats", "pcr_live_resources",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -282,6 +291,9 @@ def load_library():
     L.pcr_site_variants.restype = C.c_int64
     L.pcr_site_variants.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.POINTER(ThermoArgs), C.c_float, C.c_void_p,
                                     C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.pcr_site_repair.restype = C.c_int64
+    L.pcr_site_repair.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                  C.c_uint32, C.POINTER(ThermoArgs), C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]
     L.pcr_pool_products_tm.restype = C.c_int64
     L.pcr_pool_products_tm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
                                        C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
@@ -360,6 +372,21 @@ def variant_texts(variants):
     """The oligo-oriented spelling of each site_variants record's word in IUPAC letters, lowest occupied slot to highest
     (flanks included; read it beside the oligo's own text shifted by one where the 5' flank slot is occupied)."""
     return [W.word_text((int(r["word"][0]), int(r["word"][1]))) for r in variants]
+
+
+def repaired_panel(panel, ids, steps, min_gain=1, require_valid=True):
+    """The panel with each oligo replaced by the word of its last site_repair step that gained at least min_gain sequences
+    and, with require_valid, is valid; an oligo without such a step stays as it is.  ids and steps are what site_repair
+    returned for this panel: an oligo that several pairs share is replaced in all of them.  -> list of (f, r) word tuples."""
+    new = {}
+    for r in steps:                                     # sorted by (oligo, step): a later acceptable step overwrites
+        if r["step"] > 0 and r["gain"] >= min_gain and (r["valid"] or not require_valid):
+            new[int(r["oligo"])] = (int(r["word"][0]), int(r["word"][1]))
+    out = []
+    for i, (f, r) in enumerate(panel):
+        f, r = (int(f[0]), int(f[1])), (int(r[0]), int(r[1]))
+        out.append((new.get(int(ids[2 * i]), f), new.get(int(ids[2 * i + 1]), r)))
+    return out
 
 
 def _slot_planes(slots):
@@ -1084,6 +1111,42 @@ class Screener:
                 return res + (smap[:int(counts[0])].copy(),) if site_map else res
             cap = max(cap, n)
             site_cap = int(counts[0]) if site_map else 0
+
+    def site_repair(self, panel, threshold=1.0, max_degeneracy=16, max_mismatch=0, clamp3=0, max_candidates=256, max_steps=12,
+                    which=TARGET, select=False, thermo=True, check_homo_dimer=True, salt=0.05, primer_strand=9e-7, tm_min=50.0,
+                    tm_max=75.0, max_hairpin=40.0, max_dimer=40.0, cap=1 << 12):
+        """Which bases to make degenerate to win back the sequences each oligo of the panel no longer binds
+        (pcr_site_repair) -> (oligo_id uint32[2 * len(panel)], steps: REPAIR_STEP_DTYPE array sorted by (oligo, step)).
+
+        The sites and variants are site_variants' for the same arguments.  A word holds a variant if at most max_mismatch
+        of the oligo's slots miss it and its last clamp3 slots all match; a sequence is held if one of its sites is.  Step
+        0 is the oligo as it is.  Every further step unions one observed single-base variant into the oligo -- of the first
+        max_candidates unheld ones whose union stays within max_degeneracy expansions, the one whose union holds the most
+        new sequences -- and says what the new word is, which slots gained a base (added_mask), what it now holds and
+        whether it is valid (thermo=True: is_valid's verdict with these thresholds; never a gate).  flags on an oligo's
+        last record: REPAIR_COMPLETE, REPAIR_STEPS, REPAIR_DEGENERACY or REPAIR_NO_GAIN.  `variant` indexes
+        site_variants(thermo=False)'s records.  Sequences without a site at the floor are invisible here: choose the
+        threshold low.  `select` as for site_variants.  repaired_panel() applies the steps to the panel."""
+        thr2 = float(np.float32(threshold) * np.float32(threshold))
+        if isinstance(select, str):
+            if select != "all":
+                raise ValueError("site_repair: select must be True, False or 'all'")
+            self.select_sites(panel, thr2, which=which)
+        elif select:
+            self.select_words(panel, thr2, which=which)
+        a = W.pairs_array(panel)
+        ids = np.zeros(max(2 * len(panel), 1), np.uint32)
+        args = C.byref(self._targs(salt, primer_strand, tm_min, tm_max, max_hairpin, max_dimer)) if thermo else None
+        while True:
+            out = np.zeros(max(cap, 1), REPAIR_STEP_DTYPE)
+            n = self.L.pcr_site_repair(self.h, which, a.ctypes.data, len(panel), float(threshold), int(max_degeneracy), int(max_mismatch),
+                                       int(clamp3), int(max_candidates), int(max_steps), args, int(check_homo_dimer), ids.ctypes.data,
+                                       out.ctypes.data, cap)
+            if n < 0:
+                raise PcrError(_err(self.L))
+            if n <= cap:
+                return ids[:2 * len(panel)].copy(), out[:n].copy()
+            cap = int(n)
 
     @staticmethod
     def product_tm(products, sites):

@@ -29,6 +29,7 @@
 //   thermo::k_thermo_wave  : NucCruc (pcr_thermo.inc)
 //   k_site_tm, k_site_reduce : the same engine over the binding sites of the word DB, jobs built on the device (pcr_site_tm.inc)
 //   k_sv_items, k_sv_heads, k_sv_tm : the sites grouped by (oligo, template planes in the window) with radix sorts over the whole key, one melt per group (pcr_site_variants.inc)
+//   k_rp_candidates, k_rp_weigh, k_rp_step : a greedy union of variants into each oligo, every (oligo, candidate) weighed by what its union holds (pcr_site_repair.inc)
 //   k_pool_dimer, k_pool_dimer_reduce : the same engine over every ordered oligo pair of a pool, jobs derived from the job number (pcr_pool_dimers.inc)
 //   k_item_tm, k_products_join : k_site_tm's Tm per item, and k_pool_join's geometry with the two sites' Tm, the floor and the pool's bit rows (pcr_products_tm.inc)
 //   k_anneal_join, k_anneal_rows : the same join without a floor: per (pool pair, sequence) the highest min-Tm by integer atomicMax, LDS histograms over an ascending temperature list (pcr_anneal_profile.inc)
@@ -762,6 +763,9 @@ struct pcr_ctx {
 	// records (key order | record order), the variants' sort keys and orders (+ their rank), the site map
 	DevBuf<uint8_t> sv_item; DevBuf<uint32_t> sv_ord, sv_var, sv_start, sv_vord, sv_map; DevBuf<pcr_site_variant> sv_rec; DevBuf<uint64_t> sv_vkeys;
 	bool sv_attr_set = false;
+	// pcr_site_repair (pcr_site_repair.inc; on top of the variant pipeline's site_* and sv_*): footprints, (oligo, sequence) pair keys + the
+	// held bitset, the uint32 tables (sites, ranges, pairs, runs, candidates), per-oligo state + candidate scores, the step records
+	DevBuf<uint4> rp_foot; DevBuf<uint64_t> rp_keys; DevBuf<uint32_t> rp_u32; DevBuf<uint8_t> rp_state; DevBuf<pcr_repair_step> rp_rec;
 	// an attached target shard (pcr_shard_targets, pcr_shard.inc): PCR_SET_TARGET holds rows [shard_first, shard_first + n) of
 	// shard_n_total, and the local search combines target coverage over shard_comm; NULL = not sharded
 	pcr_comm *shard_comm = nullptr; uint64_t shard_first = 0, shard_n_total = 0; int shard_mode = 0;
@@ -2188,6 +2192,7 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_pool.inc"
 #include "pcr_site_tm.inc"
 #include "pcr_site_variants.inc"
+#include "pcr_site_repair.inc"
 #include "pcr_pool_dimers.inc"
 #include "pcr_products_tm.inc"
 #include "pcr_anneal_profile.inc"

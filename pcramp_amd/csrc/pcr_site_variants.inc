@@ -17,6 +17,8 @@
 //      per (variant, expansion)), k_sv_reduce (k_site_reduce's rule).
 //   7. Two stable sorts of the variants into record order, k_sv_gather, and k_sv_map for the site map.
 // Steps 1, 3 and 6 use pcr_site_tm's scratch (pcr_ctx::site_*: nothing is kept in it between calls); the rest is pcr_ctx::sv_*.
+// sv_check (the refusals before the handle, the distinct oligos) and sv_run (steps 1 to 7) are shared with pcr_site_repair.inc,
+// which goes on from what sv_run leaves on the device (SvRun); pcr_site_variants adds the site map and the copy-out.
 
 namespace {
 
@@ -199,29 +201,40 @@ __global__ __launch_bounds__(POOL_THREADS) void k_sv_map(const uint32_t *__restr
 	if(r < n_items) map[r] = rank[item_var[site_ord[r]]];
 }
 
-} // namespace
+static_assert(sizeof(pcr_site_variant) == 80, "record layout");
+static_assert(sizeof(SvItem) == 32, "item layout");
+static_assert(POOL_MAX_OLIGOS <= (1u << 16), "k_sv_vkey2 keeps the oligo above 32 bits of a 48-bit key");
 
-extern "C" {
+// What one run of the pipeline leaves on the device for its caller (pcr_site_variants copies it out, pcr_site_repair.inc goes
+// on from it): valid until the next call that uses pcr_ctx::site_* or sv_*.
+struct SvRun {
+	bool done = false;                 // the records exist (false: the run ended early with a count, an empty answer or an error)
+	uint32_t n_ol = 0, ni = 0, nv = 0, n_vseq = 0;   // distinct oligos, sites, variants, distinct (variant, sequence) pairs
+	uint64_t n_jobs = 0;
+	const PoolOligo *d_ol = nullptr;
+	const SvItem *sv = nullptr;        // the items
+	const uint32_t *key_ord = nullptr, *site_ord = nullptr;   // position in key order -> item; pcr_site_tm's record order -> item
+	const uint64_t *sum = nullptr;     // k_sv_heads' flags scanned, by position in key order
+	const uint32_t *start = nullptr;   // variant (key order) -> its first position; start[nv] = ni
+	const uint32_t *item_var = nullptr, *rank = nullptr;      // item -> variant (key order); variant (key order) -> record
+	const pcr_site_variant *rec = nullptr;                    // the records in record order
+};
 
-int64_t pcr_site_variants(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs, float threshold,
-	const pcr_thermo_args *args, float template_strand, uint32_t *oligo_id, pcr_site_variant *out, uint64_t cap,
-	uint32_t *site_variant, uint64_t site_cap, uint64_t counts[2])
+// The arguments every caller of the pipeline refuses before the handle (pcr_site_tm's, in its order; args may be NULL), and the
+// distinct oligos, in order of first appearance (as pcr_pool_products).  bad_out: the caller's own "cap without a buffer".
+int sv_check(const char *who, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs, float threshold, const pcr_thermo_args *args,
+	float template_strand, uint32_t *oligo_id, bool bad_out, std::vector<PoolOligo> &ol, std::vector<SiteOligoX> &olx)
 {
-	static_assert(sizeof(pcr_site_variant) == 80, "record layout");
-	static_assert(sizeof(SvItem) == 32, "item layout");
-	static_assert(POOL_MAX_OLIGOS <= (1u << 16), "k_sv_vkey2 keeps the oligo above 32 bits of a 48-bit key");
-	// ---- the arguments, before the handle (pcr_site_tm's, in its order; args may be NULL)
-	if(!set_ok(which)){ g_err = "pcr_site_variants: unknown sequence set"; return PCR_ERR_ARG; }
-	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = "pcr_site_variants: PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
-	if((n_pairs && (!pairs || !oligo_id)) || (cap && !out)){ g_err = "pcr_site_variants: bad argument"; return PCR_ERR_ARG; }
-	if(n_pairs > PCR_POOL_MAX_PAIRS){ g_err = "pcr_site_variants: panel larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
+	const std::string w(who);
+	if(!set_ok(which)){ g_err = w + ": unknown sequence set"; return PCR_ERR_ARG; }
+	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = w + ": PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
+	if((n_pairs && (!pairs || !oligo_id)) || bad_out){ g_err = w + ": bad argument"; return PCR_ERR_ARG; }
+	if(n_pairs > PCR_POOL_MAX_PAIRS){ g_err = w + ": panel larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
 	if(args){
-		if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f)){ g_err = "pcr_site_variants: negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
-		if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = "pcr_site_variants: salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
+		if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f)){ g_err = w + ": negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
+		if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = w + ": salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
 	}
 	// the distinct oligos, in order of first appearance (as pcr_pool_products)
-	std::vector<PoolOligo> ol;
-	std::vector<SiteOligoX> olx;
 	std::map<std::pair<uint64_t, uint64_t>, uint32_t> id_of;
 	const float thr2 = threshold*threshold;                                      // pcr_assay.cpp:775-776
 	for(uint32_t s = 0;s < 2*n_pairs;++s){
@@ -231,29 +244,37 @@ int64_t pcr_site_variants(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, ui
 			OligoDev d; fill_oligo(d, wd.w, thr2);
 			const uint32_t occ = pcrhost::planes_occupied(d.m);
 			if(!occ || __builtin_popcount(occ) != d.stop - d.start + 1){
-				g_err = "pcr_site_variants: an oligo is empty or has a hole between its ends (NucCruc::set_query throws)"; return PCR_ERR_ARG;
+				g_err = w + ": an oligo is empty or has a hole between its ends (NucCruc::set_query throws)"; return PCR_ERR_ARG;
 			}
 			const double degen = pcrhost::planes_degeneracy(d.m);
-			if(degen > (double)PCR_SITE_MAX_EXPANSIONS){ g_err = "pcr_site_variants: an oligo has more than PCR_SITE_MAX_EXPANSIONS expansions"; return PCR_ERR_ARG; }
+			if(degen > (double)PCR_SITE_MAX_EXPANSIONS){ g_err = w + ": an oligo has more than PCR_SITE_MAX_EXPANSIONS expansions"; return PCR_ERR_ARG; }
 			PoolOligo p; p.m = d.m; p.floor2 = d.floor2; p.start = d.start; p.stop = d.stop; p.pad = 0;
 			ol.push_back(p);
 			SiteOligoX x; x.n_exp = (uint32_t)degen; x.log_strand = 0.0f;
 			if(args){
 				const float ca = (float)(args->primer_strand/degen), cb = template_strand;
 				const float strand = (ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca;      // nuc_cruc.h:832-837
-				if(!(strand > 0.0f)){ g_err = "pcr_site_variants: the strand concentration of an oligo's duplex is zero (primer_strand / degeneracy and template_strand both 0)"; return PCR_ERR_ARG; }
+				if(!(strand > 0.0f)){ g_err = w + ": the strand concentration of an oligo's duplex is zero (primer_strand / degeneracy and template_strand both 0)"; return PCR_ERR_ARG; }
 				x.log_strand = logf(strand);
 			}
 			olx.push_back(x);
 		}
 		oligo_id[s] = ins.first->second;
 	}
-	if(site_cap && !site_variant){ g_err = "pcr_site_variants: site_cap without a site_variant buffer"; return PCR_ERR_ARG; }
-	if(!ctx){ g_err = "pcr_site_variants: null handle"; return PCR_ERR_ARG; }
+	return PCR_OK;
+}
+
+// Steps 1 to 7 on a checked panel -> the number of variants or a negative error; `run` says what is where.  A count above cap
+// ends the run before the records (no thermodynamics, run.done stays false) unless always is set.
+int64_t sv_run(const char *who, pcr_ctx *ctx, pcr_set which, uint32_t n_pairs, const pcr_thermo_args *args, const std::vector<PoolOligo> &ol,
+	const std::vector<SiteOligoX> &olx, uint64_t cap, bool always, uint64_t counts[2], SvRun &run)
+{
+	const std::string w(who);
+	if(!ctx){ g_err = w + ": null handle"; return PCR_ERR_ARG; }
 	{ const int drc = drain(ctx); if(drc != PCR_OK) return drc; }
 	HIP_TRY(hipSetDevice(ctx->device));
 	SeqSet &S = ctx->sets[which];
-	if(!S.have_db){ g_err = "pcr_site_variants: no word DB (call pcr_select_words or pcr_select_sites first)"; return PCR_ERR_STATE; }
+	if(!S.have_db){ g_err = w + ": no word DB (call pcr_select_words or pcr_select_sites first)"; return PCR_ERR_STATE; }
 	if(counts) counts[0] = counts[1] = 0;
 	if(n_pairs == 0) return 0;
 	{ const int erc = ensure_touched(ctx, S); if(erc != PCR_OK) return erc; }
@@ -282,7 +303,7 @@ int64_t pcr_site_variants(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, ui
 	uint64_t n_items = 0;
 	HIP_TRY(hipMemcpyAsync(&n_items, ctx->site_eoff.p + n_db, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
-	if(n_items >= POOL_MAX_ITEMS){ g_err = "pcr_site_variants: too many sites"; return PCR_ERR_CAPACITY; }
+	if(n_items >= POOL_MAX_ITEMS){ g_err = w + ": too many sites"; return PCR_ERR_CAPACITY; }
 	if(counts) counts[0] = n_items;
 	if(n_items == 0) return 0;
 	if((rc = ctx->site_items.ensure(n_items)) != PCR_OK) return rc;
@@ -336,7 +357,8 @@ int64_t pcr_site_variants(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, ui
 	HIP_TRY(hipMemcpyAsync(&last, k1 + (ni - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
 	const uint32_t nv = (uint32_t)last;                                          // 1 .. ni
-	if(nv > cap) return (int64_t)nv;                                             // count only: out and site_variant are left as they are
+	run.n_ol = n_ol; run.ni = ni; run.nv = nv; run.n_vseq = (uint32_t)(last >> 32);
+	if(!always && nv > cap) return (int64_t)nv;                                  // count only: the caller leaves out and site_variant as they are
 	if((rc = ctx->sv_start.ensure((size_t)nv + 1)) != PCR_OK) return rc;
 	if((rc = ctx->sv_var.ensure(ni)) != PCR_OK) return rc;
 	hipLaunchKernelGGL(k_sv_groups, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint32_t *)g0, (const uint64_t *)k1, ni, nv,
@@ -367,7 +389,7 @@ int64_t pcr_site_variants(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, ui
 		uint64_t n_jobs64 = 0;
 		HIP_TRY(hipMemcpyAsync(&n_jobs64, ctx->site_joff.p + nv, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(hipStreamSynchronize(ctx->stream));
-		if(n_jobs64 >= POOL_MAX_ITEMS){ g_err = "pcr_site_variants: too many (variant, expansion) jobs"; return PCR_ERR_CAPACITY; }
+		if(n_jobs64 >= POOL_MAX_ITEMS){ g_err = w + ": too many (variant, expansion) jobs"; return PCR_ERR_CAPACITY; }
 		const uint32_t n_jobs = (uint32_t)n_jobs64;
 		if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
 		if(!ctx->sv_attr_set){
@@ -396,6 +418,32 @@ int64_t pcr_site_variants(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, ui
 	HIP_TRY(rocprim::radix_sort_pairs(ctx->site_tmp.p, t2, vk0, vk1, vo1, vo0, nv, 0, 48, ctx->stream));
 	hipLaunchKernelGGL(k_sv_gather, dim3(grid_v), dim3(POOL_THREADS), 0, ctx->stream, (const pcr_site_variant *)r0, (const uint32_t *)vo0, nv, r1, rank);
 	HIP_TRY(hipGetLastError());
+	run.d_ol = d_ol; run.sv = sv; run.key_ord = g0; run.site_ord = o0; run.sum = k1; run.start = ctx->sv_start.p; run.item_var = ctx->sv_var.p;
+	run.rank = rank; run.rec = r1; run.done = true;
+	return (int64_t)nv;
+}
+
+} // namespace
+
+extern "C" {
+
+int64_t pcr_site_variants(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs, float threshold,
+	const pcr_thermo_args *args, float template_strand, uint32_t *oligo_id, pcr_site_variant *out, uint64_t cap,
+	uint32_t *site_variant, uint64_t site_cap, uint64_t counts[2])
+{
+	std::vector<PoolOligo> ol;
+	std::vector<SiteOligoX> olx;
+	int rc = sv_check("pcr_site_variants", which, pairs, n_pairs, threshold, args, template_strand, oligo_id, cap && !out, ol, olx);
+	if(rc != PCR_OK) return rc;
+	if(site_cap && !site_variant){ g_err = "pcr_site_variants: site_cap without a site_variant buffer"; return PCR_ERR_ARG; }
+	SvRun run;
+	const int64_t n = sv_run("pcr_site_variants", ctx, which, n_pairs, args, ol, olx, cap, false, counts, run);
+	if(!run.done) return n;
+	const uint32_t ni = run.ni, nv = run.nv;
+	const uint64_t n_items = ni;
+	const unsigned grid_i = (ni + POOL_THREADS - 1)/POOL_THREADS;
+	const uint32_t *o0 = run.site_ord, *rank = run.rank;
+	const pcr_site_variant *r1 = run.rec;
 	const bool want_map = site_variant && n_items <= site_cap;
 	if(want_map){
 		if((rc = ctx->sv_map.ensure(ni)) != PCR_OK) return rc;
