@@ -1,12 +1,12 @@
 // What a primer pool amplifies at every temperature of an annealing gradient, from one melt and one join
-// (pcr_pool_anneal_profile; included by pcr_device.hip after pcr_products_tm.inc, whose steps 1-3 it launches as they are).
+// (pcr_pool_anneal_profile; included by pcr_device.hip after pcr_pool.inc and pcr_site_tm.inc, whose stages are its steps 1-3).
 //
 // The Tm of a site does not depend on the floor pcr_pool_products_tm applies, only the comparison does.  A product with
 // v = min(tm_plus, tm_minus) is kept at temps[t] iff !(temps[t] > 0) || v >= temps[t]; temps is strictly ascending, so the kept
 // temperatures are a prefix 0 .. u - 1 and u is all a product contributes to the counts.  Per (pool pair, sequence) the highest
 // v of the cell's products decides the bit of pcr_pool_products_tm at every floor.
-//   1-3. the items, the jobs, k_site_tm, k_item_tm -> item_tm[] (pcr_products_tm.inc's steps, on this call's own scratch).
-//   4. k_anneal_join: k_products_join's geometry and tests, no floor.  Per product: u by a binary search in an LDS copy of temps,
+//   1-3. the items, the jobs, k_site_tm, k_item_tm -> item_tm[] (item_count / item_fill, melt_items, on the shared scratch set).
+//   4. k_anneal_join: k_products_join's walk (join_walk), no floor.  Per product: u by a binary search in an LDS copy of temps,
 //      hist[intended][u] += 1 in LDS (flushed once per block with 64-bit atomic adds), and the cell's melt value raised with an
 //      integer atomicMax on the float's bits: v >= +0 (the engine clamps a Tm at 0; v + 0.0f turns a -0 into +0), non-negative
 //      floats order like their bit patterns read as int32, and the sentinel -1.0f is a negative int32.  A maximum does not depend
@@ -18,7 +18,7 @@
 //      max(fr, rf) per sequence into an LDS histogram, and writes the suffix sums: pair_sequences[i][t], cells[t] (atomics),
 //      spurious_sequences[t].
 //   6. The host turns hist into the points' product counts (products at t = sum of hist[.][u] over u > t).
-// The number of launches and copies does not depend on n_temps.  The call owns its scratch (pcr_ctx::anp_*).
+// The number of launches and copies does not depend on n_temps.  Steps 1-3 work in pcr_ctx::shared, the rest in pcr_ctx::anp_*.
 
 namespace {
 
@@ -39,72 +39,44 @@ __device__ __forceinline__ uint32_t anneal_prefix(const float *ts, uint32_t n, f
 	return lo;
 }
 
-// k_products_join<false> without a floor: one thread per item k, a plus-strand item (i, x) against the minus-strand items (j, y)
-// of its segment.  Every product: hist[intended][u], and its cell of `melt` (intended: the row of its key) or of the last row
-// (spurious) raised to v.
-__global__ __launch_bounds__(POOL_THREADS) void k_anneal_join(const DevEntry *__restrict__ db, uint32_t cap, const uint32_t *__restrict__ touched,
-	const uint32_t *__restrict__ seg_hi, const uint2 *__restrict__ items, uint32_t n_items, const uint64_t *__restrict__ item_off,
-	const PoolOligo *__restrict__ oligos, uint32_t n_ol, const uint4 *__restrict__ planes, const uint64_t *__restrict__ blk_off,
-	const uint64_t *__restrict__ len, const uint8_t *__restrict__ has_eos, int32_t amp_min, int32_t amp_max,
-	const ItemTm *__restrict__ item_tm, const uint32_t *__restrict__ intended, const uint32_t *__restrict__ key_tab, uint32_t n_tab,
-	const float *__restrict__ temps, uint32_t n_temps, int *__restrict__ melt, uint32_t n_seq, unsigned long long *__restrict__ out)
+// k_products_join<false> without a floor: one thread per item k, join_walk.  Every product: hist[intended][u], and its cell of
+// `melt` (intended: the row of its key) or of the last row (spurious) raised to v.
+__global__ __launch_bounds__(POOL_THREADS) void k_anneal_join(const JoinIn J, const ItemTm *__restrict__ item_tm, const uint32_t *__restrict__ intended,
+	const uint32_t *__restrict__ key_tab, uint32_t n_tab, const float *__restrict__ temps, uint32_t n_temps, int *__restrict__ melt, uint32_t n_seq,
+	unsigned long long *__restrict__ out)
 {
-	__shared__ int2 ss[POOL_MAX_OLIGOS];                                        // Word::start() / stop()
+	__shared__ int2 ss[POOL_MAX_OLIGOS];
 	__shared__ float ts[PCR_ANNEAL_MAX_TEMPS];
 	__shared__ uint32_t hist[2*ANP_BINS];
-	for(uint32_t o = threadIdx.x;o < n_ol;o += blockDim.x) ss[o] = make_int2(oligos[o].start, oligos[o].stop);
 	for(uint32_t t = threadIdx.x;t < n_temps;t += blockDim.x) ts[t] = temps[t];
 	for(uint32_t b = threadIdx.x;b < 2*ANP_BINS;b += blockDim.x) hist[b] = 0;
-	__syncthreads();
+	join_geometry(J, ss);
 	const uint32_t k = blockIdx.x*blockDim.x + threadIdx.x;
-	if(k < n_items){
-		const uint2 it = items[k];
+	if(k < J.n_items){                                                           // (no early return: the flush below is the whole block's)
+		const uint2 it = J.items[k];
 		const uint32_t g = it.x, x = it.y;
-		const uint32_t i = touched[g/cap]*cap + g % cap;
-		const DevEntry ei = db[i];
+		const uint32_t i = J.touched[g/J.cap]*J.cap + g % J.cap;
+		const DevEntry ei = J.db[i];
 		if(ei.strand == 1){
-			const uint32_t hi = seg_hi[ei.seq];
-			const int32_t L = (int32_t)len[ei.seq];
-			const uint64_t blk_base = blk_off[ei.seq];
-			const bool eos = has_eos[ei.seq] != 0;
-			const int2 P = ss[x];
-			const int32_t p5 = ei.loc + P.x, p3 = ei.loc + P.y;                      // template_loc5/3, sequence.h:57-75
 			const ItemTm tp = item_tm[k];
-			for(uint32_t j = i + 1;j < hi;++j){
-				const DevEntry ej = db[j];
-				if(ej.loc - ei.loc > amp_max + 128) break;
-				if(ej.strand != 2) continue;
-				const uint32_t gj = g + (j - i);                                     // same segment: consecutive DB threads
-				const uint64_t t_end = item_off[gj + 1];
-				for(uint64_t t = item_off[gj];t < t_end;++t){
-					const uint32_t y = items[t].y;
-					const int2 M = ss[y];
-					const int32_t m5 = ej.loc - M.y, m3 = ej.loc - M.x;
-					if(p3 >= m5) continue;                                           // pcr_assay.cpp:468-471
-					const int32_t amp_len = m3 - p5 + 1;
-					if(amp_len < amp_min || amp_len > amp_max) continue;             // :477-484
-					const int32_t in_start = p3 + 1 - 4;                             // :489-490
-					const int32_t in_len = m5 - in_start + 8;                        // :492-494
-					if(in_start < 0 || in_len < 0 || in_start + in_len > L) continue;
-					if(eos && has_split(planes, blk_base, in_start, in_len)) continue;   // :504-521
-					const ItemTm tm = item_tm[t];
-					const float v = ((tp.tm < tm.tm) ? tp.tm : tm.tm) + 0.0f;        // k_products_join's min; + 0.0f: -0 -> +0 (contraction is off)
-					const uint32_t u = anneal_prefix(ts, n_temps, v);
-					const uint32_t b = x*n_ol + y;
-					size_t row = n_tab;                                              // the spurious row
-					const bool is_intended = (intended[b >> 5] >> (b & 31)) & 1u;
-					if(is_intended){
-						uint32_t lo = 0, above = n_tab;                              // key_tab[lo] <= b < key_tab[above]; an intended b is in the table
-						while(above - lo > 1u){
-							const uint32_t mid = lo + (above - lo)/2u;
-							if(key_tab[mid] <= b) lo = mid; else above = mid;
-						}
-						row = lo;
+			join_walk<false>(J, ss, g, x, i, ei, 0u, [&](uint64_t t, uint32_t y, uint32_t, int32_t, int32_t, int32_t, int32_t){
+				const ItemTm tm = item_tm[t];
+				const float v = ((tp.tm < tm.tm) ? tp.tm : tm.tm) + 0.0f;            // k_products_join's min; + 0.0f: -0 -> +0 (contraction is off)
+				const uint32_t u = anneal_prefix(ts, n_temps, v);
+				const uint32_t b = x*J.n_ol + y;
+				size_t row = n_tab;                                                  // the spurious row
+				const bool is_intended = (intended[b >> 5] >> (b & 31)) & 1u;
+				if(is_intended){
+					uint32_t lo = 0, above = n_tab;                                  // key_tab[lo] <= b < key_tab[above]; an intended b is in the table
+					while(above - lo > 1u){
+						const uint32_t mid = lo + (above - lo)/2u;
+						if(key_tab[mid] <= b) lo = mid; else above = mid;
 					}
-					atomicAdd(&hist[(is_intended ? ANP_BINS : 0u) + u], 1u);
-					atomicMax(melt + row*n_seq + ei.seq, __float_as_int(v));
+					row = lo;
 				}
-			}
+				atomicAdd(&hist[(is_intended ? ANP_BINS : 0u) + u], 1u);
+				atomicMax(melt + row*n_seq + ei.seq, __float_as_int(v));
+			});
 		}
 	}
 	__syncthreads();
@@ -158,40 +130,16 @@ int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *poo
 {
 	static_assert(sizeof(pcr_anneal_point) == 40, "record layout");
 	static_assert(sizeof(PoolOligo) == 32 && sizeof(SiteOligoX) == 8, "table layout");
-	// ---- the arguments, before the handle (pcr_pool_products_tm's checks in its order, then the temperatures)
+	// ---- the arguments, before the handle (pcr_pool_products_tm's checks in its order, the oligo table, then the temperatures)
 	if(!set_ok(which)){ g_err = "pcr_pool_anneal_profile: unknown sequence set"; return PCR_ERR_ARG; }
 	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = "pcr_pool_anneal_profile: PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
 	if(!args || !temps || !points || (n_pool && (!pool || !oligo_id))){ g_err = "pcr_pool_anneal_profile: bad argument"; return PCR_ERR_ARG; }
 	if(n_pool > PCR_POOL_MAX_PAIRS){ g_err = "pcr_pool_anneal_profile: pool larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
 	if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f)){ g_err = "pcr_pool_anneal_profile: negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
 	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = "pcr_pool_anneal_profile: salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
-	// the distinct oligos, in order of first appearance (as pcr_pool_products_tm)
 	std::vector<PoolOligo> ol;
 	std::vector<SiteOligoX> olx;
-	std::map<std::pair<uint64_t, uint64_t>, uint32_t> id_of;
-	const float thr2 = threshold*threshold;                                      // pcr_assay.cpp:775-776
-	for(uint32_t s = 0;s < 2*n_pool;++s){
-		const pcr_word128 &wd = (s & 1) ? pool[s/2].r : pool[s/2].f;
-		auto ins = id_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)ol.size()));
-		if(ins.second){
-			OligoDev d; fill_oligo(d, wd.w, thr2);
-			const uint32_t occ = pcrhost::planes_occupied(d.m);
-			if(!occ || __builtin_popcount(occ) != d.stop - d.start + 1){
-				g_err = "pcr_pool_anneal_profile: an oligo is empty or has a hole between its ends (NucCruc::set_query throws)"; return PCR_ERR_ARG;
-			}
-			const double degen = pcrhost::planes_degeneracy(d.m);
-			if(degen > (double)PCR_SITE_MAX_EXPANSIONS){ g_err = "pcr_pool_anneal_profile: an oligo has more than PCR_SITE_MAX_EXPANSIONS expansions"; return PCR_ERR_ARG; }
-			PoolOligo p; p.m = d.m; p.floor2 = d.floor2; p.start = d.start; p.stop = d.stop; p.pad = 0;
-			ol.push_back(p);
-			const float ca = (float)(args->primer_strand/degen), cb = template_strand;
-			const float strand = (ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca;          // nuc_cruc.h:832-837
-			if(!(strand > 0.0f)){ g_err = "pcr_pool_anneal_profile: the strand concentration of an oligo's duplex is zero (primer_strand / degeneracy and template_strand both 0)"; return PCR_ERR_ARG; }
-			SiteOligoX x; x.n_exp = (uint32_t)degen;
-			x.log_strand = logf(strand);
-			olx.push_back(x);
-		}
-		oligo_id[s] = ins.first->second;
-	}
+	if(site_oligo_table("pcr_pool_anneal_profile", "an oligo", "primer_strand", pool, n_pool, threshold, args, template_strand, oligo_id, ol, olx) != PCR_OK) return PCR_ERR_ARG;
 	if(n_temps == 0 || n_temps > PCR_ANNEAL_MAX_TEMPS){ g_err = "pcr_pool_anneal_profile: n_temps is 0 or larger than PCR_ANNEAL_MAX_TEMPS"; return PCR_ERR_ARG; }
 	for(uint32_t t = 0;t < n_temps;++t){
 		if(!std::isfinite(temps[t])){ g_err = "pcr_pool_anneal_profile: a temperature is not finite"; return PCR_ERR_ARG; }
@@ -254,80 +202,36 @@ int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *poo
 	memcpy(blob.data() + ol_bytes + olx_bytes + map_bytes, key_tab.data(), tab_bytes);
 	memcpy(blob.data() + ol_bytes + olx_bytes + map_bytes + tab_bytes, intended.data(), int_bytes);
 	memcpy(blob.data() + ol_bytes + olx_bytes + map_bytes + tab_bytes + int_bytes, temps, temp_bytes);
-	if((rc = ctx->anp_in.ensure(blob.size())) != PCR_OK) return rc;
-	const PoolOligo *d_ol = (const PoolOligo *)ctx->anp_in.p;
-	const SiteOligoX *d_olx = (const SiteOligoX *)(ctx->anp_in.p + ol_bytes);
-	const uint2 *d_map = (const uint2 *)(ctx->anp_in.p + ol_bytes + olx_bytes);
-	const uint32_t *d_tab = (const uint32_t *)(ctx->anp_in.p + ol_bytes + olx_bytes + map_bytes);
-	const uint32_t *d_intended = (const uint32_t *)(ctx->anp_in.p + ol_bytes + olx_bytes + map_bytes + tab_bytes);
-	const float *d_temps = (const float *)(ctx->anp_in.p + ol_bytes + olx_bytes + map_bytes + tab_bytes + int_bytes);
-	HIP_TRY(hipMemcpyAsync(ctx->anp_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
-	// ---- 1. the items (k_pool_entry_oligos: count, scan, fill)
-	const uint32_t n_db = S.n_touched*S.db_cap;
-	if((rc = ctx->anp_cnt.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
-	if((rc = ctx->anp_eoff.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->anp_cnt.p + n_db, 0, sizeof(uint32_t), ctx->stream));
-	size_t tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->anp_cnt.p, ctx->anp_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	if((rc = ctx->anp_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-	const unsigned grid_e = std::min<unsigned>((n_db + POOL_THREADS - 1)/POOL_THREADS, ctx->n_cu*8);
-	hipLaunchKernelGGL(k_pool_entry_oligos<false>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
-		S.d_seg_hi, S.d_active.p, d_ol, n_ol, ctx->anp_cnt.p, (const uint64_t *)nullptr, (uint2 *)nullptr);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(rocprim::exclusive_scan(ctx->anp_tmp.p, tmp, ctx->anp_cnt.p, ctx->anp_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	ItemScratch &X = ctx->shared;
+	const ItemBufs B = X.bufs();
+	if((rc = X.in.ensure(blob.size())) != PCR_OK) return rc;
+	const PoolOligo *d_ol = (const PoolOligo *)X.in.p;
+	const SiteOligoX *d_olx = (const SiteOligoX *)(X.in.p + ol_bytes);
+	const uint2 *d_map = (const uint2 *)(X.in.p + ol_bytes + olx_bytes);
+	const uint32_t *d_tab = (const uint32_t *)(X.in.p + ol_bytes + olx_bytes + map_bytes);
+	const uint32_t *d_intended = (const uint32_t *)(X.in.p + ol_bytes + olx_bytes + map_bytes + tab_bytes);
+	const float *d_temps = (const float *)(X.in.p + ol_bytes + olx_bytes + map_bytes + tab_bytes + int_bytes);
+	HIP_TRY(hipMemcpyAsync(X.in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+	// ---- 1. the items (item_count waits: blob is read by then)
 	uint64_t n_items = 0;
-	HIP_TRY(hipMemcpyAsync(&n_items, ctx->anp_eoff.p + n_db, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));                                   // (blob is read by now)
+	if((rc = item_count(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
 	if(n_items >= POOL_MAX_ITEMS){ g_err = "pcr_pool_anneal_profile: too many (entry, oligo) hits"; return PCR_ERR_CAPACITY; }
 	if(n_items == 0){ write_empty(); return 0; }
-	if((rc = ctx->anp_items.ensure(n_items)) != PCR_OK) return rc;
-	hipLaunchKernelGGL(k_pool_entry_oligos<true>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
-		S.d_seg_hi, S.d_active.p, d_ol, n_ol, (uint32_t *)nullptr, (const uint64_t *)ctx->anp_eoff.p, ctx->anp_items.p);
-	HIP_TRY(hipGetLastError());
+	if((rc = item_fill(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
 	const uint32_t ni = (uint32_t)n_items;
 	const unsigned grid_i = (ni + POOL_THREADS - 1)/POOL_THREADS;
-	if((rc = ctx->anp_cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;         // (the entry counts are spent)
-	if((rc = ctx->anp_flag.ensure(1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->anp_flag.p, 0, sizeof(uint32_t), ctx->stream));
-	// ---- 2. job offsets, the jobs (k_site_jobs, k_site_tm as they stand)
-	if((rc = ctx->anp_joff.ensure((size_t)ni + 1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->anp_cnt.p + ni, 0, sizeof(uint32_t), ctx->stream));
-	hipLaunchKernelGGL(k_site_jobs, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint2 *)ctx->anp_items.p, ni, d_olx, ctx->anp_cnt.p);
-	HIP_TRY(hipGetLastError());
-	tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->anp_cnt.p, ctx->anp_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	if((rc = ctx->anp_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-	HIP_TRY(rocprim::exclusive_scan(ctx->anp_tmp.p, tmp, ctx->anp_cnt.p, ctx->anp_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	uint64_t n_jobs64 = 0;
-	HIP_TRY(hipMemcpyAsync(&n_jobs64, ctx->anp_joff.p + ni, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));
-	if(n_jobs64 >= POOL_MAX_ITEMS){ g_err = "pcr_pool_anneal_profile: too many (site, expansion) jobs"; return PCR_ERR_CAPACITY; }
-	const uint32_t n_jobs = (uint32_t)n_jobs64;
-	if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
-	if(!ctx->site_attr_set){                                                   // (k_site_tm's own flag: the attribute is the kernel's)
-		HIP_TRY(hipFuncSetAttribute((const void *)k_site_tm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SITE_LDS));
-		ctx->site_attr_set = true;
-	}
-	if((rc = ctx->anp_res.ensure(n_jobs)) != PCR_OK) return rc;
-	if((rc = ctx->anp_item_tm.ensure(ni)) != PCR_OK) return rc;
-	// at most one block per CU (a block takes most of a CU's LDS), the waves striding over the jobs
-	const unsigned grid_j = std::max(1u, std::min<unsigned>((n_jobs + SITE_WAVES - 1)/SITE_WAVES, (unsigned)ctx->n_cu));
-	hipLaunchKernelGGL(k_site_tm, dim3(grid_j), dim3(SITE_THREADS), SITE_LDS, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
-		(const uint2 *)ctx->anp_items.p, ni, (const uint64_t *)ctx->anp_joff.p, n_jobs, d_ol, d_olx, (const int *)ctx->th_dg.p, logf(args->salt), ctx->anp_res.p);
-	HIP_TRY(hipGetLastError());
-	// ---- 3. Tm per item
-	hipLaunchKernelGGL(k_item_tm, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint64_t *)ctx->anp_joff.p, ni,
-		(const float4 *)ctx->anp_res.p, (ItemTm *)ctx->anp_item_tm.p, ctx->anp_flag.p);
-	HIP_TRY(hipGetLastError());
+	if((rc = X.cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;                // (the entry counts are spent)
+	// ---- 2. job offsets, the jobs; 3. Tm per item
+	if((rc = melt_items("pcr_pool_anneal_profile", ctx, S, d_ol, d_olx, ni, args->salt, B)) != PCR_OK) return rc;
 	// ---- 4. the join: histograms and melt rows
 	if((rc = ctx->anp_out.ensure(ANP_OUT_WORDS)) != PCR_OK) return rc;
 	if((rc = ctx->anp_pairseq.ensure((size_t)n_pool*n_temps)) != PCR_OK) return rc;
 	HIP_TRY(hipMemsetAsync(ctx->anp_out.p, 0, ANP_OUT_WORDS*sizeof(uint64_t), ctx->stream));
 	HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ctx->anp_melt.p, (int)0xBF800000u, melt_elems, ctx->stream));   // -1.0f
-	hipLaunchKernelGGL(k_anneal_join, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
-		ctx->anp_items.p, ni, (const uint64_t *)ctx->anp_eoff.p, d_ol, n_ol, S.planes.p, S.d_blk_off.p, S.d_len.p, S.d_has_eos.p,
-		amp_min, amp_max, (const ItemTm *)ctx->anp_item_tm.p, d_intended, d_tab, n_tab, d_temps, n_temps, (int *)ctx->anp_melt.p,
-		(uint32_t)n_seq, (unsigned long long *)ctx->anp_out.p);
+	const JoinIn J{S.db.p, S.db_cap, S.touched.p, S.d_seg_hi, X.items.p, ni, X.eoff.p, d_ol, n_ol, S.planes.p, S.d_blk_off.p, S.d_len.p,
+		S.d_has_eos.p, amp_min, amp_max};
+	hipLaunchKernelGGL(k_anneal_join, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, (const ItemTm *)X.item_tm.p, d_intended, d_tab, n_tab,
+		d_temps, n_temps, (int *)ctx->anp_melt.p, (uint32_t)n_seq, (unsigned long long *)ctx->anp_out.p);
 	HIP_TRY(hipGetLastError());
 	// ---- 5. the rows' histograms
 	hipLaunchKernelGGL(k_anneal_rows, dim3(n_pool + 1), dim3(ANP_ROW_THREADS), 0, ctx->stream, (const int *)ctx->anp_melt.p, (uint32_t)n_seq,
@@ -338,7 +242,7 @@ int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *poo
 	const bool want_rows = melt_fr || melt_rf;
 	std::vector<float> host_melt;                                               // the keyed rows (+ the spurious row), when a matrix is asked for
 	HIP_TRY(hipMemcpyAsync(small, ctx->anp_out.p, sizeof small, hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipMemcpyAsync(&bad, ctx->anp_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipMemcpyAsync(&bad, X.flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
 	if(pair_sequences) HIP_TRY(hipMemcpyAsync(pair_sequences, ctx->anp_pairseq.p, (size_t)n_pool*n_temps*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
 	if(want_rows){
 		host_melt.resize(melt_elems);

@@ -696,6 +696,20 @@ struct HostPool {
 
 namespace { struct PassJob; struct Launcher; }   // pcr_select.inc
 
+// Which of a handle's buffers a call's item stage (pcr_pool.inc) and melt stage (pcr_site_tm.inc) work in: the stages know no
+// member names.  joff and res are the melt stage's; item_tm and flag go with its k_item_tm (NULL: the caller reduces the jobs itself).
+struct ItemBufs {
+	DevBuf<uint8_t> *tmp; DevBuf<uint32_t> *cnt; DevBuf<uint64_t> *eoff; DevBuf<uint2> *items;
+	DevBuf<uint64_t> *joff; DevBuf<float4> *res; DevBuf<uint2> *item_tm; DevBuf<uint32_t> *flag;
+};
+// The scratch that the entry points which melt a pool's items and join them have in common: the uploaded tables, scan / sort
+// scratch, per-entry / per-item counts, error flags, entry and job offsets, items, per-job results, per-item Tm, and the offsets of
+// the items' products where the join counts products (ioff).  Nothing in it outlives the call that wrote it.
+struct ItemScratch {
+	DevBuf<uint8_t> in, tmp; DevBuf<uint32_t> cnt, flag; DevBuf<uint64_t> eoff, joff, ioff; DevBuf<uint2> items, item_tm; DevBuf<float4> res;
+	ItemBufs bufs() { return ItemBufs{&tmp, &cnt, &eoff, &items, &joff, &res, &item_tm, &flag}; }
+};
+
 struct pcr_ctx {
 	int device = 0;
 	std::unique_ptr<HostPool> pool_;
@@ -841,36 +855,33 @@ struct pcr_ctx {
 	// (Last, so that every member above keeps its place: the screen pass is host-bound and two threads share this struct.)
 	DevBuf<uint8_t> pdim_in, pdim_tmp; DevBuf<float4> pdim_res; DevBuf<pcr_pool_dimer> pdim_rec, pdim_out; DevBuf<uint32_t> pdim_keep, pdim_off, pdim_flag;
 	bool pdim_attr_set = false;
-	// pcr_pool_products_tm (pcr_products_tm.inc): oligo tables + pair table + intended bitmap, per-entry / per-item counts and offsets, items, job offsets,
-	// per-job results, per-item Tm, the pool's bit rows, records, sort keys and order, error flag.  (After pdim_*, for the same reason.)
-	DevBuf<uint8_t> ptm_in, ptm_tmp; DevBuf<uint32_t> ptm_cnt, ptm_ord, ptm_flag; DevBuf<uint64_t> ptm_eoff, ptm_joff, ptm_ioff, ptm_keys, ptm_bits;
-	DevBuf<uint2> ptm_items; DevBuf<float4> ptm_res; DevBuf<uint2> ptm_item_tm; DevBuf<pcr_product_tm> ptm_rec;
-	// pcr_pool_probe_hits (pcr_probe_hits.inc): the same over primers + probes, then the kept products (two item indices and two DB slots each), the hit
-	// counts and offsets per product, the detected rows, hit records, sort keys and order.  (After ptm_*, for the same reason.)
-	DevBuf<uint8_t> pph_in, pph_tmp; DevBuf<uint32_t> pph_cnt, pph_hcnt, pph_ord, pph_flag; DevBuf<uint64_t> pph_eoff, pph_joff, pph_ioff, pph_hoff, pph_keys, pph_bits;
-	DevBuf<uint2> pph_items; DevBuf<float4> pph_res; DevBuf<uint2> pph_item_tm; DevBuf<uint4> pph_prod; DevBuf<pcr_probe_hit> pph_rec;
+	// pcr_pool_products_tm (pcr_products_tm.inc), beside the shared set at the end (`shared`): the pool's bit rows, records, sort keys and order.
+	// (After pdim_*, for the same reason; so is everything below.)
+	DevBuf<uint32_t> ptm_ord; DevBuf<uint64_t> ptm_keys, ptm_bits; DevBuf<pcr_product_tm> ptm_rec;
+	// pcr_pool_probe_hits (pcr_probe_hits.inc), beside `shared`: the kept products (two item indices and two DB slots each), the hit
+	// counts and offsets per product, the detected rows, hit records, sort keys and order.
+	DevBuf<uint32_t> pph_hcnt, pph_ord; DevBuf<uint64_t> pph_hoff, pph_keys, pph_bits; DevBuf<uint4> pph_prod; DevBuf<pcr_probe_hit> pph_rec;
 	// pcr_pool_amplicons (pcr_pool_amplicons.inc): the records' intervals, their {gc, other, reversed}, the u32 and u64 arrays carved from one buffer
 	// each (sort keys and order, run starts, representatives, counts, class tables), the info records, scan / sort scratch, the packed spellings.
-	// (After pph_*, for the same reason.)
 	DevBuf<uint4> pam_iv, pam_stat; DevBuf<uint32_t> pam_u32; DevBuf<uint64_t> pam_u64; DevBuf<pcr_amplicon_info> pam_info; DevBuf<uint8_t> pam_tmp, pam_packed;
 	uint32_t bg_max_pairs = 0;        // pcr_background_match: the largest batch whose oligo geometry k_bg_emit's workgroup can hold in LDS (0: not asked yet)
 	uint32_t amp_dbg_hash_bits = 0;   // PCRAMP_DEBUG_AMP_HASH_BITS=<bits>: pcr_pool_amplicons groups by that many bits of its hash, so that unequal spellings share a key and its resolve path runs (tests)
 	// pcr_pool_probe_candidates (pcr_probe_candidates.inc): the records' inserts, the start positions' offsets + chunk counts and offsets + error flag,
 	// the u32 and u64 arrays carved from one buffer each (occurrences, sort keys and indices, flags and their scans), the candidate and the kept
-	// records, scan / sort scratch.  (After pam_*, for the same reason.)
+	// records, scan / sort scratch.
 	DevBuf<uint4> ppc_iv; DevBuf<uint32_t> ppc_pos, ppc_u32; DevBuf<uint64_t> ppc_u64; DevBuf<pcr_probe_candidate> ppc_rec; DevBuf<uint8_t> ppc_tmp;
-	// pcr_pool_anneal_profile (pcr_anneal_profile.inc): oligo tables + row map + key table + intended bitmap + temperatures, per-entry / per-item counts
-	// and offsets, items, job offsets, per-job results, per-item Tm, error flag, the melt rows of the pool's distinct (plus, minus) keys + the spurious row,
-	// the histograms and per-temperature sums, pair_sequences.  (After ppc_*, for the same reason.)
-	DevBuf<uint8_t> anp_in, anp_tmp; DevBuf<uint32_t> anp_cnt, anp_flag, anp_pairseq; DevBuf<uint64_t> anp_eoff, anp_joff, anp_out;
-	DevBuf<uint2> anp_items; DevBuf<float4> anp_res; DevBuf<uint2> anp_item_tm; DevBuf<float> anp_melt;
-	// pcr_pool_conflicts (pcr_pool_conflicts.inc): oligo tables + each row's oligos + intended bitmap + the rows of every oligo, per-entry / per-item counts
-	// and offsets, items, job offsets, per-job results, per-item Tm, error flags, attribution offsets, (cell, sequence) keys and melt bits, the cells with a
-	// product and their aggregates, the dense aggregates; pcr_pool_dimers' tables, per-duplex results, per-cell records and keep words, the dense tm_max
-	// matrix; the cells' records, keep words and their scan, the kept records.  (After anp_*, for the same reason.)
-	DevBuf<uint8_t> pcf_in, pcf_tmp, pcf_din; DevBuf<uint32_t> pcf_cnt, pcf_flag, pcf_vals, pcf_ucell, pcf_dkeep, pcf_keep, pcf_koff;
-	DevBuf<uint64_t> pcf_eoff, pcf_joff, pcf_aoff, pcf_keys; DevBuf<uint2> pcf_items, pcf_item_tm; DevBuf<float4> pcf_res, pcf_dres;
+	// pcr_pool_anneal_profile (pcr_anneal_profile.inc), beside `shared`: the melt rows of the pool's distinct (plus, minus) keys + the spurious row,
+	// the histograms and per-temperature sums, pair_sequences.
+	DevBuf<uint32_t> anp_pairseq; DevBuf<uint64_t> anp_out; DevBuf<float> anp_melt;
+	// pcr_pool_conflicts (pcr_pool_conflicts.inc), beside `shared` (whose flag holds two words here: k_item_tm's, k_pool_dimer_reduce's): attribution
+	// offsets, (cell, sequence) keys and melt bits, the cells with a product and their aggregates, the dense aggregates; pcr_pool_dimers' tables,
+	// per-duplex results, per-cell records and keep words, the dense tm_max matrix; the cells' records, keep words and their scan, the kept records.
+	DevBuf<uint8_t> pcf_din; DevBuf<uint32_t> pcf_vals, pcf_ucell, pcf_dkeep, pcf_keep, pcf_koff;
+	DevBuf<uint64_t> pcf_aoff, pcf_keys; DevBuf<float4> pcf_dres;
 	DevBuf<uint4> pcf_uagg, pcf_dense; DevBuf<pcr_pool_dimer> pcf_drec; DevBuf<float> pcf_dmat; DevBuf<pcr_pool_conflict> pcf_rec, pcf_out;
+	// The one scratch set of pcr_pool_products_tm, pcr_pool_probe_hits, pcr_pool_anneal_profile and pcr_pool_conflicts: each call overwrites what the
+	// last one left.  pool_*, site_* and sv_* are apart: they keep their places above, and SvRun hands pointers into site_* / sv_* to pcr_site_repair.
+	ItemScratch shared;
 };
 
 namespace {

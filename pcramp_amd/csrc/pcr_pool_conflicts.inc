@@ -1,12 +1,12 @@
 // Which assays of a primer pool cannot share a tube: the pool's spurious products and its oligo-by-oligo dimers reduced to
-// unordered pairs of pool rows on the device (pcr_pool_conflicts; included by pcr_device.hip after pcr_anneal_profile.inc, whose
-// way of launching pcr_products_tm.inc's steps 1-3 it follows, and after pcr_pool_dimers.inc, whose plan and kernels it runs).
+// unordered pairs of pool rows on the device (pcr_pool_conflicts; included by pcr_device.hip after pcr_pool.inc and pcr_site_tm.inc,
+// whose stages are its steps 1-3, and after pcr_pool_dimers.inc, whose plan and kernels it runs).
 //
 // A spurious product (plus oligo x, minus oligo y) belongs to every unordered row pair {i, j} with (x in O(i), y in O(j)) or
 // (x in O(j), y in O(i)): the unordered pairs of rows(x) x rows(y).  The ordered walk meets {i, j} twice exactly when (j, i) is
 // in rows(x) x rows(y) as well; the copy with i > j is dropped then, which needs the two rows' oligo ids and no memory.
-//   1-3. the items, the jobs, k_site_tm, k_item_tm -> item_tm[] (pcr_products_tm.inc's steps, on this call's own scratch).
-//   4. k_conflict_join<false> / <true>: k_products_join's geometry and tests with the floor; a kept product that is no pool pair's
+//   1-3. the items, the jobs, k_site_tm, k_item_tm -> item_tm[] (item_count / item_fill, melt_items, on the shared scratch set).
+//   4. k_conflict_join<false> / <true>: k_products_join's walk (join_walk) with the floor; a kept product that is no pool pair's
 //      walks rows(x) x rows(y).  Count pass, scan, emit pass: one (cell << seq_bits | sequence, bits of v) pair per attribution.
 //   5. rocprim::radix_sort_pairs by (cell, sequence), then rocprim::reduce_by_key over the cells with {max of (v bits << 32 |
 //      ~sequence), count, count of (cell, sequence) run heads}: products, sequences, melt and melt_sequence of every cell with a
@@ -19,7 +19,7 @@
 //   8. k_conflict_cells: a thread per cell a <= b joins the aggregate with the maximum of the cell's (up to eight) dimer cells,
 //      the lowest (q, t) on a tie, and sets the flags and the keep word; an exclusive scan and k_conflict_compact put the kept
 //      cells into (row_a, row_b) order.
-// The call owns its scratch (pcr_ctx::pcf_*); the dG table is the handle's (th_dg, keyed by its salt).
+// Steps 1-4 work in pcr_ctx::shared (its flag holds two words here), the rest in pcr_ctx::pcf_*; the dG table is the handle's (th_dg, keyed by its salt).
 
 #include <rocprim/device/device_reduce_by_key.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -64,84 +64,55 @@ struct PcfMerge {
 	}
 };
 
-// k_products_join with the floor, over the spurious kept products only: one thread per item k, a plus-strand item (i, x) against
-// the minus-strand items (j, y) of its segment.  Every attribution of a product to a cell: <false> counts it, <true> writes its
-// key and the bits of v at att_off[k] ..
+// k_products_join with the floor, over the spurious kept products only: one thread per item k, join_walk.  Every attribution of a
+// product to a cell: <false> counts it, <true> writes its key and the bits of v at att_off[k] ..
 template<bool EMIT>
-__global__ __launch_bounds__(POOL_THREADS) void k_conflict_join(const DevEntry *__restrict__ db, uint32_t cap, const uint32_t *__restrict__ touched,
-	const uint32_t *__restrict__ seg_hi, const uint2 *__restrict__ items, uint32_t n_items, const uint64_t *__restrict__ item_off,
-	const PoolOligo *__restrict__ oligos, uint32_t n_ol, const uint4 *__restrict__ planes, const uint64_t *__restrict__ blk_off,
-	const uint64_t *__restrict__ len, const uint8_t *__restrict__ has_eos, int32_t amp_min, int32_t amp_max,
-	const ItemTm *__restrict__ item_tm, float tm_floor, const uint32_t *__restrict__ intended, const uint32_t *__restrict__ rows_off,
-	const uint32_t *__restrict__ rows, const uint2 *__restrict__ row_ol, uint32_t n_pool, uint32_t seq_bits,
-	uint32_t *__restrict__ count, const uint64_t *__restrict__ att_off, uint64_t *__restrict__ key, uint32_t *__restrict__ val)
+__global__ __launch_bounds__(POOL_THREADS) void k_conflict_join(const JoinIn J, const ItemTm *__restrict__ item_tm, float tm_floor,
+	const uint32_t *__restrict__ intended, const uint32_t *__restrict__ rows_off, const uint32_t *__restrict__ rows, const uint2 *__restrict__ row_ol,
+	uint32_t n_pool, uint32_t seq_bits, uint32_t *__restrict__ count, const uint64_t *__restrict__ att_off, uint64_t *__restrict__ key,
+	uint32_t *__restrict__ val)
 {
-	__shared__ int2 ss[POOL_MAX_OLIGOS];                                        // Word::start() / stop()
-	for(uint32_t o = threadIdx.x;o < n_ol;o += blockDim.x) ss[o] = make_int2(oligos[o].start, oligos[o].stop);
-	__syncthreads();
+	__shared__ int2 ss[POOL_MAX_OLIGOS];
+	join_geometry(J, ss);
 	const uint32_t k = blockIdx.x*blockDim.x + threadIdx.x;
-	if(k >= n_items) return;
-	const uint2 it = items[k];
+	if(k >= J.n_items) return;
+	const uint2 it = J.items[k];
 	const uint32_t g = it.x, x = it.y;
-	const uint32_t i = touched[g/cap]*cap + g % cap;
-	const DevEntry ei = db[i];
+	const uint32_t i = J.touched[g/J.cap]*J.cap + g % J.cap;
+	const DevEntry ei = J.db[i];
 	uint32_t c = 0;
 	uint64_t w = EMIT ? att_off[k] : 0;
 	if(ei.strand == 1){
-		const uint32_t hi = seg_hi[ei.seq];
-		const int32_t L = (int32_t)len[ei.seq];
-		const uint64_t blk_base = blk_off[ei.seq];
-		const bool eos = has_eos[ei.seq] != 0;
-		const int2 P = ss[x];
-		const int32_t p5 = ei.loc + P.x, p3 = ei.loc + P.y;                      // template_loc5/3, sequence.h:57-75
 		const ItemTm tp = item_tm[k];
 		const bool floored = tm_floor > 0.0f;
 		const uint32_t x0 = rows_off[x], x1 = rows_off[x + 1];
-		if(!(floored && tp.tm < tm_floor)){                                      // (a plus site below the floor keeps no product)
-			for(uint32_t j = i + 1;j < hi;++j){
-				const DevEntry ej = db[j];
-				if(ej.loc - ei.loc > amp_max + 128) break;
-				if(ej.strand != 2) continue;
-				const uint32_t gj = g + (j - i);                                     // same segment: consecutive DB threads
-				const uint64_t t_end = item_off[gj + 1];
-				for(uint64_t t = item_off[gj];t < t_end;++t){
-					const uint32_t y = items[t].y;
-					const int2 M = ss[y];
-					const int32_t m5 = ej.loc - M.y, m3 = ej.loc - M.x;
-					if(p3 >= m5) continue;                                           // pcr_assay.cpp:468-471
-					const int32_t amp_len = m3 - p5 + 1;
-					if(amp_len < amp_min || amp_len > amp_max) continue;             // :477-484
-					const int32_t in_start = p3 + 1 - 4;                             // :489-490
-					const int32_t in_len = m5 - in_start + 8;                        // :492-494
-					if(in_start < 0 || in_len < 0 || in_start + in_len > L) continue;
-					if(eos && has_split(planes, blk_base, in_start, in_len)) continue;   // :504-521
-					const uint32_t b = x*n_ol + y;
-					if((intended[b >> 5] >> (b & 31)) & 1u) continue;                // a pool pair's own product is no conflict
-					const ItemTm tm = item_tm[t];
-					const float v = ((tp.tm < tm.tm) ? tp.tm : tm.tm) + 0.0f;        // k_products_join's min; + 0.0f: -0 -> +0 (contraction is off)
-					if(floored && !(v >= tm_floor)) continue;
-					const uint32_t y0 = rows_off[y], y1 = rows_off[y + 1];
-					for(uint32_t ia = x0;ia < x1;++ia){
-						const uint32_t ri = rows[ia];
-						for(uint32_t ja = y0;ja < y1;++ja){
-							const uint32_t rj = rows[ja];
-							if(ri > rj){
-								// {rj, ri} arises again as (rj in rows(x), ri in rows(y)): that copy, with the lower row first, is the one kept
-								const uint2 oj = row_ol[rj], oi = row_ol[ri];
-								if((oj.x == x || oj.y == x) && (oi.x == y || oi.y == y)) continue;
-							}
-							if(EMIT){
-								const uint32_t cell = (ri <= rj) ? pcf_cell(ri, rj, n_pool) : pcf_cell(rj, ri, n_pool);
-								key[w] = ((uint64_t)cell << seq_bits) | ei.seq;
-								val[w] = __float_as_uint(v);
-								++w;
-							}
-							else ++c;
-						}
+		auto keep = [&](uint64_t t, uint32_t y, uint32_t, int32_t, int32_t, int32_t, int32_t){
+			const uint32_t b = x*J.n_ol + y;
+			if((intended[b >> 5] >> (b & 31)) & 1u) return;                      // a pool pair's own product is no conflict
+			const ItemTm tm = item_tm[t];
+			const float v = ((tp.tm < tm.tm) ? tp.tm : tm.tm) + 0.0f;            // k_products_join's min; + 0.0f: -0 -> +0 (contraction is off)
+			if(floored && !(v >= tm_floor)) return;
+			const uint32_t y0 = rows_off[y], y1 = rows_off[y + 1];
+			for(uint32_t ia = x0;ia < x1;++ia){
+				const uint32_t ri = rows[ia];
+				for(uint32_t ja = y0;ja < y1;++ja){
+					const uint32_t rj = rows[ja];
+					if(ri > rj){
+						// {rj, ri} arises again as (rj in rows(x), ri in rows(y)): that copy, with the lower row first, is the one kept
+						const uint2 oj = row_ol[rj], oi = row_ol[ri];
+						if((oj.x == x || oj.y == x) && (oi.x == y || oi.y == y)) continue;
 					}
+					if(EMIT){
+						const uint32_t cell = (ri <= rj) ? pcf_cell(ri, rj, n_pool) : pcf_cell(rj, ri, n_pool);
+						key[w] = ((uint64_t)cell << seq_bits) | ei.seq;
+						val[w] = __float_as_uint(v);
+						++w;
+					}
+					else ++c;
 				}
 			}
-		}
+		};
+		if(!(floored && tp.tm < tm_floor)) join_walk<false>(J, ss, g, x, i, ei, 0u, keep);   // (a plus site below the floor keeps no product)
 	}
 	if(!EMIT) count[k] = c;
 }
@@ -243,89 +214,42 @@ int conflict_products(pcr_ctx *ctx, SeqSet &S, const std::vector<PoolOligo> &ol,
 	memcpy(blob.data() + ol_bytes + olx_bytes + rol_bytes, intended.data(), int_bytes);
 	memcpy(blob.data() + ol_bytes + olx_bytes + rol_bytes + int_bytes, rows_off.data(), off_bytes);
 	memcpy(blob.data() + ol_bytes + olx_bytes + rol_bytes + int_bytes + off_bytes, rows.data(), rows_bytes);
-	if((rc = ctx->pcf_in.ensure(blob.size())) != PCR_OK) return rc;
-	const PoolOligo *d_ol = (const PoolOligo *)ctx->pcf_in.p;
-	const SiteOligoX *d_olx = (const SiteOligoX *)(ctx->pcf_in.p + ol_bytes);
-	const uint2 *d_row_ol = (const uint2 *)(ctx->pcf_in.p + ol_bytes + olx_bytes);
-	const uint32_t *d_intended = (const uint32_t *)(ctx->pcf_in.p + ol_bytes + olx_bytes + rol_bytes);
-	const uint32_t *d_rows_off = (const uint32_t *)(ctx->pcf_in.p + ol_bytes + olx_bytes + rol_bytes + int_bytes);
-	const uint32_t *d_rows = (const uint32_t *)(ctx->pcf_in.p + ol_bytes + olx_bytes + rol_bytes + int_bytes + off_bytes);
-	HIP_TRY(hipMemcpyAsync(ctx->pcf_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+	ItemScratch &X = ctx->shared;
+	const ItemBufs B = X.bufs();
+	if((rc = X.in.ensure(blob.size())) != PCR_OK) return rc;
+	const PoolOligo *d_ol = (const PoolOligo *)X.in.p;
+	const SiteOligoX *d_olx = (const SiteOligoX *)(X.in.p + ol_bytes);
+	const uint2 *d_row_ol = (const uint2 *)(X.in.p + ol_bytes + olx_bytes);
+	const uint32_t *d_intended = (const uint32_t *)(X.in.p + ol_bytes + olx_bytes + rol_bytes);
+	const uint32_t *d_rows_off = (const uint32_t *)(X.in.p + ol_bytes + olx_bytes + rol_bytes + int_bytes);
+	const uint32_t *d_rows = (const uint32_t *)(X.in.p + ol_bytes + olx_bytes + rol_bytes + int_bytes + off_bytes);
+	HIP_TRY(hipMemcpyAsync(X.in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
 	HIP_TRY(hipStreamSynchronize(ctx->stream));                                   // (blob is this function's)
 	if(S.n_entries == 0 || S.n_touched == 0) return PCR_OK;
-	// ---- 1. the items (k_pool_entry_oligos: count, scan, fill)
-	const uint32_t n_db = S.n_touched*S.db_cap;
-	if((rc = ctx->pcf_cnt.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
-	if((rc = ctx->pcf_eoff.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->pcf_cnt.p + n_db, 0, sizeof(uint32_t), ctx->stream));
-	size_t tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pcf_cnt.p, ctx->pcf_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	if((rc = ctx->pcf_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-	const unsigned grid_e = std::min<unsigned>((n_db + POOL_THREADS - 1)/POOL_THREADS, ctx->n_cu*8);
-	hipLaunchKernelGGL(k_pool_entry_oligos<false>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
-		S.d_seg_hi, S.d_active.p, d_ol, n_ol, ctx->pcf_cnt.p, (const uint64_t *)nullptr, (uint2 *)nullptr);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(rocprim::exclusive_scan(ctx->pcf_tmp.p, tmp, ctx->pcf_cnt.p, ctx->pcf_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	// ---- 1. the items
 	uint64_t n_items = 0;
-	HIP_TRY(hipMemcpyAsync(&n_items, ctx->pcf_eoff.p + n_db, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if((rc = item_count(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
 	if(n_items >= POOL_MAX_ITEMS){ g_err = "pcr_pool_conflicts: too many (entry, oligo) hits"; return PCR_ERR_CAPACITY; }
 	if(n_items == 0) return PCR_OK;
-	if((rc = ctx->pcf_items.ensure(n_items)) != PCR_OK) return rc;
-	hipLaunchKernelGGL(k_pool_entry_oligos<true>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
-		S.d_seg_hi, S.d_active.p, d_ol, n_ol, (uint32_t *)nullptr, (const uint64_t *)ctx->pcf_eoff.p, ctx->pcf_items.p);
-	HIP_TRY(hipGetLastError());
+	if((rc = item_fill(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
 	const uint32_t ni = (uint32_t)n_items;
 	const unsigned grid_i = (ni + POOL_THREADS - 1)/POOL_THREADS;
-	if((rc = ctx->pcf_cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;         // (the entry counts are spent)
-	// ---- 2. job offsets, the jobs (k_site_jobs, k_site_tm as they stand)
-	if((rc = ctx->pcf_joff.ensure((size_t)ni + 1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->pcf_cnt.p + ni, 0, sizeof(uint32_t), ctx->stream));
-	hipLaunchKernelGGL(k_site_jobs, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint2 *)ctx->pcf_items.p, ni, d_olx, ctx->pcf_cnt.p);
-	HIP_TRY(hipGetLastError());
-	tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pcf_cnt.p, ctx->pcf_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	if((rc = ctx->pcf_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-	HIP_TRY(rocprim::exclusive_scan(ctx->pcf_tmp.p, tmp, ctx->pcf_cnt.p, ctx->pcf_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	uint64_t n_jobs64 = 0;
-	HIP_TRY(hipMemcpyAsync(&n_jobs64, ctx->pcf_joff.p + ni, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));
-	if(n_jobs64 >= POOL_MAX_ITEMS){ g_err = "pcr_pool_conflicts: too many (site, expansion) jobs"; return PCR_ERR_CAPACITY; }
-	const uint32_t n_jobs = (uint32_t)n_jobs64;
-	if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
-	if(!ctx->site_attr_set){                                                   // (k_site_tm's own flag: the attribute is the kernel's)
-		HIP_TRY(hipFuncSetAttribute((const void *)k_site_tm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SITE_LDS));
-		ctx->site_attr_set = true;
-	}
-	if((rc = ctx->pcf_res.ensure(n_jobs)) != PCR_OK) return rc;
-	if((rc = ctx->pcf_item_tm.ensure(ni)) != PCR_OK) return rc;
-	// at most one block per CU (a block takes most of a CU's LDS), the waves striding over the jobs
-	const unsigned grid_j = std::max(1u, std::min<unsigned>((n_jobs + SITE_WAVES - 1)/SITE_WAVES, (unsigned)ctx->n_cu));
-	hipLaunchKernelGGL(k_site_tm, dim3(grid_j), dim3(SITE_THREADS), SITE_LDS, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
-		(const uint2 *)ctx->pcf_items.p, ni, (const uint64_t *)ctx->pcf_joff.p, n_jobs, d_ol, d_olx, (const int *)ctx->th_dg.p, logf(args->salt), ctx->pcf_res.p);
-	HIP_TRY(hipGetLastError());
-	// ---- 3. Tm per item
-	hipLaunchKernelGGL(k_item_tm, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint64_t *)ctx->pcf_joff.p, ni,
-		(const float4 *)ctx->pcf_res.p, (ItemTm *)ctx->pcf_item_tm.p, ctx->pcf_flag.p);
-	HIP_TRY(hipGetLastError());
+	if((rc = X.cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;                // (the entry counts are spent)
+	// ---- 2. job offsets, the jobs; 3. Tm per item
+	if((rc = melt_items("pcr_pool_conflicts", ctx, S, d_ol, d_olx, ni, args->salt, B)) != PCR_OK) return rc;
 	// ---- 4. the join: count, scan, emit
 	const uint32_t seq_bits = pool_bits(S.n);
-	if((rc = ctx->pcf_aoff.ensure((size_t)ni + 1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->pcf_cnt.p + ni, 0, sizeof(uint32_t), ctx->stream));
-	hipLaunchKernelGGL(k_conflict_join<false>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
-		ctx->pcf_items.p, ni, (const uint64_t *)ctx->pcf_eoff.p, d_ol, n_ol, S.planes.p, S.d_blk_off.p, S.d_len.p, S.d_has_eos.p,
-		amp_min, amp_max, (const ItemTm *)ctx->pcf_item_tm.p, tm_floor, d_intended, d_rows_off, d_rows, d_row_ol, n_pool, seq_bits,
-		ctx->pcf_cnt.p, (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr);
+	const JoinIn J{S.db.p, S.db_cap, S.touched.p, S.d_seg_hi, X.items.p, ni, X.eoff.p, d_ol, n_ol, S.planes.p, S.d_blk_off.p, S.d_len.p,
+		S.d_has_eos.p, amp_min, amp_max};
+	hipLaunchKernelGGL(k_conflict_join<false>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, (const ItemTm *)X.item_tm.p, tm_floor, d_intended,
+		d_rows_off, d_rows, d_row_ol, n_pool, seq_bits, X.cnt.p, (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr);
 	HIP_TRY(hipGetLastError());
-	tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pcf_cnt.p, ctx->pcf_aoff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	if((rc = ctx->pcf_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-	HIP_TRY(rocprim::exclusive_scan(ctx->pcf_tmp.p, tmp, ctx->pcf_cnt.p, ctx->pcf_aoff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
 	uint64_t total = 0;
 	uint32_t bad = 0;
-	HIP_TRY(hipMemcpyAsync(&total, ctx->pcf_aoff.p + ni, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipMemcpyAsync(&bad, ctx->pcf_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if((rc = scan_total(ctx, X.cnt.p, ctx->pcf_aoff, X.tmp, ni, total, [&]() -> int {
+		HIP_TRY(hipMemcpyAsync(&bad, X.flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		return PCR_OK;
+	})) != PCR_OK) return rc;
 	if(bad & 1u){ g_err = "pcr_pool_conflicts: internal trace-back error"; return PCR_ERR_RANGE; }
 	if(total >= PCF_MAX_ATTRIBUTIONS){ g_err = "pcr_pool_conflicts: 2^31 or more (product, cell) attributions"; return PCR_ERR_CAPACITY; }
 	if(total == 0) return PCR_OK;
@@ -334,10 +258,8 @@ int conflict_products(pcr_ctx *ctx, SeqSet &S, const std::vector<PoolOligo> &ol,
 	if((rc = ctx->pcf_vals.ensure(2*(size_t)na)) != PCR_OK) return rc;
 	uint64_t *k0 = ctx->pcf_keys.p, *k1 = k0 + na;
 	uint32_t *v0 = ctx->pcf_vals.p, *v1 = v0 + na;
-	hipLaunchKernelGGL(k_conflict_join<true>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
-		ctx->pcf_items.p, ni, (const uint64_t *)ctx->pcf_eoff.p, d_ol, n_ol, S.planes.p, S.d_blk_off.p, S.d_len.p, S.d_has_eos.p,
-		amp_min, amp_max, (const ItemTm *)ctx->pcf_item_tm.p, tm_floor, d_intended, d_rows_off, d_rows, d_row_ol, n_pool, seq_bits,
-		(uint32_t *)nullptr, (const uint64_t *)ctx->pcf_aoff.p, k0, v0);
+	hipLaunchKernelGGL(k_conflict_join<true>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, (const ItemTm *)X.item_tm.p, tm_floor, d_intended,
+		d_rows_off, d_rows, d_row_ol, n_pool, seq_bits, (uint32_t *)nullptr, (const uint64_t *)ctx->pcf_aoff.p, k0, v0);
 	HIP_TRY(hipGetLastError());
 	// ---- 5. (cell, sequence) order, then one aggregate per cell
 	const uint32_t n_slots = std::min(na, n_cells);                              // the cells with a product
@@ -351,9 +273,9 @@ int conflict_products(pcr_ctx *ctx, SeqSet &S, const std::vector<PoolOligo> &ol,
 	HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, k0, k1, v0, v1, na, 0, seq_bits + PCF_CELL_BITS, ctx->stream));
 	HIP_TRY(rocprim::reduce_by_key(nullptr, t2, cells_in, aggs_in, na, ctx->pcf_ucell.p, (ConflictAgg *)ctx->pcf_uagg.p, d_n_unique,
 		PcfMerge(), rocprim::equal_to<uint32_t>(), ctx->stream));
-	if((rc = ctx->pcf_tmp.ensure(std::max(t1, t2) + 16)) != PCR_OK) return rc;
-	HIP_TRY(rocprim::radix_sort_pairs(ctx->pcf_tmp.p, t1, k0, k1, v0, v1, na, 0, seq_bits + PCF_CELL_BITS, ctx->stream));
-	HIP_TRY(rocprim::reduce_by_key(ctx->pcf_tmp.p, t2, cells_in, aggs_in, na, ctx->pcf_ucell.p, (ConflictAgg *)ctx->pcf_uagg.p, d_n_unique,
+	if((rc = ctx->shared.tmp.ensure(std::max(t1, t2) + 16)) != PCR_OK) return rc;
+	HIP_TRY(rocprim::radix_sort_pairs(ctx->shared.tmp.p, t1, k0, k1, v0, v1, na, 0, seq_bits + PCF_CELL_BITS, ctx->stream));
+	HIP_TRY(rocprim::reduce_by_key(ctx->shared.tmp.p, t2, cells_in, aggs_in, na, ctx->pcf_ucell.p, (ConflictAgg *)ctx->pcf_uagg.p, d_n_unique,
 		PcfMerge(), rocprim::equal_to<uint32_t>(), ctx->stream));
 	// ---- 6. into the dense array
 	const unsigned grid_u = std::max(1u, std::min<unsigned>((n_slots + POOL_THREADS - 1)/POOL_THREADS, ctx->n_cu*8));
@@ -416,7 +338,7 @@ int conflict_dimers(pcr_ctx *ctx, const pcr_thermo_args *args, const std::vector
 		HIP_TRY(hipGetLastError());
 		const unsigned grid_c = (nc + POOL_THREADS - 1)/POOL_THREADS;
 		hipLaunchKernelGGL(k_pool_dimer_reduce, dim3(grid_c), dim3(POOL_THREADS), 0, ctx->stream, P, (uint32_t)c0, nc, j0, (const float4 *)ctx->pcf_dres.p,
-			0.0f, ctx->pcf_drec.p, ctx->pcf_dkeep.p, ctx->pcf_flag.p + 1);
+			0.0f, ctx->pcf_drec.p, ctx->pcf_dkeep.p, ctx->shared.flag.p + 1);
 		HIP_TRY(hipGetLastError());
 		hipLaunchKernelGGL(k_conflict_dimer_store, dim3(grid_c), dim3(POOL_THREADS), 0, ctx->stream, (const pcr_pool_dimer *)ctx->pcf_drec.p, nc, ctx->pcf_dmat.p + c0);
 		HIP_TRY(hipGetLastError());
@@ -424,7 +346,7 @@ int conflict_dimers(pcr_ctx *ctx, const pcr_thermo_args *args, const std::vector
 		c0 = c1;
 	}
 	uint32_t bad = 0;
-	HIP_TRY(hipMemcpyAsync(&bad, ctx->pcf_flag.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipMemcpyAsync(&bad, ctx->shared.flag.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
 	if(bad & 1u){ g_err = "pcr_pool_conflicts: internal trace-back error"; return PCR_ERR_RANGE; }
 	return PCR_OK;
@@ -440,45 +362,24 @@ int64_t pcr_pool_conflicts(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, ui
 {
 	static_assert(sizeof(pcr_pool_conflict) == 48, "record layout");
 	static_assert(sizeof(ConflictAgg) == 16 && sizeof(uint4) == 16, "the dense array is kept as uint4");
-	// ---- the arguments, before the handle (pcr_pool_products_tm's checks in its order, then the dimer arguments)
+	// ---- the arguments, before the handle (pcr_pool_products_tm's checks in its order, the oligo table, then the dimer arguments)
 	if(!set_ok(which)){ g_err = "pcr_pool_conflicts: unknown sequence set"; return PCR_ERR_ARG; }
 	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = "pcr_pool_conflicts: PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
 	if(!args || (n_pool && (!pool || !oligo_id)) || (cap && !out)){ g_err = "pcr_pool_conflicts: bad argument"; return PCR_ERR_ARG; }
 	if(n_pool > PCR_POOL_MAX_PAIRS){ g_err = "pcr_pool_conflicts: pool larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
 	if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f)){ g_err = "pcr_pool_conflicts: negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
 	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = "pcr_pool_conflicts: salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
-	// the distinct oligos, in order of first appearance (as pcr_pool_products_tm and pcr_pool_dimers)
 	std::vector<PoolOligo> ol;
 	std::vector<SiteOligoX> olx;
-	std::vector<DimerOligo> dol;
-	std::map<std::pair<uint64_t, uint64_t>, uint32_t> id_of;
-	const float thr2 = threshold*threshold;                                      // pcr_assay.cpp:775-776
+	if(site_oligo_table("pcr_pool_conflicts", "an oligo", "primer_strand", pool, n_pool, threshold, args, template_strand, oligo_id, ol, olx) != PCR_OK) return PCR_ERR_ARG;
+	std::vector<DimerOligo> dol;                                                 // pcr_pool_dimers' records of the same oligos
 	for(uint32_t s = 0;s < 2*n_pool;++s){
-		const pcr_word128 &wd = (s & 1) ? pool[s/2].r : pool[s/2].f;
-		auto ins = id_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)ol.size()));
-		if(ins.second){
-			OligoDev d; fill_oligo(d, wd.w, thr2);
-			const uint32_t occ = pcrhost::planes_occupied(d.m);
-			if(!occ || __builtin_popcount(occ) != d.stop - d.start + 1){
-				g_err = "pcr_pool_conflicts: an oligo is empty or has a hole between its ends (NucCruc::set_query throws)"; return PCR_ERR_ARG;
-			}
-			const double degen = pcrhost::planes_degeneracy(d.m);
-			if(degen > (double)PCR_SITE_MAX_EXPANSIONS){ g_err = "pcr_pool_conflicts: an oligo has more than PCR_SITE_MAX_EXPANSIONS expansions"; return PCR_ERR_ARG; }
-			PoolOligo p; p.m = d.m; p.floor2 = d.floor2; p.start = d.start; p.stop = d.stop; p.pad = 0;
-			ol.push_back(p);
-			const float ca = (float)(args->primer_strand/degen), cb = template_strand;
-			const float strand = (ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca;          // nuc_cruc.h:832-837
-			if(!(strand > 0.0f)){ g_err = "pcr_pool_conflicts: the strand concentration of an oligo's duplex is zero (primer_strand / degeneracy and template_strand both 0)"; return PCR_ERR_ARG; }
-			SiteOligoX x; x.n_exp = (uint32_t)degen;
-			x.log_strand = logf(strand);
-			olx.push_back(x);
-			DimerOligo q;                                                          // pcr_pool_dimers' record of the same oligo
-			q.m = pcrhost::planes_of_word(wd.w);
-			q.start = pcrhost::planes_start(q.m); q.stop = pcrhost::planes_stop(q.m);
-			q.n_exp = (uint32_t)degen; q.cls = 0;
-			dol.push_back(q);
-		}
-		oligo_id[s] = ins.first->second;
+		if(oligo_id[s] != dol.size()) continue;                                  // (ids count up in order of first appearance)
+		DimerOligo q;
+		q.m = pcrhost::planes_of_word(((s & 1) ? pool[s/2].r : pool[s/2].f).w);
+		q.start = pcrhost::planes_start(q.m); q.stop = pcrhost::planes_stop(q.m);
+		q.n_exp = olx[dol.size()].n_exp; q.cls = 0;
+		dol.push_back(q);
 	}
 	if(!std::isfinite(tm_floor)){ g_err = "pcr_pool_conflicts: tm_floor is not finite"; return PCR_ERR_ARG; }
 	if(dimer_rule != PCR_DIMER_RULE_POOL && dimer_rule != PCR_DIMER_RULE_ASSAY && dimer_rule != PCR_CONFLICT_NO_DIMERS){
@@ -534,30 +435,23 @@ int64_t pcr_pool_conflicts(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, ui
 	{ const int erc = ensure_touched(ctx, S); if(erc != PCR_OK) return erc; }
 	int rc;
 	const uint32_t n_cells = n_pool*(n_pool + 1u)/2u;
-	if((rc = ctx->pcf_flag.ensure(2)) != PCR_OK) return rc;                      // [0]: k_item_tm's, [1]: k_pool_dimer_reduce's
-	HIP_TRY(hipMemsetAsync(ctx->pcf_flag.p, 0, 2*sizeof(uint32_t), ctx->stream));
+	if((rc = ctx->shared.flag.ensure(2)) != PCR_OK) return rc;                      // [0]: k_item_tm's (melt_items zeroes it), [1]: k_pool_dimer_reduce's
+	HIP_TRY(hipMemsetAsync(ctx->shared.flag.p + 1, 0, sizeof(uint32_t), ctx->stream));
 	if((rc = ctx->pcf_dense.ensure(n_cells)) != PCR_OK) return rc;
 	HIP_TRY(hipMemsetAsync(ctx->pcf_dense.p, 0, (size_t)n_cells*sizeof(uint4), ctx->stream));
 	if((rc = conflict_products(ctx, S, ol, olx, oligo_id, n_pool, amp_min, amp_max, args, tm_floor, n_cells)) != PCR_OK) return rc;
 	if(dimers && (rc = conflict_dimers(ctx, args, dol, pref, row, logs, (uint32_t)cls_degen.size())) != PCR_OK) return rc;
 	// ---- 8. the records, the kept ones in (row_a, row_b) order
 	const size_t ol_bytes = ol.size()*sizeof(PoolOligo), olx_bytes = olx.size()*sizeof(SiteOligoX);
-	const uint2 *d_row_ol = (const uint2 *)(ctx->pcf_in.p + ol_bytes + olx_bytes);   // (conflict_products' upload)
+	const uint2 *d_row_ol = (const uint2 *)(ctx->shared.in.p + ol_bytes + olx_bytes);   // (conflict_products' upload)
 	if((rc = ctx->pcf_rec.ensure(n_cells)) != PCR_OK) return rc;
 	if((rc = ctx->pcf_keep.ensure((size_t)n_cells + 1)) != PCR_OK) return rc;
-	if((rc = ctx->pcf_koff.ensure((size_t)n_cells + 1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->pcf_keep.p + n_cells, 0, sizeof(uint32_t), ctx->stream));
 	hipLaunchKernelGGL(k_conflict_cells, dim3((n_pool + POOL_THREADS - 1)/POOL_THREADS, n_pool), dim3(POOL_THREADS), 0, ctx->stream,
 		(const ConflictAgg *)ctx->pcf_dense.p, dimers ? (const float *)ctx->pcf_dmat.p : (const float *)nullptr, n_ol, d_row_ol, n_pool, dimer_floor,
 		ctx->pcf_rec.p, ctx->pcf_keep.p);
 	HIP_TRY(hipGetLastError());
-	size_t tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pcf_keep.p, ctx->pcf_koff.p, uint32_t(0), (size_t)n_cells + 1, rocprim::plus<uint32_t>(), ctx->stream));
-	if((rc = ctx->pcf_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-	HIP_TRY(rocprim::exclusive_scan(ctx->pcf_tmp.p, tmp, ctx->pcf_keep.p, ctx->pcf_koff.p, uint32_t(0), (size_t)n_cells + 1, rocprim::plus<uint32_t>(), ctx->stream));
 	uint32_t kept = 0;
-	HIP_TRY(hipMemcpyAsync(&kept, ctx->pcf_koff.p + n_cells, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if((rc = scan_total(ctx, ctx->pcf_keep.p, ctx->pcf_koff, ctx->shared.tmp, n_cells, kept)) != PCR_OK) return rc;
 	if(kept == 0 || kept > cap) return (int64_t)kept;                            // count only: out is left as it is
 	if((rc = ctx->pcf_out.ensure(kept)) != PCR_OK) return rc;
 	hipLaunchKernelGGL(k_conflict_compact, dim3((n_cells + POOL_THREADS - 1)/POOL_THREADS), dim3(POOL_THREADS), 0, ctx->stream,

@@ -1,10 +1,11 @@
 // Which products of a pool a probe binds inside, and which sequences each (F, R, probe) assay detects (pcr_pool_probe_hits;
-// included by pcr_device.hip after pcr_products_tm.inc, whose item, job and Tm kernels it launches as they are).
+// included by pcr_device.hip after pcr_pool.inc and pcr_site_tm.inc, whose item and melt stages it runs).
 //
 // One oligo table holds the pool's distinct primers (pcr_pool_products' ids 0 .. n_prim - 1) and then its distinct probes
 // (table entry n_prim + probe id); SiteOligoX::log_strand carries each oligo's own concentration.  The (entry, oligo) items,
-// their jobs and item_tm[] are then pcr_pool_products_tm's steps 1-3 over that table.  From there:
-//   4. k_probe_products<false> / <true>: k_products_join's walk, geometry and floor, with primer items only in either role.
+// their jobs and item_tm[] are then pcr_pool_products_tm's steps 1-3 over that table (item_count / item_fill, melt_items).
+// From there:
+//   4. k_probe_products<false> / <true>: k_products_join's walk (join_walk) and floor, with primer items only in either role.
 //      The count pass also ORs the bit of every kept product of a pool pair WITHOUT a probe into that pair's row (its row is
 //      pcr_pool_products_tm's fr | rf); the emit pass compacts the kept products: {plus item, minus item, plus slot, minus slot}.
 //   5. k_probe_hits<false> / <true>: one wave per kept product.  A probe site inside it (p3 < loc5, loc3 < m5) lies on an entry
@@ -16,7 +17,7 @@
 //      record lands does not depend on scheduling).
 //   6. The record order: three stable radix sorts, least significant key first -- (probe, probe_loc5, probe_strand), (begin, end),
 //      (plus_oligo, minus_oligo, sequence) -- and a gather.
-// The call owns its scratch (pcr_ctx::pph_*); the dG table is the handle's (th_dg, keyed by its salt as for every thermo call).
+// Steps 1-3 work in the scratch set shared with pcr_pool_products_tm and the others (pcr_ctx::shared), the rest in pcr_ctx::pph_*; the dG table is the handle's (th_dg, keyed by its salt as for every thermo call).
 
 namespace {
 
@@ -37,72 +38,42 @@ __device__ __forceinline__ uint32_t probe_assay_row(const ProbeAssay *__restrict
 	return (a.key == key) ? a.row : PPH_NO_ROW;
 }
 
-// k_products_join over the primer items (oligo < n_prim) of a table that also lists probes.  <false>: count[k], and with
-// bits != NULL the bit of every kept product whose (plus, minus) is a pool pair without a probe; <true>: the kept products at
-// prod_off[k] .. as {k, t, plus slot, minus slot}.
+// k_products_join over the primer items (oligo < n_prim) of a table that also lists probes: join_walk<true> with n_minus = n_prim.
+// <false>: count[k], and with bits != NULL the bit of every kept product whose (plus, minus) is a pool pair without a probe;
+// <true>: the kept products at prod_off[k] .. as {k, t, plus slot, minus slot}.
 template<bool EMIT>
-__global__ __launch_bounds__(POOL_THREADS) void k_probe_products(const DevEntry *__restrict__ db, uint32_t cap, const uint32_t *__restrict__ touched,
-	const uint32_t *__restrict__ seg_hi, const uint2 *__restrict__ items, uint32_t n_items, const uint64_t *__restrict__ item_off,
-	const PoolOligo *__restrict__ oligos, uint32_t n_ol, uint32_t n_prim, const uint4 *__restrict__ planes, const uint64_t *__restrict__ blk_off,
-	const uint64_t *__restrict__ len, const uint8_t *__restrict__ has_eos, int32_t amp_min, int32_t amp_max,
-	const ItemTm *__restrict__ item_tm, float tm_floor, const uint32_t *__restrict__ intended, const ProbeAssay *__restrict__ tab,
-	uint32_t n_tab, unsigned long long *__restrict__ bits, uint32_t words,
+__global__ __launch_bounds__(POOL_THREADS) void k_probe_products(const JoinIn J, uint32_t n_prim, const ItemTm *__restrict__ item_tm, float tm_floor,
+	const uint32_t *__restrict__ intended, const ProbeAssay *__restrict__ tab, uint32_t n_tab, unsigned long long *__restrict__ bits, uint32_t words,
 	uint32_t *__restrict__ count, const uint64_t *__restrict__ prod_off, uint4 *__restrict__ prod)
 {
-	__shared__ int2 ss[POOL_MAX_OLIGOS];                                        // Word::start() / stop()
-	for(uint32_t o = threadIdx.x;o < n_ol;o += blockDim.x) ss[o] = make_int2(oligos[o].start, oligos[o].stop);
-	__syncthreads();
+	__shared__ int2 ss[POOL_MAX_OLIGOS];
+	join_geometry(J, ss);
 	const uint32_t k = blockIdx.x*blockDim.x + threadIdx.x;
-	if(k >= n_items) return;
-	const uint2 it = items[k];
+	if(k >= J.n_items) return;
+	const uint2 it = J.items[k];
 	const uint32_t g = it.x, x = it.y;
 	uint32_t c = 0;
 	uint64_t w = EMIT ? prod_off[k] : 0;
 	if(x < n_prim){                                                             // (a probe takes no primer role)
-		const uint32_t i = touched[g/cap]*cap + g % cap;
-		const DevEntry ei = db[i];
+		const uint32_t i = J.touched[g/J.cap]*J.cap + g % J.cap;
+		const DevEntry ei = J.db[i];
 		if(ei.strand == 1){
-			const uint32_t hi = seg_hi[ei.seq];
-			const int32_t L = (int32_t)len[ei.seq];
-			const uint64_t blk_base = blk_off[ei.seq];
-			const bool eos = has_eos[ei.seq] != 0;
-			const int2 P = ss[x];
-			const int32_t p5 = ei.loc + P.x, p3 = ei.loc + P.y;                  // template_loc5/3, sequence.h:57-75
 			const ItemTm tp = item_tm[k];
 			const bool floored = tm_floor > 0.0f;
-			if(!(floored && tp.tm < tm_floor)){                                  // (a plus site below the floor keeps no product)
-				for(uint32_t j = i + 1;j < hi;++j){
-					const DevEntry ej = db[j];
-					if(ej.loc - ei.loc > amp_max + 128) break;
-					if(ej.strand != 2) continue;
-					const uint32_t gj = g + (j - i);                             // same segment: consecutive DB threads
-					const uint64_t t_end = item_off[gj + 1];
-					for(uint64_t t = item_off[gj];t < t_end;++t){
-						const uint32_t y = items[t].y;
-						if(y >= n_prim) continue;
-						const int2 M = ss[y];
-						const int32_t m5 = ej.loc - M.y, m3 = ej.loc - M.x;
-						if(p3 >= m5) continue;                                   // pcr_assay.cpp:468-471
-						const int32_t amp_len = m3 - p5 + 1;
-						if(amp_len < amp_min || amp_len > amp_max) continue;     // :477-484
-						const int32_t in_start = p3 + 1 - 4;                     // :489-490
-						const int32_t in_len = m5 - in_start + 8;                // :492-494
-						if(in_start < 0 || in_len < 0 || in_start + in_len > L) continue;
-						if(eos && has_split(planes, blk_base, in_start, in_len)) continue;   // :504-521
-						const ItemTm tm = item_tm[t];
-						if(floored && !(((tp.tm < tm.tm) ? tp.tm : tm.tm) >= tm_floor)) continue;   // min(tm_plus, tm_minus) >= tm_floor
-						if(EMIT) prod[w++] = make_uint4(k, (uint32_t)t, i, j);
-						else{
-							++c;
-							const uint32_t b = x*n_prim + y;
-							if(bits && ((intended[b >> 5] >> (b & 31)) & 1u)){
-								const uint32_t row = probe_assay_row(tab, n_tab, ((uint64_t)b << 32) | PCR_NO_PROBE);
-								if(row != PPH_NO_ROW) atomicOr(bits + (size_t)row*words + (ei.seq >> 6), 1ull << (ei.seq & 63u));
-							}
-						}
+			auto keep = [&](uint64_t t, uint32_t y, uint32_t j, int32_t, int32_t, int32_t, int32_t){
+				const ItemTm tm = item_tm[t];
+				if(floored && !(((tp.tm < tm.tm) ? tp.tm : tm.tm) >= tm_floor)) return;   // min(tm_plus, tm_minus) >= tm_floor
+				if(EMIT) prod[w++] = make_uint4(k, (uint32_t)t, i, j);
+				else{
+					++c;
+					const uint32_t b = x*n_prim + y;
+					if(bits && ((intended[b >> 5] >> (b & 31)) & 1u)){
+						const uint32_t row = probe_assay_row(tab, n_tab, ((uint64_t)b << 32) | PCR_NO_PROBE);
+						if(row != PPH_NO_ROW) atomicOr(bits + (size_t)row*words + (ei.seq >> 6), 1ull << (ei.seq & 63u));
 					}
 				}
-			}
+			};
+			if(!(floored && tp.tm < tm_floor)) join_walk<true>(J, ss, g, x, i, ei, n_prim, keep);   // (a plus site below the floor keeps no product)
 		}
 	}
 	if(!EMIT) count[k] = c;
@@ -240,37 +211,18 @@ int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, c
 	std::vector<PoolOligo> ol;
 	std::vector<SiteOligoX> olx;
 	const float thr2 = threshold*threshold;                                      // pcr_assay.cpp:775-776
-	// one oligo of either kind -> its table entry; false: g_err says why it is refused
-	auto add_oligo = [&](const pcr_word128 &wd, float conc, const char *what) -> bool {
-		OligoDev d; fill_oligo(d, wd.w, thr2);
-		const uint32_t occ = pcrhost::planes_occupied(d.m);
-		if(!occ || __builtin_popcount(occ) != d.stop - d.start + 1){
-			g_err = std::string("pcr_pool_probe_hits: a ") + what + " is empty or has a hole between its ends (NucCruc::set_query throws)"; return false;
-		}
-		const double degen = pcrhost::planes_degeneracy(d.m);
-		if(degen > (double)PCR_SITE_MAX_EXPANSIONS){ g_err = std::string("pcr_pool_probe_hits: a ") + what + " has more than PCR_SITE_MAX_EXPANSIONS expansions"; return false; }
-		PoolOligo p; p.m = d.m; p.floor2 = d.floor2; p.start = d.start; p.stop = d.stop; p.pad = 0;
-		const float ca = (float)(conc/degen), cb = template_strand;
-		const float strand = (ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca;              // nuc_cruc.h:832-837
-		if(!(strand > 0.0f)){ g_err = std::string("pcr_pool_probe_hits: the strand concentration of a ") + what + "'s duplex is zero (its concentration / degeneracy and template_strand both 0)"; return false; }
-		SiteOligoX x; x.n_exp = (uint32_t)degen;
-		x.log_strand = logf(strand);
-		ol.push_back(p); olx.push_back(x);
-		return true;
-	};
-	std::map<std::pair<uint64_t, uint64_t>, uint32_t> id_of, probe_of;
-	for(uint32_t s = 0;s < 2*n_pool;++s){
-		const pcr_word128 &wd = (s & 1) ? pool[s/2].r : pool[s/2].f;
-		auto ins = id_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)id_of.size()));
-		if(ins.second && !add_oligo(wd, args->primer_strand, "primer")) return PCR_ERR_ARG;
-		oligo_id[s] = ins.first->second;
-	}
+	if(site_oligo_table("pcr_pool_probe_hits", "a primer", "its concentration", pool, n_pool, threshold, args, template_strand, oligo_id, ol, olx) != PCR_OK) return PCR_ERR_ARG;
 	const uint32_t n_prim = (uint32_t)ol.size();
+	std::map<std::pair<uint64_t, uint64_t>, uint32_t> probe_of;
 	for(uint32_t i = 0;i < n_pool;++i){
 		const pcr_word128 &wd = probes[i];
 		if(!wd.w[0] && !wd.w[1]){ probe_id[i] = PCR_NO_PROBE; continue; }
 		auto ins = probe_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)probe_of.size()));
-		if(ins.second && !add_oligo(wd, probe_strand_conc, "probe")) return PCR_ERR_ARG;
+		if(ins.second){
+			PoolOligo p; SiteOligoX x;
+			if(!site_oligo("pcr_pool_probe_hits", "a probe", wd, thr2, true, probe_strand_conc, "its concentration", template_strand, p, x)) return PCR_ERR_ARG;
+			ol.push_back(p); olx.push_back(x);
+		}
 		probe_id[i] = ins.first->second;
 	}
 	if(ol.size() > POOL_MAX_OLIGOS){ g_err = "pcr_pool_probe_hits: too many distinct oligos (primers plus probes over 2*PCR_POOL_MAX_PAIRS)"; return PCR_ERR_ARG; }
@@ -311,71 +263,27 @@ int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, c
 	memcpy(blob.data() + ol_bytes, tab.data(), tab_bytes);
 	memcpy(blob.data() + ol_bytes + tab_bytes, olx.data(), olx_bytes);
 	memcpy(blob.data() + ol_bytes + tab_bytes + olx_bytes, intended.data(), int_bytes);
-	if((rc = ctx->pph_in.ensure(blob.size())) != PCR_OK) return rc;
-	const PoolOligo *d_ol = (const PoolOligo *)ctx->pph_in.p;
-	const ProbeAssay *d_tab = (const ProbeAssay *)(ctx->pph_in.p + ol_bytes);
-	const SiteOligoX *d_olx = (const SiteOligoX *)(ctx->pph_in.p + ol_bytes + tab_bytes);
-	const uint32_t *d_intended = (const uint32_t *)(ctx->pph_in.p + ol_bytes + tab_bytes + olx_bytes);
+	ItemScratch &X = ctx->shared;
+	const ItemBufs B = X.bufs();
+	if((rc = X.in.ensure(blob.size())) != PCR_OK) return rc;
+	const PoolOligo *d_ol = (const PoolOligo *)X.in.p;
+	const ProbeAssay *d_tab = (const ProbeAssay *)(X.in.p + ol_bytes);
+	const SiteOligoX *d_olx = (const SiteOligoX *)(X.in.p + ol_bytes + tab_bytes);
+	const uint32_t *d_intended = (const uint32_t *)(X.in.p + ol_bytes + tab_bytes + olx_bytes);
 	const uint32_t n_tab = (uint32_t)tab.size();
-	HIP_TRY(hipMemcpyAsync(ctx->pph_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
-	// ---- 1. the items (k_pool_entry_oligos: count, scan, fill)
-	const uint32_t n_db = S.n_touched*S.db_cap;
-	if((rc = ctx->pph_cnt.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
-	if((rc = ctx->pph_eoff.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->pph_cnt.p + n_db, 0, sizeof(uint32_t), ctx->stream));
-	size_t tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pph_cnt.p, ctx->pph_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	if((rc = ctx->pph_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-	const unsigned grid_e = std::min<unsigned>((n_db + POOL_THREADS - 1)/POOL_THREADS, ctx->n_cu*8);
-	hipLaunchKernelGGL(k_pool_entry_oligos<false>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
-		S.d_seg_hi, S.d_active.p, d_ol, n_ol, ctx->pph_cnt.p, (const uint64_t *)nullptr, (uint2 *)nullptr);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(rocprim::exclusive_scan(ctx->pph_tmp.p, tmp, ctx->pph_cnt.p, ctx->pph_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	HIP_TRY(hipMemcpyAsync(X.in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+	// ---- 1. the items (item_count waits: blob is read by then)
 	uint64_t n_items = 0;
-	HIP_TRY(hipMemcpyAsync(&n_items, ctx->pph_eoff.p + n_db, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));                                   // (blob is read by now)
+	if((rc = item_count(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
 	if(n_items >= POOL_MAX_ITEMS){ g_err = "pcr_pool_probe_hits: too many (entry, oligo) hits"; return PCR_ERR_CAPACITY; }
 	if(n_items == 0){ zero_rows(); return 0; }
-	if((rc = ctx->pph_items.ensure(n_items)) != PCR_OK) return rc;
-	hipLaunchKernelGGL(k_pool_entry_oligos<true>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
-		S.d_seg_hi, S.d_active.p, d_ol, n_ol, (uint32_t *)nullptr, (const uint64_t *)ctx->pph_eoff.p, ctx->pph_items.p);
-	HIP_TRY(hipGetLastError());
+	if((rc = item_fill(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
 	const uint32_t ni = (uint32_t)n_items;
 	const unsigned grid_i = (ni + POOL_THREADS - 1)/POOL_THREADS;
-	if((rc = ctx->pph_cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;         // (the entry counts are spent)
-	if((rc = ctx->pph_flag.ensure(1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->pph_flag.p, 0, sizeof(uint32_t), ctx->stream));
-	// ---- 2. job offsets, the jobs (k_site_jobs, k_site_tm as they stand)
-	if((rc = ctx->pph_joff.ensure((size_t)ni + 1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->pph_cnt.p + ni, 0, sizeof(uint32_t), ctx->stream));
-	hipLaunchKernelGGL(k_site_jobs, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint2 *)ctx->pph_items.p, ni, d_olx, ctx->pph_cnt.p);
-	HIP_TRY(hipGetLastError());
-	tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pph_cnt.p, ctx->pph_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	if((rc = ctx->pph_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-	HIP_TRY(rocprim::exclusive_scan(ctx->pph_tmp.p, tmp, ctx->pph_cnt.p, ctx->pph_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	uint64_t n_jobs64 = 0;
-	HIP_TRY(hipMemcpyAsync(&n_jobs64, ctx->pph_joff.p + ni, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));
-	if(n_jobs64 >= POOL_MAX_ITEMS){ g_err = "pcr_pool_probe_hits: too many (site, expansion) jobs"; return PCR_ERR_CAPACITY; }
-	const uint32_t n_jobs = (uint32_t)n_jobs64;
-	if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
-	if(!ctx->site_attr_set){                                                       // (k_site_tm's own flag: the attribute is the kernel's)
-		HIP_TRY(hipFuncSetAttribute((const void *)k_site_tm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SITE_LDS));
-		ctx->site_attr_set = true;
-	}
-	if((rc = ctx->pph_res.ensure(n_jobs)) != PCR_OK) return rc;
-	if((rc = ctx->pph_item_tm.ensure(ni)) != PCR_OK) return rc;
-	// at most one block per CU (a block takes most of a CU's LDS), the waves striding over the jobs
-	const unsigned grid_j = std::max(1u, std::min<unsigned>((n_jobs + SITE_WAVES - 1)/SITE_WAVES, (unsigned)ctx->n_cu));
-	hipLaunchKernelGGL(k_site_tm, dim3(grid_j), dim3(SITE_THREADS), SITE_LDS, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
-		(const uint2 *)ctx->pph_items.p, ni, (const uint64_t *)ctx->pph_joff.p, n_jobs, d_ol, d_olx, (const int *)ctx->th_dg.p, logf(args->salt), ctx->pph_res.p);
-	HIP_TRY(hipGetLastError());
-	// ---- 3. Tm per item
-	hipLaunchKernelGGL(k_item_tm, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint64_t *)ctx->pph_joff.p, ni,
-		(const float4 *)ctx->pph_res.p, (ItemTm *)ctx->pph_item_tm.p, ctx->pph_flag.p);
-	HIP_TRY(hipGetLastError());
-	const ItemTm *d_item_tm = (const ItemTm *)ctx->pph_item_tm.p;                 // (the handle keeps it as uint2: the struct is pcr_products_tm.inc's)
+	if((rc = X.cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;                // (the entry counts are spent)
+	// ---- 2. job offsets, the jobs; 3. Tm per item
+	if((rc = melt_items("pcr_pool_probe_hits", ctx, S, d_ol, d_olx, ni, args->salt, B)) != PCR_OK) return rc;
+	const ItemTm *d_item_tm = (const ItemTm *)X.item_tm.p;
 	// ---- 4. the kept products: count (and the rows of the pairs without a probe), scan, compact
 	unsigned long long *d_bits = nullptr;
 	if(detected){
@@ -383,50 +291,41 @@ int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, c
 		HIP_TRY(hipMemsetAsync(ctx->pph_bits.p, 0, row_words*sizeof(uint64_t), ctx->stream));
 		d_bits = (unsigned long long *)ctx->pph_bits.p;
 	}
-	if((rc = ctx->pph_ioff.ensure((size_t)ni + 1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->pph_cnt.p + ni, 0, sizeof(uint32_t), ctx->stream));
-	hipLaunchKernelGGL(k_probe_products<false>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
-		ctx->pph_items.p, ni, (const uint64_t *)ctx->pph_eoff.p, d_ol, n_ol, n_prim, S.planes.p, S.d_blk_off.p, S.d_len.p, S.d_has_eos.p,
-		amp_min, amp_max, d_item_tm, tm_floor, d_intended, d_tab, n_tab, d_bits, words,
-		ctx->pph_cnt.p, (const uint64_t *)nullptr, (uint4 *)nullptr);
+	const JoinIn J{S.db.p, S.db_cap, S.touched.p, S.d_seg_hi, X.items.p, ni, X.eoff.p, d_ol, n_ol, S.planes.p, S.d_blk_off.p, S.d_len.p,
+		S.d_has_eos.p, amp_min, amp_max};
+	hipLaunchKernelGGL(k_probe_products<false>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, n_prim, d_item_tm, tm_floor, d_intended, d_tab, n_tab,
+		d_bits, words, X.cnt.p, (const uint64_t *)nullptr, (uint4 *)nullptr);
 	HIP_TRY(hipGetLastError());
-	tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pph_cnt.p, ctx->pph_ioff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	if((rc = ctx->pph_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-	HIP_TRY(rocprim::exclusive_scan(ctx->pph_tmp.p, tmp, ctx->pph_cnt.p, ctx->pph_ioff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
 	uint64_t n_prod64 = 0;
-	HIP_TRY(hipMemcpyAsync(&n_prod64, ctx->pph_ioff.p + ni, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if((rc = scan_total(ctx, X.cnt.p, X.ioff, X.tmp, ni, n_prod64)) != PCR_OK) return rc;
 	if(n_prod64 >= POOL_MAX_ITEMS){ g_err = "pcr_pool_probe_hits: too many products"; return PCR_ERR_CAPACITY; }
 	const uint32_t np = (uint32_t)n_prod64;
 	uint64_t total = 0;
 	unsigned grid_p = 0;
 	if(np){
 		if((rc = ctx->pph_prod.ensure(np)) != PCR_OK) return rc;
-		hipLaunchKernelGGL(k_probe_products<true>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
-			ctx->pph_items.p, ni, (const uint64_t *)ctx->pph_eoff.p, d_ol, n_ol, n_prim, S.planes.p, S.d_blk_off.p, S.d_len.p, S.d_has_eos.p,
-			amp_min, amp_max, d_item_tm, tm_floor, d_intended, d_tab, n_tab, (unsigned long long *)nullptr, words,
-			(uint32_t *)nullptr, (const uint64_t *)ctx->pph_ioff.p, ctx->pph_prod.p);
+		hipLaunchKernelGGL(k_probe_products<true>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, n_prim, d_item_tm, tm_floor, d_intended, d_tab, n_tab,
+			(unsigned long long *)nullptr, words, (uint32_t *)nullptr, (const uint64_t *)X.ioff.p, ctx->pph_prod.p);
 		HIP_TRY(hipGetLastError());
 		// ---- 5. the hits: a wave per product; count (and the rows of the pairs with a probe), scan
 		if((rc = ctx->pph_hcnt.ensure((size_t)np + 1)) != PCR_OK) return rc;
-		if((rc = ctx->pph_hoff.ensure((size_t)np + 1)) != PCR_OK) return rc;
-		HIP_TRY(hipMemsetAsync(ctx->pph_hcnt.p + np, 0, sizeof(uint32_t), ctx->stream));
 		grid_p = std::min<unsigned>((np + PPH_WAVES - 1)/PPH_WAVES, ctx->n_cu*8);
 		hipLaunchKernelGGL(k_probe_hits<false>, dim3(grid_p), dim3(64*PPH_WAVES), 0, ctx->stream, S.db.p, S.db_cap, S.d_seg_hi,
-			(const uint2 *)ctx->pph_items.p, (const uint64_t *)ctx->pph_eoff.p, d_ol, n_ol, n_prim, (const uint4 *)ctx->pph_prod.p, np, d_item_tm, probe_tm_floor,
+			(const uint2 *)X.items.p, (const uint64_t *)X.eoff.p, d_ol, n_ol, n_prim, (const uint4 *)ctx->pph_prod.p, np, d_item_tm, probe_tm_floor,
 			d_intended, d_tab, n_tab, d_bits, words, ctx->pph_hcnt.p, (const uint64_t *)nullptr, (pcr_probe_hit *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr);
 		HIP_TRY(hipGetLastError());
-		tmp = 0;
-		HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->pph_hcnt.p, ctx->pph_hoff.p, uint64_t(0), (size_t)np + 1, rocprim::plus<uint64_t>(), ctx->stream));
-		if((rc = ctx->pph_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-		HIP_TRY(rocprim::exclusive_scan(ctx->pph_tmp.p, tmp, ctx->pph_hcnt.p, ctx->pph_hoff.p, uint64_t(0), (size_t)np + 1, rocprim::plus<uint64_t>(), ctx->stream));
-		HIP_TRY(hipMemcpyAsync(&total, ctx->pph_hoff.p + np, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
 	}
 	uint32_t bad = 0;
-	HIP_TRY(hipMemcpyAsync(&bad, ctx->pph_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-	if(detected) HIP_TRY(hipMemcpyAsync(detected, ctx->pph_bits.p, row_words*sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	auto flag_and_rows = [&]() -> int {
+		HIP_TRY(hipMemcpyAsync(&bad, X.flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		if(detected) HIP_TRY(hipMemcpyAsync(detected, ctx->pph_bits.p, row_words*sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+		return PCR_OK;
+	};
+	if(np){ if((rc = scan_total(ctx, ctx->pph_hcnt.p, ctx->pph_hoff, X.tmp, np, total, flag_and_rows)) != PCR_OK) return rc; }
+	else{
+		if((rc = flag_and_rows()) != PCR_OK) return rc;
+		HIP_TRY(hipStreamSynchronize(ctx->stream));
+	}
 	if(bad & 1u){ g_err = "pcr_pool_probe_hits: internal trace-back error"; return PCR_ERR_RANGE; }
 	// a pool pair that repeats an earlier assay has that pair's row (the device filled the first copy only)
 	for(uint32_t i = 0;i < n_pool && detected;++i)
@@ -442,7 +341,7 @@ int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, c
 	uint64_t *k0 = ctx->pph_keys.p, *k1 = k0 + nr;
 	uint32_t *o0 = ctx->pph_ord.p, *o1 = o0 + nr;
 	hipLaunchKernelGGL(k_probe_hits<true>, dim3(grid_p), dim3(64*PPH_WAVES), 0, ctx->stream, S.db.p, S.db_cap, S.d_seg_hi,
-		(const uint2 *)ctx->pph_items.p, (const uint64_t *)ctx->pph_eoff.p, d_ol, n_ol, n_prim, (const uint4 *)ctx->pph_prod.p, np, d_item_tm, probe_tm_floor,
+		(const uint2 *)X.items.p, (const uint64_t *)X.eoff.p, d_ol, n_ol, n_prim, (const uint4 *)ctx->pph_prod.p, np, d_item_tm, probe_tm_floor,
 		d_intended, d_tab, n_tab, (unsigned long long *)nullptr, words, (uint32_t *)nullptr, (const uint64_t *)ctx->pph_hoff.p, r0, k0, o0);
 	HIP_TRY(hipGetLastError());
 	const unsigned seq_bits = pool_bits(S.n), oligo_bits = pool_bits(n_prim), probe_bits = pool_bits(n_ol - n_prim);
@@ -450,15 +349,15 @@ int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, c
 	HIP_TRY(rocprim::radix_sort_pairs(nullptr, t0, k0, k1, o0, o1, nr, 0, 33 + probe_bits, ctx->stream));
 	HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, k0, k1, o1, o0, nr, 0, 64, ctx->stream));
 	HIP_TRY(rocprim::radix_sort_pairs(nullptr, t2, k0, k1, o0, o1, nr, 0, 2*oligo_bits + seq_bits, ctx->stream));
-	if((rc = ctx->pph_tmp.ensure(std::max(t0, std::max(t1, t2)) + 16)) != PCR_OK) return rc;
+	if((rc = X.tmp.ensure(std::max(t0, std::max(t1, t2)) + 16)) != PCR_OK) return rc;
 	const unsigned grid_r = (nr + 255)/256;
-	HIP_TRY(rocprim::radix_sort_pairs(ctx->pph_tmp.p, t0, k0, k1, o0, o1, nr, 0, 33 + probe_bits, ctx->stream));
+	HIP_TRY(rocprim::radix_sort_pairs(X.tmp.p, t0, k0, k1, o0, o1, nr, 0, 33 + probe_bits, ctx->stream));
 	hipLaunchKernelGGL(k_probe_key, dim3(grid_r), dim3(256), 0, ctx->stream, (const pcr_probe_hit *)r0, (const uint32_t *)o1, nr, 1, seq_bits, oligo_bits, k0);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(rocprim::radix_sort_pairs(ctx->pph_tmp.p, t1, k0, k1, o1, o0, nr, 0, 64, ctx->stream));                        // (stable)
+	HIP_TRY(rocprim::radix_sort_pairs(X.tmp.p, t1, k0, k1, o1, o0, nr, 0, 64, ctx->stream));                        // (stable)
 	hipLaunchKernelGGL(k_probe_key, dim3(grid_r), dim3(256), 0, ctx->stream, (const pcr_probe_hit *)r0, (const uint32_t *)o0, nr, 2, seq_bits, oligo_bits, k0);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(rocprim::radix_sort_pairs(ctx->pph_tmp.p, t2, k0, k1, o0, o1, nr, 0, 2*oligo_bits + seq_bits, ctx->stream));   // (stable)
+	HIP_TRY(rocprim::radix_sort_pairs(X.tmp.p, t2, k0, k1, o0, o1, nr, 0, 2*oligo_bits + seq_bits, ctx->stream));   // (stable)
 	hipLaunchKernelGGL(k_probe_gather, dim3(grid_r), dim3(256), 0, ctx->stream, (const pcr_probe_hit *)r0, (const uint32_t *)o1, nr, r1);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(out, r1, (size_t)nr*sizeof(pcr_probe_hit), hipMemcpyDeviceToHost, ctx->stream));

@@ -1,11 +1,13 @@
-// Per-site duplex Tm (pcr_site_tm; included by pcr_device.hip after pcr_pool.inc, whose item kernel it shares).
+// Per-site duplex Tm (pcr_site_tm; included by pcr_device.hip after pcr_pool.inc, whose item stage it runs).  The melting entry
+// points built on the same items share two things of this file: site_oligo / site_oligo_table, the distinct-oligo table with
+// its refusals, and melt_items, the melt stage (the only place k_site_tm is launched from).
 //
 // For every distinct oligo of a panel and every site of the word DB it matches at threshold^2: where the site is, how many
 // slots match, and NucCruc's heterodimer Tm / dH / dS of the oligo against the template strand it anneals to there -- the
 // definition is written out at pcr_site_tm in include/pcramp_hip.h.  Nothing but the device-resident DB is read:
-//   1. k_pool_entry_oligos<false> / <true> (pcr_pool.inc, as they are) + a scan: the (entry, oligo) items, one per
-//      (oligo, site).  Their number is the record count; a count-only call (or one whose cap is too small) ends here.
-//   2. k_site_jobs + a scan: item k gets n_expansions[oligo] consecutive jobs.
+//   1. item_count / item_fill (pcr_pool.inc): the (entry, oligo) items, one per (oligo, site).  Their number is the record
+//      count; a count-only call (or one whose cap is too small) ends between the two.
+//   2. melt_items: k_site_jobs + a scan, item k gets n_expansions[oligo] consecutive jobs; then
 //   3. k_site_tm: one wave per (item, expansion), grid-strided, THERMO_WAVES independent waves per block around one LDS copy of
 //      the dG table -- k_thermo_wave's shape, because the per-wave slab (thermo::WaveSlab, 11.6 KB) is the Engine's and 12 of
 //      them plus the table are what 160 KB of LDS hold.  The wave finds its item by bisection of the job offsets, picks the
@@ -193,6 +195,114 @@ __global__ __launch_bounds__(SITE_THREADS) void k_site_tm(const DevEntry *__rest
 	}
 }
 
+struct alignas(8) ItemTm { float tm; uint32_t no_tm; };                        // tm_max of the item's site (0 with NO_TM) and its NO_TM bit: one 8-byte load
+
+// Item k: its expansions joff[k] .. joff[k + 1] - 1 in index order; the highest Tm (k_site_reduce's rule for tm_max: strict >,
+// the lowest index wins, no float atomics).  Indexed by item: the join kernels read a product's two Tm as two array reads.
+__global__ __launch_bounds__(POOL_THREADS) void k_item_tm(const uint64_t *__restrict__ joff, uint32_t n_items, const float4 *__restrict__ res,
+	ItemTm *__restrict__ item_tm, uint32_t *__restrict__ error)
+{
+	const uint32_t k = blockIdx.x*blockDim.x + threadIdx.x;
+	if(k >= n_items) return;
+	const uint64_t j0 = joff[k], j1 = joff[k + 1];
+	float tm = 0.0f;
+	uint32_t st = 0;
+	for(uint64_t j = j0;j < j1;++j){
+		const float4 v = res[j];
+		st |= __float_as_uint(v.w);
+		if(j == j0 || v.x > tm) tm = v.x;
+	}
+	ItemTm r;
+	r.no_tm = (st & SITE_ST_NO_TM) ? 1u : 0u;
+	r.tm = r.no_tm ? 0.0f : tm;
+	if(st & SITE_ST_ERROR) atomicOr(error, 1u);
+	item_tm[k] = r;
+}
+
+// The melt stage over the ni items of B.items: k_site_jobs + a scan -> B.joff; k_site_tm, one wave per (item, expansion) ->
+// B.res[job]; and with B.item_tm, k_item_tm -> item_tm[] (kept as uint2 by the handle: the struct is this file's) after zeroing
+// its error flag B.flag[0], which one call leaves for the next.  B.cnt holds ni + 1 elements.  The jobs are queued, not waited for.
+int melt_items(const std::string &who, pcr_ctx *ctx, const SeqSet &S, const PoolOligo *d_ol, const SiteOligoX *d_olx, uint32_t ni, float salt,
+	const ItemBufs &B)
+{
+	static_assert(sizeof(ItemTm) == sizeof(uint2), "table layout");
+	int rc;
+	const unsigned grid_i = (ni + POOL_THREADS - 1)/POOL_THREADS;
+	if(B.item_tm){                                                               // (first, so that k_site_tm and k_item_tm follow each other on the stream)
+		if((rc = B.flag->ensure(1)) != PCR_OK) return rc;
+		HIP_TRY(hipMemsetAsync(B.flag->p, 0, sizeof(uint32_t), ctx->stream));
+	}
+	hipLaunchKernelGGL(k_site_jobs, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint2 *)B.items->p, ni, d_olx, B.cnt->p);
+	HIP_TRY(hipGetLastError());
+	uint64_t n_jobs64 = 0;
+	if((rc = scan_total(ctx, B.cnt->p, *B.joff, *B.tmp, ni, n_jobs64)) != PCR_OK) return rc;
+	if(n_jobs64 >= POOL_MAX_ITEMS){ g_err = who + ": too many (site, expansion) jobs"; return PCR_ERR_CAPACITY; }
+	const uint32_t n_jobs = (uint32_t)n_jobs64;
+	if((rc = ensure_dg_table(ctx, salt)) != PCR_OK) return rc;
+	if(!ctx->site_attr_set){
+		HIP_TRY(hipFuncSetAttribute((const void *)k_site_tm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SITE_LDS));
+		ctx->site_attr_set = true;
+	}
+	if((rc = B.res->ensure(n_jobs)) != PCR_OK) return rc;
+	// at most one block per CU (a block takes most of a CU's LDS), the waves striding over the jobs
+	const unsigned grid_j = std::max(1u, std::min<unsigned>((n_jobs + SITE_WAVES - 1)/SITE_WAVES, (unsigned)ctx->n_cu));
+	hipLaunchKernelGGL(k_site_tm, dim3(grid_j), dim3(SITE_THREADS), SITE_LDS, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
+		(const uint2 *)B.items->p, ni, (const uint64_t *)B.joff->p, n_jobs, d_ol, d_olx, (const int *)ctx->th_dg.p, logf(salt), B.res->p);
+	HIP_TRY(hipGetLastError());
+	if(!B.item_tm) return PCR_OK;
+	if((rc = B.item_tm->ensure(ni)) != PCR_OK) return rc;
+	hipLaunchKernelGGL(k_item_tm, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint64_t *)B.joff->p, ni, (const float4 *)B.res->p,
+		(ItemTm *)B.item_tm->p, B.flag->p);
+	HIP_TRY(hipGetLastError());
+	return PCR_OK;
+}
+
+// One oligo of a melting entry point -> its table entries, or false with g_err saying why it is refused.  what: "an oligo", "a
+// primer", "a probe"; conc, conc_name: the oligo's strand concentration and what the message calls it.  melt = false (no
+// thermodynamics asked for): no concentration is looked at.
+bool site_oligo(const std::string &who, const char *what, const pcr_word128 &wd, float thr2, bool melt, float conc, const char *conc_name,
+	float template_strand, PoolOligo &p, SiteOligoX &x)
+{
+	OligoDev d; fill_oligo(d, wd.w, thr2);
+	const uint32_t occ = pcrhost::planes_occupied(d.m);
+	if(!occ || __builtin_popcount(occ) != d.stop - d.start + 1){
+		g_err = who + ": " + what + " is empty or has a hole between its ends (NucCruc::set_query throws)"; return false;
+	}
+	const double degen = pcrhost::planes_degeneracy(d.m);
+	if(degen > (double)PCR_SITE_MAX_EXPANSIONS){ g_err = who + ": " + what + " has more than PCR_SITE_MAX_EXPANSIONS expansions"; return false; }
+	p.m = d.m; p.floor2 = d.floor2; p.start = d.start; p.stop = d.stop; p.pad = 0;
+	x.n_exp = (uint32_t)degen; x.log_strand = 0.0f;
+	if(melt){
+		const float ca = (float)(conc/degen), cb = template_strand;
+		const float strand = (ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca;              // nuc_cruc.h:832-837
+		if(!(strand > 0.0f)){
+			g_err = who + ": the strand concentration of " + what + "'s duplex is zero (" + conc_name + " / degeneracy and template_strand both 0)"; return false;
+		}
+		x.log_strand = logf(strand);
+	}
+	return true;
+}
+
+// The distinct oligos of a panel or pool, in order of first appearance (as pcr_pool_products), appended to ol / olx and numbered by
+// their place in ol; oligo_id[s] of every oligo listed before a refusal is written.  args = NULL: no thermodynamics (site_oligo's melt = false).
+int site_oligo_table(const std::string &who, const char *what, const char *conc_name, const pcr_pair *pairs, uint32_t n_pairs, float threshold,
+	const pcr_thermo_args *args, float template_strand, uint32_t *oligo_id, std::vector<PoolOligo> &ol, std::vector<SiteOligoX> &olx)
+{
+	std::map<std::pair<uint64_t, uint64_t>, uint32_t> id_of;
+	const float thr2 = threshold*threshold;                                      // pcr_assay.cpp:775-776
+	for(uint32_t s = 0;s < 2*n_pairs;++s){
+		const pcr_word128 &wd = (s & 1) ? pairs[s/2].r : pairs[s/2].f;
+		auto ins = id_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)ol.size()));
+		if(ins.second){
+			PoolOligo p; SiteOligoX x;
+			if(!site_oligo(who, what, wd, thr2, args != nullptr, args ? args->primer_strand : 0.0f, conc_name, template_strand, p, x)) return PCR_ERR_ARG;
+			ol.push_back(p); olx.push_back(x);
+		}
+		oligo_id[s] = ins.first->second;
+	}
+	return PCR_OK;
+}
+
 // sort keys of the items: (loc5, strand) first, then stably (oligo, sequence)
 __global__ __launch_bounds__(POOL_THREADS) void k_site_key1(const DevEntry *__restrict__ db, uint32_t cap, const uint32_t *__restrict__ touched,
 	const uint2 *__restrict__ items, uint32_t n_items, const PoolOligo *__restrict__ oligos, uint64_t *__restrict__ key, uint32_t *__restrict__ ord)
@@ -265,33 +375,9 @@ int64_t pcr_site_tm(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t
 	if(n_pairs > PCR_POOL_MAX_PAIRS){ g_err = "pcr_site_tm: panel larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
 	if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f)){ g_err = "pcr_site_tm: negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
 	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = "pcr_site_tm: salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
-	// the distinct oligos, in order of first appearance (as pcr_pool_products)
 	std::vector<PoolOligo> ol;
 	std::vector<SiteOligoX> olx;
-	std::map<std::pair<uint64_t, uint64_t>, uint32_t> id_of;
-	const float thr2 = threshold*threshold;                                      // pcr_assay.cpp:775-776
-	for(uint32_t s = 0;s < 2*n_pairs;++s){
-		const pcr_word128 &wd = (s & 1) ? pairs[s/2].r : pairs[s/2].f;
-		auto ins = id_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)ol.size()));
-		if(ins.second){
-			OligoDev d; fill_oligo(d, wd.w, thr2);
-			const uint32_t occ = pcrhost::planes_occupied(d.m);
-			if(!occ || __builtin_popcount(occ) != d.stop - d.start + 1){
-				g_err = "pcr_site_tm: an oligo is empty or has a hole between its ends (NucCruc::set_query throws)"; return PCR_ERR_ARG;
-			}
-			const double degen = pcrhost::planes_degeneracy(d.m);
-			if(degen > (double)PCR_SITE_MAX_EXPANSIONS){ g_err = "pcr_site_tm: an oligo has more than PCR_SITE_MAX_EXPANSIONS expansions"; return PCR_ERR_ARG; }
-			PoolOligo p; p.m = d.m; p.floor2 = d.floor2; p.start = d.start; p.stop = d.stop; p.pad = 0;
-			ol.push_back(p);
-			const float ca = (float)(args->primer_strand/degen), cb = template_strand;
-			const float strand = (ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca;          // nuc_cruc.h:832-837
-			if(!(strand > 0.0f)){ g_err = "pcr_site_tm: the strand concentration of an oligo's duplex is zero (primer_strand / degeneracy and template_strand both 0)"; return PCR_ERR_ARG; }
-			SiteOligoX x; x.n_exp = (uint32_t)degen;
-			x.log_strand = logf(strand);
-			olx.push_back(x);
-		}
-		oligo_id[s] = ins.first->second;
-	}
+	if(site_oligo_table("pcr_site_tm", "an oligo", "primer_strand", pairs, n_pairs, threshold, args, template_strand, oligo_id, ol, olx) != PCR_OK) return PCR_ERR_ARG;
 	if(!ctx){ g_err = "pcr_site_tm: null handle"; return PCR_ERR_ARG; }
 	{ const int drc = drain(ctx); if(drc != PCR_OK) return drc; }
 	HIP_TRY(hipSetDevice(ctx->device));
@@ -308,59 +394,19 @@ int64_t pcr_site_tm(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t
 	const SiteOligoX *d_olx = (const SiteOligoX *)(ctx->site_in.p + ol_bytes);
 	HIP_TRY(hipMemcpyAsync(ctx->site_in.p, ol.data(), ol_bytes, hipMemcpyHostToDevice, ctx->stream));
 	HIP_TRY(hipMemcpyAsync(ctx->site_in.p + ol_bytes, olx.data(), olx_bytes, hipMemcpyHostToDevice, ctx->stream));
-	// ---- 1. the items (k_pool_entry_oligos: count, scan, fill)
-	const uint32_t n_db = S.n_touched*S.db_cap;
-	if((rc = ctx->site_cnt.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
-	if((rc = ctx->site_eoff.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->site_cnt.p + n_db, 0, sizeof(uint32_t), ctx->stream));
-	size_t tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->site_cnt.p, ctx->site_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	if((rc = ctx->site_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-	const unsigned grid_e = std::min<unsigned>((n_db + POOL_THREADS - 1)/POOL_THREADS, ctx->n_cu*8);
-	hipLaunchKernelGGL(k_pool_entry_oligos<false>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
-		S.d_seg_hi, S.d_active.p, d_ol, n_ol, ctx->site_cnt.p, (const uint64_t *)nullptr, (uint2 *)nullptr);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(rocprim::exclusive_scan(ctx->site_tmp.p, tmp, ctx->site_cnt.p, ctx->site_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	// ---- 1. the items; 2. job offsets; 3. the jobs
+	const ItemBufs B{&ctx->site_tmp, &ctx->site_cnt, &ctx->site_eoff, &ctx->site_items, &ctx->site_joff, &ctx->site_res};   // (k_site_reduce, not k_item_tm, reads the jobs)
 	uint64_t n_items = 0;
-	HIP_TRY(hipMemcpyAsync(&n_items, ctx->site_eoff.p + n_db, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if((rc = item_count(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
 	if(n_items >= POOL_MAX_ITEMS){ g_err = "pcr_site_tm: too many sites"; return PCR_ERR_CAPACITY; }
 	if(n_items == 0 || n_items > cap) return (int64_t)n_items;                   // count only: out is left as it is
-	if((rc = ctx->site_items.ensure(n_items)) != PCR_OK) return rc;
-	hipLaunchKernelGGL(k_pool_entry_oligos<true>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
-		S.d_seg_hi, S.d_active.p, d_ol, n_ol, (uint32_t *)nullptr, (const uint64_t *)ctx->site_eoff.p, ctx->site_items.p);
-	HIP_TRY(hipGetLastError());
-	// ---- 2. job offsets
+	if((rc = item_fill(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
 	const uint32_t ni = (uint32_t)n_items;
 	const unsigned grid_i = (ni + POOL_THREADS - 1)/POOL_THREADS;
 	if((rc = ctx->site_cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;        // (the entry counts are spent)
-	if((rc = ctx->site_joff.ensure((size_t)ni + 1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->site_cnt.p + ni, 0, sizeof(uint32_t), ctx->stream));
-	hipLaunchKernelGGL(k_site_jobs, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, (const uint2 *)ctx->site_items.p, ni, d_olx, ctx->site_cnt.p);
-	HIP_TRY(hipGetLastError());
-	tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->site_cnt.p, ctx->site_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	if((rc = ctx->site_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-	HIP_TRY(rocprim::exclusive_scan(ctx->site_tmp.p, tmp, ctx->site_cnt.p, ctx->site_joff.p, uint64_t(0), (size_t)ni + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	uint64_t n_jobs64 = 0;
-	HIP_TRY(hipMemcpyAsync(&n_jobs64, ctx->site_joff.p + ni, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));
-	if(n_jobs64 >= POOL_MAX_ITEMS){ g_err = "pcr_site_tm: too many (site, expansion) jobs"; return PCR_ERR_CAPACITY; }
-	const uint32_t n_jobs = (uint32_t)n_jobs64;
-	// ---- 3. the jobs
-	if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
-	if(!ctx->site_attr_set){
-		HIP_TRY(hipFuncSetAttribute((const void *)k_site_tm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SITE_LDS));
-		ctx->site_attr_set = true;
-	}
-	if((rc = ctx->site_res.ensure(n_jobs)) != PCR_OK) return rc;
+	if((rc = melt_items("pcr_site_tm", ctx, S, d_ol, d_olx, ni, args->salt, B)) != PCR_OK) return rc;
 	if((rc = ctx->site_flag.ensure(1)) != PCR_OK) return rc;
 	HIP_TRY(hipMemsetAsync(ctx->site_flag.p, 0, sizeof(uint32_t), ctx->stream));
-	// at most one block per CU (a block takes most of a CU's LDS), the waves striding over the jobs
-	const unsigned grid_j = std::max(1u, std::min<unsigned>((n_jobs + SITE_WAVES - 1)/SITE_WAVES, (unsigned)ctx->n_cu));
-	hipLaunchKernelGGL(k_site_tm, dim3(grid_j), dim3(SITE_THREADS), SITE_LDS, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
-		(const uint2 *)ctx->site_items.p, ni, (const uint64_t *)ctx->site_joff.p, n_jobs, d_ol, d_olx, (const int *)ctx->th_dg.p, logf(args->salt), ctx->site_res.p);
-	HIP_TRY(hipGetLastError());
 	// ---- 4. the record order, the records
 	if((rc = ctx->site_keys.ensure(2*(size_t)ni)) != PCR_OK) return rc;
 	if((rc = ctx->site_ord.ensure(2*(size_t)ni)) != PCR_OK) return rc;

@@ -221,7 +221,7 @@ struct SvRun {
 };
 
 // The arguments every caller of the pipeline refuses before the handle (pcr_site_tm's, in its order; args may be NULL), and the
-// distinct oligos, in order of first appearance (as pcr_pool_products).  bad_out: the caller's own "cap without a buffer".
+// distinct oligos (site_oligo_table, pcr_site_tm.inc).  bad_out: the caller's own "cap without a buffer".
 int sv_check(const char *who, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs, float threshold, const pcr_thermo_args *args,
 	float template_strand, uint32_t *oligo_id, bool bad_out, std::vector<PoolOligo> &ol, std::vector<SiteOligoX> &olx)
 {
@@ -234,34 +234,7 @@ int sv_check(const char *who, pcr_set which, const pcr_pair *pairs, uint32_t n_p
 		if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f)){ g_err = w + ": negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
 		if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = w + ": salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
 	}
-	// the distinct oligos, in order of first appearance (as pcr_pool_products)
-	std::map<std::pair<uint64_t, uint64_t>, uint32_t> id_of;
-	const float thr2 = threshold*threshold;                                      // pcr_assay.cpp:775-776
-	for(uint32_t s = 0;s < 2*n_pairs;++s){
-		const pcr_word128 &wd = (s & 1) ? pairs[s/2].r : pairs[s/2].f;
-		auto ins = id_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)ol.size()));
-		if(ins.second){
-			OligoDev d; fill_oligo(d, wd.w, thr2);
-			const uint32_t occ = pcrhost::planes_occupied(d.m);
-			if(!occ || __builtin_popcount(occ) != d.stop - d.start + 1){
-				g_err = w + ": an oligo is empty or has a hole between its ends (NucCruc::set_query throws)"; return PCR_ERR_ARG;
-			}
-			const double degen = pcrhost::planes_degeneracy(d.m);
-			if(degen > (double)PCR_SITE_MAX_EXPANSIONS){ g_err = w + ": an oligo has more than PCR_SITE_MAX_EXPANSIONS expansions"; return PCR_ERR_ARG; }
-			PoolOligo p; p.m = d.m; p.floor2 = d.floor2; p.start = d.start; p.stop = d.stop; p.pad = 0;
-			ol.push_back(p);
-			SiteOligoX x; x.n_exp = (uint32_t)degen; x.log_strand = 0.0f;
-			if(args){
-				const float ca = (float)(args->primer_strand/degen), cb = template_strand;
-				const float strand = (ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca;      // nuc_cruc.h:832-837
-				if(!(strand > 0.0f)){ g_err = w + ": the strand concentration of an oligo's duplex is zero (primer_strand / degeneracy and template_strand both 0)"; return PCR_ERR_ARG; }
-				x.log_strand = logf(strand);
-			}
-			olx.push_back(x);
-		}
-		oligo_id[s] = ins.first->second;
-	}
-	return PCR_OK;
+	return site_oligo_table(w, "an oligo", "primer_strand", pairs, n_pairs, threshold, args, template_strand, oligo_id, ol, olx);
 }
 
 // Steps 1 to 7 on a checked panel -> the number of variants or a negative error; `run` says what is where.  A count above cap
@@ -287,29 +260,14 @@ int64_t sv_run(const char *who, pcr_ctx *ctx, pcr_set which, uint32_t n_pairs, c
 	const SiteOligoX *d_olx = (const SiteOligoX *)(ctx->site_in.p + ol_bytes);
 	HIP_TRY(hipMemcpyAsync(ctx->site_in.p, ol.data(), ol_bytes, hipMemcpyHostToDevice, ctx->stream));
 	HIP_TRY(hipMemcpyAsync(ctx->site_in.p + ol_bytes, olx.data(), olx_bytes, hipMemcpyHostToDevice, ctx->stream));
-	// ---- 1. the items (k_pool_entry_oligos: count, scan, fill)
-	const uint32_t n_db = S.n_touched*S.db_cap;
-	if((rc = ctx->site_cnt.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
-	if((rc = ctx->site_eoff.ensure((size_t)n_db + 1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->site_cnt.p + n_db, 0, sizeof(uint32_t), ctx->stream));
-	size_t tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->site_cnt.p, ctx->site_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
-	if((rc = ctx->site_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-	const unsigned grid_e = std::min<unsigned>((n_db + POOL_THREADS - 1)/POOL_THREADS, ctx->n_cu*8);
-	hipLaunchKernelGGL(k_pool_entry_oligos<false>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
-		S.d_seg_hi, S.d_active.p, d_ol, n_ol, ctx->site_cnt.p, (const uint64_t *)nullptr, (uint2 *)nullptr);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(rocprim::exclusive_scan(ctx->site_tmp.p, tmp, ctx->site_cnt.p, ctx->site_eoff.p, uint64_t(0), (size_t)n_db + 1, rocprim::plus<uint64_t>(), ctx->stream));
+	// ---- 1. the items (item_count, item_fill)
+	const ItemBufs B{&ctx->site_tmp, &ctx->site_cnt, &ctx->site_eoff, &ctx->site_items};
 	uint64_t n_items = 0;
-	HIP_TRY(hipMemcpyAsync(&n_items, ctx->site_eoff.p + n_db, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if((rc = item_count(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
 	if(n_items >= POOL_MAX_ITEMS){ g_err = w + ": too many sites"; return PCR_ERR_CAPACITY; }
 	if(counts) counts[0] = n_items;
 	if(n_items == 0) return 0;
-	if((rc = ctx->site_items.ensure(n_items)) != PCR_OK) return rc;
-	hipLaunchKernelGGL(k_pool_entry_oligos<true>, dim3(grid_e), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, n_db, S.db_cap, S.touched.p,
-		S.d_seg_hi, S.d_active.p, d_ol, n_ol, (uint32_t *)nullptr, (const uint64_t *)ctx->site_eoff.p, ctx->site_items.p);
-	HIP_TRY(hipGetLastError());
+	if((rc = item_fill(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
 	// ---- 2. what each item spells; 3. the orders
 	const uint32_t ni = (uint32_t)n_items;
 	const unsigned grid_i = (ni + POOL_THREADS - 1)/POOL_THREADS;
@@ -349,7 +307,7 @@ int64_t sv_run(const char *who, pcr_ctx *ctx, pcr_set which, uint32_t n_pairs, c
 	// ---- 4. the variants: heads, their scan, starts
 	hipLaunchKernelGGL(k_sv_heads, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, sv, (const uint32_t *)g0, ni, k0);
 	HIP_TRY(hipGetLastError());
-	tmp = 0;
+	size_t tmp = 0;
 	HIP_TRY(rocprim::inclusive_scan(nullptr, tmp, k0, k1, (size_t)ni, rocprim::plus<uint64_t>(), ctx->stream));
 	if((rc = ctx->site_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
 	HIP_TRY(rocprim::inclusive_scan(ctx->site_tmp.p, tmp, k0, k1, (size_t)ni, rocprim::plus<uint64_t>(), ctx->stream));
@@ -371,7 +329,6 @@ int64_t sv_run(const char *who, pcr_ctx *ctx, pcr_set which, uint32_t n_pairs, c
 	if((rc = ctx->sv_vord.ensure(3*(size_t)nv)) != PCR_OK) return rc;
 	if((rc = ctx->site_cnt.ensure((size_t)nv + 1)) != PCR_OK) return rc;        // (the entry counts are spent)
 	if((rc = ctx->site_flag.ensure(1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->site_cnt.p + nv, 0, sizeof(uint32_t), ctx->stream));
 	HIP_TRY(hipMemsetAsync(ctx->site_flag.p, 0, sizeof(uint32_t), ctx->stream));
 	pcr_site_variant *r0 = ctx->sv_rec.p, *r1 = r0 + nv;
 	uint64_t *vk0 = ctx->sv_vkeys.p, *vk1 = vk0 + nv;
@@ -381,14 +338,8 @@ int64_t sv_run(const char *who, pcr_ctx *ctx, pcr_set which, uint32_t n_pairs, c
 	HIP_TRY(hipGetLastError());
 	// ---- 6. one job per (variant, expansion)
 	if(args){
-		if((rc = ctx->site_joff.ensure((size_t)nv + 1)) != PCR_OK) return rc;
-		tmp = 0;
-		HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, ctx->site_cnt.p, ctx->site_joff.p, uint64_t(0), (size_t)nv + 1, rocprim::plus<uint64_t>(), ctx->stream));
-		if((rc = ctx->site_tmp.ensure(tmp + 16)) != PCR_OK) return rc;
-		HIP_TRY(rocprim::exclusive_scan(ctx->site_tmp.p, tmp, ctx->site_cnt.p, ctx->site_joff.p, uint64_t(0), (size_t)nv + 1, rocprim::plus<uint64_t>(), ctx->stream));
 		uint64_t n_jobs64 = 0;
-		HIP_TRY(hipMemcpyAsync(&n_jobs64, ctx->site_joff.p + nv, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-		HIP_TRY(hipStreamSynchronize(ctx->stream));
+		if((rc = scan_total(ctx, ctx->site_cnt.p, ctx->site_joff, ctx->site_tmp, nv, n_jobs64)) != PCR_OK) return rc;
 		if(n_jobs64 >= POOL_MAX_ITEMS){ g_err = w + ": too many (variant, expansion) jobs"; return PCR_ERR_CAPACITY; }
 		const uint32_t n_jobs = (uint32_t)n_jobs64;
 		if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
