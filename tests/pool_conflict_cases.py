@@ -101,23 +101,25 @@ def best_dimer(cells, tm_of):
 
 
 @functools.lru_cache(None)
-def _dimer_matrix(oracle, pool, rule):
+def _dimer_matrix(oracle, pool, rule, salt=SC.SALT, primer_strand=SC.PRIMER_STRAND):
     P = DC.Pool(oracle, list(pool))
-    cells = DC.expected_cells(oracle, P, rule)
+    cells = DC.expected_cells(oracle, P, rule, salt=salt, primer_strand=primer_strand)
     return P.ids, {(c[0], c[1]): c[6] for c in cells}
 
 
 def expected(oracle, name, tm_floor=0.0, rule=NO_DIMERS, dimer_floor=0.0, pool=None, rec=None, ids=None):
     """-> (oligo_id list, the records as tuples of eleven integers: every field, the floats as their bit patterns)."""
+    cond = SC.conditions_of({})
     if rec is None:
         ids, rec, _, _ = PC.all_products(oracle, name)
         pool = PC.scenario(oracle, name)["panel"]
+        cond = SC.conditions_of(PC.scenario(oracle, name))
     n_pool = len(ids) // 2
     prod = product_cells(ids, rec, tm_floor)
     dimers = rule != NO_DIMERS
     tm = None
     if dimers:
-        d_ids, tm = _dimer_matrix(oracle, tuple(pool), rule)
+        d_ids, tm = _dimer_matrix(oracle, tuple(pool), rule, cond["salt"], cond["primer_strand"])
         assert list(d_ids) == list(ids)
     out = []
     fl = np.float32(dimer_floor)

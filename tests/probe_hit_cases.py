@@ -70,9 +70,10 @@ def _everything(oracle, name):
     entries = db_of(oracle, case)
     amp_min, amp_max = PC.amp_of(case)
     jobs = _JOBS.setdefault(name, set())
-    kw = dict(template_strand=case.get("template_strand", 0.0), active=case.get("active"),
+    cond = SC.conditions_of(case)
+    kw = dict(salt=cond["salt"], template_strand=case.get("template_strand", 0.0), active=case.get("active"),
               seqs=None if case.get("splits") else case["seqs"], jobs=jobs, cache=SC._CACHE)
-    ids, sites, _ = SC.expected_sites(oracle, entries, case["panel"], case["thr"], primer_strand=SC.PRIMER_STRAND, **kw)
+    ids, sites, _ = SC.expected_sites(oracle, entries, case["panel"], case["thr"], primer_strand=cond["primer_strand"], **kw)
     lens = [len(s) for s in case["seqs"]]
     by_rule = case["select"] == "all" and not case.get("splits")
     pi, mi = PC._pairs_of(sites, lens, amp_min, amp_max, by_rule)
@@ -396,6 +397,11 @@ SCENARIO_NAMES = ("edges", "ladder", "cross", "words", "degenerate", "ambiguity"
 _MAKERS = {"edges": edges_case, "offset": offset_case, "ladder": ladder_case, "cross": cross_case, "words": words_case, "degenerate": degenerate_case,
            "ambiguity": ambiguity_case, "words_db": lambda oracle: edges_case(oracle, "words"), "split": split_case}
 _CASES = {}
+
+
+def register(name, case):
+    _CASES[name] = case
+    return name
 
 
 def scenario(oracle, name):

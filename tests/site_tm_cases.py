@@ -75,12 +75,22 @@ def strand_rule(ca, cb):
     return ca - np.float32(0.5) * cb if ca > cb else cb - np.float32(0.5) * ca
 
 
+def melt_cached(oracle, cache, key, salt):
+    """oracle.heterodimer_full of key = (query, target, strand_a, strand_b) at a salt, kept in cache under (salt,) + key."""
+    k = (float(salt),) + key
+    if k not in cache:
+        cache[k] = oracle.heterodimer_full(key[0], key[1], salt, key[2], key[3])
+    return cache[k]
+
+
 def expected_sites(oracle, entries, panel, thr, salt=SALT, primer_strand=PRIMER_STRAND, template_strand=0.0, active=None,
-                   seqs=None, jobs=None, cache=None):
+                   seqs=None, jobs=None, cache=None, tamper=None):
     """-> (oligo_id list, SITE array sorted by (oligo, sequence, loc5, strand), number of (site, expansion) jobs).
     entries: the word DB as sorted (w0, w1, loc, index, strand) tuples.  seqs: the sequence texts, for the second spelling of
     full-window targets (leave None where the sequences were split).  jobs: a set that receives every
-    (query, target, strand_a, strand_b) the thermodynamics were asked for.  cache: {(query, target, a, b): result}."""
+    (query, target, strand_a, strand_b) the thermodynamics were asked for.  cache: {(salt, query, target, a, b): result}.
+    tamper(oligo id, expansions) -> the expansions melted in their place: what a wrong decode of the expansion index would
+    report (tests/test_melt_conditions_host.py asks whether the records could tell)."""
     ids, words = distinct_oligos(panel)
     cache = {} if cache is None else cache
     thr2 = np.float32(thr) * np.float32(thr)
@@ -93,6 +103,8 @@ def expected_sites(oracle, entries, panel, thr, salt=SALT, primer_strand=PRIMER_
         exps = [spell(slots_of(x)) for x in oracle.word_expand(c)]
         degen = oracle.word_degeneracy(c)
         assert len(exps) == int(degen)
+        if tamper is not None:
+            exps = tamper(oid, exps)
         ca = np.float32(float(np.float32(primer_strand)) / degen)
         cb = np.float32(template_strand)
         hit = np.nonzero(word_and_np(c, w0, w1) >= floor_of(c, thr2))[0] if len(entries) else []
@@ -125,11 +137,9 @@ def expected_sites(oracle, entries, panel, thr, salt=SALT, primer_strand=PRIMER_
                 res = []
                 for q in exps:
                     key = (q, target, float(ca), float(cb))
-                    if key not in cache:
-                        cache[key] = oracle.heterodimer_full(q, target, salt, float(ca), float(cb))
+                    res.append(melt_cached(oracle, cache, key, salt))
                     if jobs is not None:
                         jobs.add(key)
-                    res.append(cache[key])
                 tms = [r[0] for r in res]
                 best = max(range(len(res)), key=lambda k: (tms[k], -k))     # the highest Tm, the lowest index on a tie
                 rec["tm_max"], rec["tm_min"] = tms[best], min(tms)
@@ -149,7 +159,8 @@ def as_bits(rec):
 
 # ---------------------------------------------------------------------------------------------------------------- scenarios
 # A scenario: dict(seqs, panel, thr, select ("all": select_sites, "words": select_words at thr squared), and optionally
-# active, splits [(sequence, position)], template_strand).  db_of() gives the word DB the oracle expects for it.
+# active, splits [(sequence, position)], template_strand, salt, primer_strand -- SALT and PRIMER_STRAND where it has none).
+# db_of() gives the word DB the oracle expects for it.
 
 _SUB = {"A": "C", "C": "A", "G": "T", "T": "G"}
 
@@ -189,9 +200,14 @@ def db_of(oracle, case):
 _CACHE = {}
 
 
+def conditions_of(case):
+    """The salt and the primer concentration a scenario is melted at: its own keys, or the defaults."""
+    return dict(salt=case.get("salt", SALT), primer_strand=case.get("primer_strand", PRIMER_STRAND))
+
+
 def expectation(oracle, case, jobs=None, **kw):
     """expected_sites() of a scenario on the DB db_of() gives; the thermodynamic results are shared between calls."""
-    args = dict(template_strand=case.get("template_strand", 0.0), active=case.get("active"),
+    args = dict(conditions_of(case), template_strand=case.get("template_strand", 0.0), active=case.get("active"),
                 seqs=None if case.get("splits") else case["seqs"])
     args.update(kw)
     return expected_sites(oracle, db_of(oracle, case), case["panel"], case["thr"], jobs=jobs, cache=_CACHE, **args)

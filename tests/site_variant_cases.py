@@ -87,11 +87,9 @@ def expected_variants(oracle, entries, panel, thr, salt=SC.SALT, primer_strand=S
             res = []
             for q in exps:
                 k = (q, tgt[0], float(ca), float(cb))
-                if k not in cache:
-                    cache[k] = oracle.heterodimer_full(q, tgt[0], salt, float(ca), float(cb))
+                res.append(SC.melt_cached(oracle, cache, k, salt))
                 if jobs is not None:
                     jobs.add(k)
-                res.append(cache[k])
             tms = [r[0] for r in res]
             best = max(range(len(res)), key=lambda k: (tms[k], -k))     # the highest Tm, the lowest index on a tie
             rec["tm_max"], rec["tm_min"] = tms[best], min(tms)
@@ -107,7 +105,7 @@ def expected_variants(oracle, entries, panel, thr, salt=SC.SALT, primer_strand=S
 
 def expectation(oracle, case, jobs=None, **kw):
     """expected_variants() of a scenario on the DB site_tm_cases.db_of() gives."""
-    args = dict(template_strand=case.get("template_strand", 0.0), active=case.get("active"))
+    args = dict(SC.conditions_of(case), template_strand=case.get("template_strand", 0.0), active=case.get("active"))
     args.update(kw)
     return expected_variants(oracle, SC.db_of(oracle, case), case["panel"], case["thr"], jobs=jobs, **args)
 

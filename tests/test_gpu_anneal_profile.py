@@ -42,8 +42,8 @@ def _load(d, oracle, case, which=api.TARGET):
 
 def _run(d, case, temps, which=api.TARGET, **kw):
     lo, hi = PC.amp_of(case)
-    return d.anneal_profile(case["panel"], temps, case["thr"], salt=SC.SALT, primer_strand=SC.PRIMER_STRAND,
-                            template_strand=case.get("template_strand", 0.0), amp_min=lo, amp_max=hi, which=which, **kw)
+    return d.anneal_profile(case["panel"], temps, case["thr"], template_strand=case.get("template_strand", 0.0), amp_min=lo,
+                            amp_max=hi, which=which, **SC.conditions_of(case), **kw)
 
 
 def _poisoned(n, dtype):
@@ -58,7 +58,8 @@ def _raw(d, case, temps, want=("pair_seq", "fr", "rf", "spur"), which=api.TARGET
     n_pool, n_seq, n_t = len(case["panel"]), len(case["seqs"]), len(temps)
     a = W.pairs_array(case["panel"])
     t = np.ascontiguousarray(temps, np.float32)
-    args = api.ThermoArgs(SC.SALT, SC.PRIMER_STRAND, 0.0, 0.0, 0.0, 0.0)
+    cond = SC.conditions_of(case)
+    args = api.ThermoArgs(cond["salt"], cond["primer_strand"], 0.0, 0.0, 0.0, 0.0)
     lo, hi = PC.amp_of(case)
     size = dict(ids=(2 * n_pool, np.uint32), points=(n_t, api.ANNEAL_POINT_DTYPE), pair_seq=(n_pool * n_t, np.uint32),
                 fr=(n_pool * n_seq, np.float32), rf=(n_pool * n_seq, np.float32), spur=(n_seq, np.float32))

@@ -49,7 +49,8 @@ def _raw(d, case, tm_floor=0.0, rule=CC.NO_DIMERS, dimer_floor=0.0, cap=None, wh
     panel = case["panel"] if panel is None else panel
     n_pool = len(panel)
     a = W.pairs_array(panel)
-    args = api.ThermoArgs(SC.SALT, SC.PRIMER_STRAND, 0.0, 0.0, 0.0, 0.0)
+    cond = SC.conditions_of(case)
+    args = api.ThermoArgs(cond["salt"], cond["primer_strand"], 0.0, 0.0, 0.0, 0.0)
     lo, hi = PC.amp_of(case)
     if cap is None:
         cap = n_pool * (n_pool + 1) // 2

@@ -49,7 +49,7 @@ def _load(d, oracle, case, which=api.TARGET):
 
 def _kw(case):
     lo, hi = PC.amp_of(case)
-    return dict(salt=SC.SALT, primer_strand=SC.PRIMER_STRAND, probe_strand=case.get("probe_strand", H.PROBE_STRAND),
+    return dict(SC.conditions_of(case), probe_strand=case.get("probe_strand", H.PROBE_STRAND),
                 template_strand=case.get("template_strand", 0.0), amp_min=lo, amp_max=hi)
 
 

@@ -39,8 +39,8 @@ def _load(d, oracle, case, which=api.TARGET):
 
 def _run(d, case, tm_floor=0.0, which=api.TARGET, **kw):
     lo, hi = PC.amp_of(case)
-    return d.pool_products_tm(case["panel"], case["thr"], tm_floor=tm_floor, salt=SC.SALT, primer_strand=SC.PRIMER_STRAND,
-                              template_strand=case.get("template_strand", 0.0), amp_min=lo, amp_max=hi, which=which, **kw)
+    return d.pool_products_tm(case["panel"], case["thr"], tm_floor=tm_floor, template_strand=case.get("template_strand", 0.0),
+                              amp_min=lo, amp_max=hi, which=which, **SC.conditions_of(case), **kw)
 
 
 def _equal(got, want):
@@ -64,7 +64,8 @@ def _compare(d, oracle, name, tm_floor=0.0, which=api.TARGET):
 def _raw(d, case, tm_floor, out, cap, fr, rf, which=api.TARGET):
     a = W.pairs_array(case["panel"])
     ids = np.zeros(2 * len(case["panel"]), np.uint32)
-    args = api.ThermoArgs(SC.SALT, SC.PRIMER_STRAND, 0.0, 0.0, 0.0, 0.0)
+    cond = SC.conditions_of(case)
+    args = api.ThermoArgs(cond["salt"], cond["primer_strand"], 0.0, 0.0, 0.0, 0.0)
     lo, hi = PC.amp_of(case)
     ptr = lambda x: None if x is None else x.ctypes.data
     return d.L.pcr_pool_products_tm(d.h, which, a.ctypes.data, len(case["panel"]), float(case["thr"]), lo, hi, C.byref(args),

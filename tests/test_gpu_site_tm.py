@@ -36,8 +36,7 @@ def _load(d, oracle, case):
 
 
 def _melt(d, case, **kw):
-    return d.site_tm(case["panel"], case["thr"], salt=SC.SALT, primer_strand=SC.PRIMER_STRAND,
-                     template_strand=case.get("template_strand", 0.0), **kw)
+    return d.site_tm(case["panel"], case["thr"], template_strand=case.get("template_strand", 0.0), **SC.conditions_of(case), **kw)
 
 
 def _check(d, oracle, case):

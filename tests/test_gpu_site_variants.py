@@ -38,14 +38,15 @@ def _load(d, oracle, case):
 
 
 def _kw(case):
-    return dict(salt=SC.SALT, primer_strand=SC.PRIMER_STRAND, template_strand=case.get("template_strand", 0.0))
+    return dict(SC.conditions_of(case), template_strand=case.get("template_strand", 0.0))
 
 
 def _raw(d, case, cap, site_cap, thermo=True):
     """The C call itself -> (return value, ids, records, site map, counts)."""
     a = W.pairs_array(case["panel"])
     ids = np.zeros(max(2 * len(case["panel"]), 1), np.uint32)
-    args = api.ThermoArgs(SC.SALT, SC.PRIMER_STRAND, 0.0, 0.0, 0.0, 0.0)
+    cond = SC.conditions_of(case)
+    args = api.ThermoArgs(cond["salt"], cond["primer_strand"], 0.0, 0.0, 0.0, 0.0)
     out = np.zeros(max(cap, 1), api.SITE_VARIANT_DTYPE)
     smap = np.full(max(site_cap, 1), 0xFFFFFFFF, np.uint32)
     counts = np.full(2, 99, np.uint64)

@@ -116,6 +116,12 @@ def test_expansion_order_is_word_begin_next(oracle):
     exps = [SC.spell(SC.slots_of(x)) for x in oracle.word_expand(w)]
     assert len(exps) == 16 and len(set(exps)) == 16
     assert exps[0] == "ACATAGCA" and exps[-1] == "ACGTTGTA"
+    # three-fold codes: the centred 8-mer lies in slots 12 .. 19, so B (slot 14) turns fastest, then H (slot 18), then R (slot 16)
+    w = oracle.centered_word("ACBTRGHA")
+    exps = [SC.spell(SC.slots_of(x)) for x in oracle.word_expand(w)]
+    assert len(exps) == 18 and len(set(exps)) == 18
+    assert exps[0] == "ACCTAGAA" and exps[-1] == "ACTTGGTA"
+    assert exps[:4] == ["ACCTAGAA", "ACGTAGAA", "ACTTAGAA", "ACCTAGCA"] and exps[9] == "ACCTGGAA"
 
 
 @pytest.mark.parametrize("name", SC.SCENARIO_NAMES)
