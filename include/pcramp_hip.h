@@ -175,7 +175,12 @@ int pcr_amplify_device(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint3
  * the stream that reads the buffers.  An error met while launching (HIP, capacity) is returned by the
  * NEXT call on the handle, with its text in that thread's pcr_last_error(); the handle's passes queued
  * behind the failed one are dropped, not launched.  Passes that cannot be planned without device work (the
- * first over a set, 5'/3' shift candidates, first-form tables, a tail that is not fused) run inline. */
+ * first over a set, 5'/3' shift candidates, first-form tables, a tail that is not fused) run inline.
+ * Pairs: a queued pass may wait on the launcher thread for the next pass of ANOTHER handle of the stream and
+ * share its two launches with it (PCRAMP_PAIR=0: never); it waits only while the GPU still has two passes
+ * to start, and any call that has to wait for the handle's queued passes releases it.  So the bits of a
+ * pass are there to be read only after pcr_synchronize (or any other entry point) of its handle has
+ * returned: a stream or device synchronisation alone does not launch a pass that is still queued. */
 int pcr_screen_device(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_pairs,
 	int optimize_5, int optimize_3, float select_threshold, uint32_t min_oligo_length,
 	const pcr_amplify_args *args, uint64_t *d_bits_fr, uint64_t *d_bits_rf);

@@ -747,6 +747,7 @@ struct pcr_ctx {
 	std::unordered_map<S2Key, S3Entry, S2KeyHash> s3_cache;
 	std::vector<pcrhost::FoldSeed> s3_tmp;
 	struct S3Launch { Seed3Slices W; uint32_t n_chunks, per_wg, slice_cap, n_irr_wg; };
+	int pair_mode = 1; bool s3_pair_attr_set = false;   // PCRAMP_PAIR: 0 never pair two handles' passes into one launch (A/B), 1 by the backlog rule, 2 "force" (tests: hold until a partner, a flush or the time cap)
 	bool no_seed3 = false, s3_attr_set = false;   // PCRAMP_SEED3=0: second form (A/B)
 	bool s3_next = true;                          // PCRAMP_S3_NEXT=0: the third form with the plain 9-gram lists, span A..T: what it read before the index was sorted by the next base (A/B)
 	bool s2_attr_set = false; uint32_t s2_dbg = 0; bool no_irr_index = false;   // PCRAMP_IRR_INDEX=0: the irregular words scanned in chunks by every wave (A/B)
@@ -1543,6 +1544,7 @@ pcr_ctx *pcr_create(int device, void *hip_stream, const pcr_params *params)
 	if(const char *v = getenv("PCRAMP_SEED3")) ctx->no_seed3 = v[0] == '0';
 	if(const char *v = getenv("PCRAMP_S3_NEXT")) ctx->s3_next = v[0] != '0';
 	if(const char *v = getenv("PCRAMP_LAUNCH_THREAD")) ctx->launch_thread = v[0] != '0';   // A/B, and for callers that want no helper thread
+	if(const char *v = getenv("PCRAMP_PAIR")) ctx->pair_mode = (v[0] == '0') ? 0 : (strcmp(v, "force") == 0) ? 2 : 1;
 	if(const char *v = getenv("PCRAMP_SCAN")){ if(v[0] == '1') ctx->scan_version = 1; else if(v[0] == '2') ctx->scan_version = 2; }   // A/B: 1 = popcount scan, 2 = bit-sliced only
 	{
 		// direct staging: fine-grained device memory the CPU can store into (large BAR) and whose stores a later launch sees.

@@ -358,8 +358,9 @@ struct PostShared {
 	uint64_t keys[POST_WAVES][POST_CAP]; PostEnt ent[POST_WAVES][POST_CAP]; uint32_t msk[POST_WAVES][POST_CAP][POST_MASK_WORDS];
 };
 
+// (the tail of one pass as the workgroups of one launch row run it: k_post is this and nothing else, k_post_pair runs it once per row)
 template<int POST_WAVES>
-__global__ __launch_bounds__(64*POST_WAVES) void k_post(const Hit *__restrict__ hits, uint32_t *__restrict__ seq_count,
+__device__ __forceinline__ void post_pass(PostShared<POST_WAVES> &sh, const Hit *__restrict__ hits, uint32_t *__restrict__ seq_count,
 	const uint32_t *__restrict__ best, uint32_t ncand, const uint4 *__restrict__ planes, const uint64_t *__restrict__ blk_off,
 	const IrrDev *__restrict__ irr, const uint32_t *__restrict__ irr_off, DevEntry *__restrict__ db, uint32_t *__restrict__ seg_hi,
 	uint32_t *__restrict__ counters, uint32_t epoch, uint32_t n_seq,
@@ -367,7 +368,6 @@ __global__ __launch_bounds__(64*POST_WAVES) void k_post(const Hit *__restrict__ 
 	const uint64_t *__restrict__ len, const uint8_t *__restrict__ active, int32_t amp_min, int32_t amp_max, float ident_thr, int use_taq,
 	uint64_t *__restrict__ bits_fr, uint64_t *__restrict__ bits_rf, uint64_t bit_words, PassMail *pub_mail, uint32_t pub_seq)
 {
-	__shared__ PostShared<POST_WAVES> sh;
 	const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
 	if(pub_mail && blockIdx.x == 0 && wave == 0){              // every scan of the pass is complete: its counters -> host mailbox
 		if(lane < 4) pub_mail->counters[lane] = (lane == 3) ? N_TOUCHED_UNKNOWN_DEV : counters[lane];
@@ -496,6 +496,44 @@ __global__ __launch_bounds__(64*POST_WAVES) void k_post(const Hit *__restrict__ 
 			}
 		}
 	}
+}
+
+template<int POST_WAVES>
+__global__ __launch_bounds__(64*POST_WAVES) void k_post(const Hit *__restrict__ hits, uint32_t *__restrict__ seq_count,
+	const uint32_t *__restrict__ best, uint32_t ncand, const uint4 *__restrict__ planes, const uint64_t *__restrict__ blk_off,
+	const IrrDev *__restrict__ irr, const uint32_t *__restrict__ irr_off, DevEntry *__restrict__ db, uint32_t *__restrict__ seg_hi,
+	uint32_t *__restrict__ counters, uint32_t epoch, uint32_t n_seq,
+	const OligoDev *__restrict__ oligos, uint32_t n_pairs, uint32_t mask_words,
+	const uint64_t *__restrict__ len, const uint8_t *__restrict__ active, int32_t amp_min, int32_t amp_max, float ident_thr, int use_taq,
+	uint64_t *__restrict__ bits_fr, uint64_t *__restrict__ bits_rf, uint64_t bit_words, PassMail *pub_mail, uint32_t pub_seq)
+{
+	__shared__ PostShared<POST_WAVES> sh;
+	post_pass<POST_WAVES>(sh, hits, seq_count, best, ncand, planes, blk_off, irr, irr_off, db, seg_hi, counters, epoch, n_seq, oligos, n_pairs, mask_words,
+		len, active, amp_min, amp_max, ident_thr, use_taq, bits_fr, bits_rf, bit_words, pub_mail, pub_seq);
+}
+
+// The tails of two passes of different handles in one launch: row blockIdx.y runs its pass's tail, gridDim.x is the larger of the two
+// workgroup counts and a workgroup beyond its own pass's count leaves at once.  Each row publishes its own mailbox and leaves its
+// own control block clean; the rows share nothing.
+struct PostRow {
+	const Hit *hits; uint32_t *seq_count; const uint32_t *best; uint32_t ncand; const uint4 *planes; const uint64_t *blk_off;
+	const IrrDev *irr; const uint32_t *irr_off; DevEntry *db; uint32_t *seg_hi; uint32_t *counters; uint32_t epoch, n_seq;
+	const OligoDev *oligos; uint32_t n_pairs, mask_words; const uint64_t *len; const uint8_t *active; int32_t amp_min, amp_max; float ident_thr; int use_taq;
+	uint64_t *bits_fr, *bits_rf; uint64_t bit_words; PassMail *pub_mail; uint32_t pub_seq;
+};
+template<int POST_WAVES>
+__device__ __forceinline__ void post_row(PostShared<POST_WAVES> &sh, const PostRow &R)
+{
+	if(blockIdx.x*POST_WAVES >= R.n_seq) return;               // (uniform per workgroup, before any barrier)
+	post_pass<POST_WAVES>(sh, R.hits, R.seq_count, R.best, R.ncand, R.planes, R.blk_off, R.irr, R.irr_off, R.db, R.seg_hi, R.counters, R.epoch, R.n_seq,
+		R.oligos, R.n_pairs, R.mask_words, R.len, R.active, R.amp_min, R.amp_max, R.ident_thr, R.use_taq, R.bits_fr, R.bits_rf, R.bit_words, R.pub_mail, R.pub_seq);
+}
+template<int POST_WAVES>
+__global__ __launch_bounds__(64*POST_WAVES) void k_post_pair(PostRow A, PostRow B)
+{
+	__shared__ PostShared<POST_WAVES> sh;
+	if(blockIdx.y == 0) post_row<POST_WAVES>(sh, A);            // (uniform per workgroup)
+	else post_row<POST_WAVES>(sh, B);
 }
 
 // The same tail for buckets that have grown to 128 or 256 slots (5'/3' shift candidates multiply the words

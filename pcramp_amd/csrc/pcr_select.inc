@@ -163,7 +163,7 @@ bool plan_seed3_slices(pcr_ctx *ctx, PlanLists &PL, bool with_irr)
 		// the launch's first workgroups look the irregular words up (16 seeds per wave turn) and leave the chunks to the others: the two
 		// chains of dependent loads then run side by side; at most a quarter of the launch
 		L.n_irr_wg = with_irr ? std::min<uint32_t>((ns + seeds_per_turn - 1u)/seeds_per_turn, G_all/4u) : 0u;
-		const uint32_t G = G_all - L.n_irr_wg;
+		const uint32_t G = (G_all - L.n_irr_wg) & ~1u;                       // even: a paired launch gives two neighbours' shares to one workgroup (pair_slices)
 		L.n_chunks = P[ns]; L.per_wg = std::max<uint32_t>(1u, (L.n_chunks + G - 1u)/G); L.slice_cap = 2;
 		if(ns == 0) continue;
 		uint32_t at = 0;
@@ -525,6 +525,8 @@ struct PassJob {
 	std::vector<uint4> hf, hr; std::vector<uint32_t> hfl;   // candidate planes and floors as the device reads them
 	std::vector<OligoDev> ol;                         // fused pass: the amplicon screen's oligo table
 	bool fuse = false; size_t bits_bytes = 0;         // fuse: the screen rides in the pass; bytes of each of its two result bitsets
+	// stage B, when the pass is one half of a paired launch (pair_slices): the slices of its half grid
+	Seed3HalfSlices pair_W; uint32_t pair_slice_cap = 0;
 	void reset()
 	{
 		seq = 0; begun = ctrl_was_clean = false; has_fa = false; fa = FusedAmp(); async = false;
@@ -700,23 +702,60 @@ int launch_seed1(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const StagedTables 
 	return PCR_OK;
 }
 
-// Third form: the launch of one seed group (its slices: plan_seed3_slices).
+// Third form: what the launch of one seed group reads (its slices: plan_seed3_slices), and the dynamic LDS it asks for.
+void seed3_args(SeqSet &S, const Seed2Tables &Tg, const uint32_t *d_chunk_prefix, const uint8_t *d_spans, const pcr_ctx::S3Launch &L3, const IrrArgs2 &IA, Seed3Tables &T3, Seed3Set &Q3)
+{
+	T3.seeds = Tg.seeds; T3.spans = d_spans; T3.chunk_prefix = d_chunk_prefix; T3.masks = Tg.masks; T3.floors = Tg.floors;
+	T3.n_seeds = Tg.n_seeds; T3.n_or = Tg.n_or; T3.or_base = Tg.or_base;
+	T3.pix_first = S.pix_first.p; T3.pix_last = S.pix_last.p; T3.pix_ent = S.pix_ent.p;
+	Q3 = Seed3Set{ S.valid_d(), S.blk_info.p, S.blk_local.p, S.d_active.p };
+	T3.n_chunks = L3.n_chunks; T3.per_wg = L3.per_wg; T3.slice_cap = L3.slice_cap;
+	T3.n_irr_wg = IA.ix_first ? L3.n_irr_wg : 0u;           // (without the index the chunk workgroups are fewer than they could be: harmless)
+}
+inline size_t seed3_lds(const Seed3Tables &T3)
+{
+	return (size_t)T3.n_or*sizeof(uint4) + 2*(size_t)T3.slice_cap*sizeof(uint32_t) + (((size_t)T3.n_or + 15) & ~size_t(15)) + (((size_t)T3.slice_cap + 15) & ~size_t(15)) + 16;
+}
+
+// Third form: the launch of one seed group.
 int launch_seed3_group(pcr_ctx *ctx, SeqSet &S, const Seed2Tables &Tg, const uint32_t *d_chunk_prefix, const uint8_t *d_spans, const pcr_ctx::S3Launch &L3, const IrrArgs2 &IA,
 	const HitSink &sink, const S2Clear &Z)
 {
-	Seed3Tables T3; T3.seeds = Tg.seeds; T3.spans = d_spans; T3.chunk_prefix = d_chunk_prefix; T3.masks = Tg.masks; T3.floors = Tg.floors;
-	T3.n_seeds = Tg.n_seeds; T3.n_or = Tg.n_or; T3.or_base = Tg.or_base;
-	T3.pix_first = S.pix_first.p; T3.pix_last = S.pix_last.p; T3.pix_ent = S.pix_ent.p;
-	Seed3Set Q3 = { S.valid_d(), S.blk_info.p, S.blk_local.p, S.d_active.p };
-	T3.n_chunks = L3.n_chunks; T3.per_wg = L3.per_wg; T3.slice_cap = L3.slice_cap;
-	T3.n_irr_wg = IA.ix_first ? L3.n_irr_wg : 0u;           // (without the index the chunk workgroups are fewer than they could be: harmless)
-	const size_t dyn3 = (size_t)Tg.n_or*sizeof(uint4) + 2*(size_t)T3.slice_cap*sizeof(uint32_t) + (((size_t)Tg.n_or + 15) & ~size_t(15)) + (((size_t)T3.slice_cap + 15) & ~size_t(15)) + 16;
+	Seed3Tables T3; Seed3Set Q3;
+	seed3_args(S, Tg, d_chunk_prefix, d_spans, L3, IA, T3, Q3);
+	const size_t dyn3 = seed3_lds(T3);
 	if(!ctx->s3_attr_set){
 		HIP_TRY(hipFuncSetAttribute((const void *)k_seed3<S3_WG_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 128*1024));
 		ctx->s3_attr_set = true;
 	}
 	hipLaunchKernelGGL(k_seed3<S3_WG_THREADS>, dim3(seed3_grid(ctx)), dim3(S3_WG_THREADS), dyn3, ctx->stream, T3, Q3, IA, ctx->d_cand_fwd, ctx->d_cand_floor, sink, Z, L3.W);
 	return PCR_OK;
+}
+
+// How the irregular words of the set reach the launch of one seed group of the second or third form.
+IrrArgs2 group_irr_args(SeqSet &S, const ScanPlan &P, uint32_t group_offmask, bool first_launch, bool irr_by_index)
+{
+	IrrArgs2 IA; IA.scan = S.irr_scan.p; IA.irr = S.irr.p; IA.n_live = P.n_live;
+	IA.off_mask = group_offmask;
+	IA.exhaustive = first_launch ? 1u : 0u;                             // words holding IUPAC slots meet every candidate once, in the first launch
+	IA.ix_first = IA.ix_last = IA.ix_words = nullptr; IA.min_cws = std::min<uint32_t>(P.min_len, 255u);
+	if(!P.or_plain.empty()){                                            // unseeded candidates in the pass: every irregular word meets every candidate, once
+		IA.off_mask = 0;
+		if(!first_launch) IA.n_live = 0;
+	}
+	else if(irr_by_index){                                               // every candidate seeded, no IUPAC word in the set: the words come in through the index, by seed
+		IA.ix_first = S.irx_first.p; IA.ix_last = S.irx_last.p; IA.ix_words = S.irx_words.p; IA.n_live = 0;
+	}
+	return IA;
+}
+// What the launch clears in its prologue: the first launch of a lean pass clears the result bitsets.
+S2Clear group_clear(const StagedTables &T, const FusedAmp *fa, const HitSink &sink, bool first_launch)
+{
+	S2Clear Z = { nullptr, 0u, nullptr, 0u, nullptr };
+	if(T.lean && first_launch){
+		Z.z0 = (uint4 *)fa->d_fr; Z.z1 = (uint4 *)fa->d_rf; Z.n0 = Z.n1 = (uint32_t)(T.bits_bytes/16); Z.ctrl = sink.counters;
+	}
+	return Z;
 }
 
 // Second and third form: one launch per seed group (plan_seed2).  The second form runs persistent workgroups of 16 waves, one per
@@ -750,23 +789,10 @@ int launch_seed_groups(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const PlanLis
 		g_begin = L.s2_group_end[g];
 		if(Tg.n_seeds == 0){ g_prefix += 1u; continue; }
 		const size_t dyn = (size_t)g_or*sizeof(uint4) + (((size_t)g_or + 15) & ~size_t(15)) + 8*((size_t)Tg.n_seeds + 64) + 16;   // masks | floors | chain | head (each with 64 dummy slots)
-		IrrArgs2 IA; IA.scan = S.irr_scan.p; IA.irr = S.irr.p; IA.n_live = P.n_live;
-		IA.off_mask = L.s2_group_offmask[g];
-		IA.exhaustive = first_launch ? 1u : 0u;                             // words holding IUPAC slots meet every candidate once, in the first launch
-		IA.ix_first = IA.ix_last = IA.ix_words = nullptr; IA.min_cws = std::min<uint32_t>(P.min_len, 255u);
-		if(!P.or_plain.empty()){                                            // unseeded candidates in the pass: every irregular word meets every candidate, once
-			IA.off_mask = 0;
-			if(!first_launch) IA.n_live = 0;
-		}
-		else if(irr_by_index){                                               // every candidate seeded, no IUPAC word in the set: the words come in through the index, by seed
-			IA.ix_first = S.irx_first.p; IA.ix_last = S.irx_last.p; IA.ix_words = S.irx_words.p; IA.n_live = 0;
-		}
+		const IrrArgs2 IA = group_irr_args(S, P, L.s2_group_offmask[g], first_launch, irr_by_index);
 		if(ctx->debug_log) fprintf(stderr, "[pcramp] k_seed2: %u workgroups, %u seeds of orientations %u..%u (group %zu of %zu), %zu + %zu B of LDS\n", sgrid.x, Tg.n_seeds,
 			or0, or0 + g_or - 1, g + 1, L.s2_group_end.size(), sizeof(S2Shared), dyn);
-		S2Clear Z = { nullptr, 0u, nullptr, 0u, nullptr };
-		if(T.lean && first_launch){                                          // the first launch of a lean pass clears the result bitsets
-			Z.z0 = (uint4 *)fa->d_fr; Z.z1 = (uint4 *)fa->d_rf; Z.n0 = Z.n1 = (uint32_t)(T.bits_bytes/16); Z.ctrl = sink.counters;
-		}
+		const S2Clear Z = group_clear(T, fa, sink, first_launch);
 		if(seed3){
 			if((rc = launch_seed3_group(ctx, S, Tg, T.d_s3_prefix + g_prefix, d_spans, L.s3_launch[g], IA, sink, Z)) != PCR_OK) return rc;
 			g_prefix += Tg.n_seeds + 1u;
@@ -816,13 +842,24 @@ int launch_scans(pcr_ctx *ctx, SeqSet &S, const ScanPlan &P, const PlanLists &L,
 
 // The whole tail -- DB finalisation and the amplicon screen -- in one launch: k_post (64-slot buckets, WAVES sequences per
 // workgroup) or k_post_big (128 / 256 slots).
+PostRow post_row_args(pcr_ctx *ctx, SeqSet &S, const HitSink &sink, const FusedAmp *fa, uint32_t seq)
+{
+	PostRow R;
+	R.hits = sink.hits; R.seq_count = sink.seq_count; R.best = sink.best; R.ncand = sink.ncand; R.planes = S.planes.p; R.blk_off = S.d_blk_off.p;
+	R.irr = S.irr.p; R.irr_off = S.irr_off.p; R.db = S.db.p; R.seg_hi = S.d_seg_hi; R.counters = sink.counters; R.epoch = sink.epoch; R.n_seq = S.n;
+	R.oligos = fa->d_oligos; R.n_pairs = fa->n_pairs; R.mask_words = (2*fa->n_pairs + 31)/32; R.len = S.d_len.p; R.active = S.d_active.p;
+	R.amp_min = fa->a->amp_min; R.amp_max = fa->a->amp_max; R.ident_thr = fa->a->ident_threshold; R.use_taq = fa->a->use_taq_mama;
+	R.bits_fr = fa->d_fr; R.bits_rf = fa->d_rf; R.bit_words = (uint64_t)((S.n + 63)/64); R.pub_mail = ctx->mail.dev + (seq % pcr_ctx::MAIL_RING); R.pub_seq = seq;
+	return R;
+}
 template<class K>
 void launch_post(K kernel, uint32_t waves, pcr_ctx *ctx, SeqSet &S, const HitSink &sink, const FusedAmp *fa, uint32_t seq)
 {
-	hipLaunchKernelGGL(kernel, dim3((S.n + waves - 1)/waves), dim3(64*waves), 0, ctx->stream, sink.hits, sink.seq_count, sink.best, sink.ncand, S.planes.p,
-		S.d_blk_off.p, S.irr.p, S.irr_off.p, S.db.p, S.d_seg_hi, sink.counters, sink.epoch, S.n,
-		fa->d_oligos, fa->n_pairs, (2*fa->n_pairs + 31)/32, S.d_len.p, S.d_active.p, fa->a->amp_min, fa->a->amp_max,
-		fa->a->ident_threshold, fa->a->use_taq_mama, fa->d_fr, fa->d_rf, (uint64_t)((S.n + 63)/64), ctx->mail.dev + (seq % pcr_ctx::MAIL_RING), seq);
+	const PostRow R = post_row_args(ctx, S, sink, fa, seq);
+	hipLaunchKernelGGL(kernel, dim3((S.n + waves - 1)/waves), dim3(64*waves), 0, ctx->stream, R.hits, R.seq_count, R.best, R.ncand, R.planes,
+		R.blk_off, R.irr, R.irr_off, R.db, R.seg_hi, R.counters, R.epoch, R.n_seq,
+		R.oligos, R.n_pairs, R.mask_words, R.len, R.active, R.amp_min, R.amp_max,
+		R.ident_thr, R.use_taq, R.bits_fr, R.bits_rf, R.bit_words, R.pub_mail, R.pub_seq);
 }
 // reserved_seq: the sequence number a pipelined pass was given at enqueue; 0: the next one
 int fused_tail(pcr_ctx *ctx, SeqSet &S, const HitSink &sink, FusedAmp *fa, uint32_t reserved_seq)
@@ -943,6 +980,59 @@ bool pass_is_pipelinable(const pcr_ctx *ctx, const PassJob &J)
 		&& fused_tail_fits(S.bucket_cap, J.fa.n_pairs) && buckets_fit((uint64_t)S.n*S.bucket_cap);
 }
 
+// Stage B in steps, so that two passes of different handles can share their launches (run_pass_pair): stage_pass and size_attempt
+// prepare a pass (buffers ensured, ring slot written, epoch taken), pass_enqueued does its bookkeeping once it is on the stream.
+
+// The pass's arg-max table and its tables on the device.  (Non-empty passes only.)
+int stage_pass(pcr_ctx *ctx, PassJob &J, bool ctrl_was_clean, StagedTables &T)
+{
+	SeqSet &S = ctx->sets[J.which];
+	int rc;
+	if((rc = ctx->best.ensure((size_t)S.n*J.cand.size())) != PCR_OK) return rc;
+	if(ctx->best.generation != ctx->best_seen){
+		// fresh (uninitialised) storage: clear once; afterwards the epoch tag makes clearing unnecessary
+		HIP_TRY(hipMemsetAsync(ctx->best.p, 0, ctx->best.cap*sizeof(uint32_t), ctx->stream));
+		ctx->best_seen = ctx->best.generation; ctx->epoch = std::min(ctx->debug_epoch, EPOCH_LIMIT);
+	}
+	if((rc = stage_tables(ctx, S, J, J.has_fa ? &J.fa : nullptr, J.async, ctrl_was_clean, T)) != PCR_OK) return rc;
+	if((rc = S.touched.ensure(S.n)) != PCR_OK) return rc;
+	S.d_seg_hi = S.ctrl.p + 8 + S.n;
+	return PCR_OK;
+}
+
+// The buckets of one attempt at the set's current bucket size, the attempt's epoch, and the sink its launches append to.
+int size_attempt(pcr_ctx *ctx, SeqSet &S, const PassJob &J, int attempt, HitSink &sink)
+{
+	int rc;
+	const uint32_t cap = S.bucket_cap;
+	const uint64_t n_slots = (uint64_t)S.n*cap;
+	if(!buckets_fit(n_slots)){
+		assert(J.seq == 0);                              // (pass_is_pipelinable)
+		S.bucket_cap = 64;   // (the size that was refused must not stay: the next pass over this set, with other candidates, starts small and grows again)
+		g_err = "pcr_select_words: the per-sequence hit buckets would not fit (too many tied sites per sequence)"; return PCR_ERR_CAPACITY;
+	}
+	if((rc = ctx->hits.ensure(n_slots)) != PCR_OK) return rc;
+	if((rc = S.db.ensure(n_slots)) != PCR_OK) return rc;
+	if(attempt > 0) HIP_TRY(hipMemsetAsync(S.ctrl.p, 0, (8 + 2*(size_t)S.n)*sizeof(uint32_t), ctx->stream));
+	if(ctx->epoch >= EPOCH_LIMIT){
+		// the tag (epoch << 8 | count) is about to leave its 24 bits: every stale entry would compare HIGHER than the new
+		// pass's hits and swallow them.  Checked per attempt (every bucket-growth retry takes an epoch of its own).
+		HIP_TRY(hipMemsetAsync(ctx->best.p, 0, ctx->best.cap*sizeof(uint32_t), ctx->stream));
+		ctx->epoch = 0;
+	}
+	++ctx->epoch;
+	sink.best = ctx->best.p; sink.hits = ctx->hits.p; sink.seq_count = S.ctrl.p + 8;
+	sink.counters = S.ctrl.p; sink.cap = cap; sink.ncand = (uint32_t)J.cand.size(); sink.epoch = ctx->epoch;
+	return PCR_OK;
+}
+
+// An asynchronous pass is on the stream: nobody looks at its counters here (the caller has recorded it as pending).
+inline void pass_enqueued(SeqSet &S, uint32_t cap)
+{
+	S.db_cap = cap; S.n_slots = (uint64_t)S.n*cap;
+	S.n_touched = N_TOUCHED_UNKNOWN; S.n_entries = 1; S.have_db = true;
+}
+
 // Stage B: size the device buffers, stage the tables, launch the scans and the tail.  async: one attempt, nobody looks at the
 // counters (pcr_screen_device; the caller has recorded or will record the pass as pending).
 int run_pass(pcr_ctx *ctx, PassJob &J, uint64_t *n_entries_out)
@@ -956,48 +1046,21 @@ int run_pass(pcr_ctx *ctx, PassJob &J, uint64_t *n_entries_out)
 	if(S.n == 0 || ncand == 0){ S.have_db = true; S.n_touched = 0; return PCR_OK; }
 	HostTimer timer(ctx, 1);
 	int rc;
-	if((rc = ctx->best.ensure((size_t)S.n*ncand)) != PCR_OK) return rc;
-	if(ctx->best.generation != ctx->best_seen){
-		// fresh (uninitialised) storage: clear once; afterwards the epoch tag makes clearing unnecessary
-		HIP_TRY(hipMemsetAsync(ctx->best.p, 0, ctx->best.cap*sizeof(uint32_t), ctx->stream));
-		ctx->best_seen = ctx->best.generation; ctx->epoch = std::min(ctx->debug_epoch, EPOCH_LIMIT);
-	}
 	StagedTables T;
-	if((rc = stage_tables(ctx, S, J, fa, async, ctrl_was_clean, T)) != PCR_OK) return rc;
+	if((rc = stage_pass(ctx, J, ctrl_was_clean, T)) != PCR_OK) return rc;
 
 	timer.next(2);
 	uint32_t h_counters[4];
-	if((rc = S.touched.ensure(S.n)) != PCR_OK) return rc;
-	S.d_seg_hi = S.ctrl.p + 8 + S.n;
 	for(int attempt = 0;;++attempt){
 		const uint32_t cap = S.bucket_cap;
 		const uint64_t n_slots = (uint64_t)S.n*cap;
-		if(!buckets_fit(n_slots)){
-			assert(J.seq == 0);                              // (pass_is_pipelinable)
-			S.bucket_cap = 64;   // (the size that was refused must not stay: the next pass over this set, with other candidates, starts small and grows again)
-			g_err = "pcr_select_words: the per-sequence hit buckets would not fit (too many tied sites per sequence)"; return PCR_ERR_CAPACITY;
-		}
-		if((rc = ctx->hits.ensure(n_slots)) != PCR_OK) return rc;
-		if((rc = S.db.ensure(n_slots)) != PCR_OK) return rc;
-		if(attempt > 0) HIP_TRY(hipMemsetAsync(S.ctrl.p, 0, (8 + 2*(size_t)S.n)*sizeof(uint32_t), ctx->stream));
-		if(ctx->epoch >= EPOCH_LIMIT){
-			// the tag (epoch << 8 | count) is about to leave its 24 bits: every stale entry would compare HIGHER than the new
-			// pass's hits and swallow them.  Checked per attempt (every bucket-growth retry takes an epoch of its own).
-			HIP_TRY(hipMemsetAsync(ctx->best.p, 0, ctx->best.cap*sizeof(uint32_t), ctx->stream));
-			ctx->epoch = 0;
-		}
-		++ctx->epoch;
-		HitSink sink; sink.best = ctx->best.p; sink.hits = ctx->hits.p; sink.seq_count = S.ctrl.p + 8;
-		sink.counters = S.ctrl.p; sink.cap = cap; sink.ncand = ncand; sink.epoch = ctx->epoch;
+		HitSink sink;
+		if((rc = size_attempt(ctx, S, J, attempt, sink)) != PCR_OK) return rc;
 		const bool fused = async && fa && fa->staged && fused_tail_fits(cap, fa->n_pairs);
 		if(J.seq && !fused){ g_err = "pcr_screen_device: a pipelined pass lost its fused tail"; return PCR_ERR_STATE; }   // (pass_is_pipelinable: cannot happen)
 		if((rc = launch_scans(ctx, S, P, J.L, T, fa, sink)) != PCR_OK) return rc;
 		if((rc = fused ? fused_tail(ctx, S, sink, fa, J.seq) : plain_tail(ctx, S, sink, async, fa)) != PCR_OK) return rc;
-		if(async){
-			S.db_cap = cap; S.n_slots = n_slots;
-			S.n_touched = N_TOUCHED_UNKNOWN; S.n_entries = 1; S.have_db = true;
-			return PCR_OK;
-		}
+		if(async){ pass_enqueued(S, cap); return PCR_OK; }
 		timer.next(3);
 		if((rc = mail_wait(ctx, ctx->mail_seq, h_counters)) != PCR_OK) return rc;
 		timer.next(2);
@@ -1019,12 +1082,117 @@ int run_pass(pcr_ctx *ctx, PassJob &J, uint64_t *n_entries_out)
 	return PCR_OK;
 }
 
+// ---- two queued passes of different handles as ONE scan launch and ONE tail launch (k_seed3_pair, k_post_pair)
+//
+// Both kernels of a pass are bound by the latency of a chain of dependent loads, and a stream runs its kernels one after the other:
+// while one pass walks its chain the next one waits.  Two passes that share no state walk side by side instead, each on half the
+// scan's workgroups.  What a pass records -- hits, fills, DB, bits, mailbox -- is what it records alone.
+
+// Could the planned pass be one half of a pair?  Third form with one launch group and no other scan launch, 64-slot buckets with
+// the fused tail, its scan not bracketed by profiling events (a bracketed scan is timed as one pass's: it launches alone).
+bool pass_is_pairable(const pcr_ctx *ctx, const PassJob &J)
+{
+	const SeqSet &S = ctx->sets[J.which];
+	return ctx->pair_mode != 0 && pass_is_pipelinable(ctx, J) && J.P.form == ScanForm::Seed3 && J.L.s2_group_end.size() == 1 && J.L.s2_group_end[0] != 0
+		&& !J.P.need_plain && !J.P.need_seedset && S.n_tiles != 0 && S.bucket_cap == POST_CAP
+		&& !(ctx->prof && ctx->prof_pass % ctx->prof_stride == 0);
+}
+
+// The slices of a pass on half the chunk workgroups with twice the share each: workgroup w takes the shares of 2w and 2w + 1 of the
+// plan (which has an even number of them), so its slice starts where 2w's does.  false: the widest slice does not fit the LDS.
+bool pair_slices(const pcr_ctx *ctx, PassJob &J)
+{
+	const pcr_ctx::S3Launch &L3 = J.L.s3_launch[0];
+	const uint32_t ns = J.L.s2_group_end[0], G = (seed3_grid(ctx) - L3.n_irr_wg) & ~1u, Gh = G/2;
+	uint32_t *const st = J.pair_W.start;
+	for(uint32_t w = 0;w <= Gh;++w) st[w] = L3.W.start[2*w];
+	for(uint32_t w = Gh + 1;w <= S3_MAX_WG/2;++w) st[w] = st[Gh];
+	uint32_t cap = 2;
+	for(uint32_t w = 0;w < Gh;++w) cap = std::max(cap, std::min(st[w + 1] + 2u, ns + 1u) - st[w]);
+	J.pair_slice_cap = cap;
+	return 17*(size_t)J.L.s2_group_nor[0] + 9*(size_t)cap + 64 <= S3_LDS_BUDGET;
+}
+
+// May A and B (pushed in this order) share their launches?  Different handles -- passes of one handle share its hits and arg-max
+// tables --, both pairable, and neither writes where the other does.
+bool passes_can_pair(PassJob &A, PassJob &B)
+{
+	if(A.ctx == B.ctx || !pass_is_pairable(A.ctx, A) || !pass_is_pairable(B.ctx, B)) return false;
+	const uintptr_t a[2] = { (uintptr_t)A.fa.d_fr, (uintptr_t)A.fa.d_rf }, b[2] = { (uintptr_t)B.fa.d_fr, (uintptr_t)B.fa.d_rf };
+	for(int i = 0;i < 2;++i) for(int j = 0;j < 2;++j){ if(a[i] < b[j] + B.bits_bytes && b[j] < a[i] + A.bits_bytes) return false; }
+	return pair_slices(A.ctx, A) && pair_slices(B.ctx, B);
+}
+
+// One half of a pair, prepared: everything run_pass does before its launches.
+struct PairHalf { pcr_ctx *ctx; PassJob *J; SeqSet *S; StagedTables T; HitSink sink; Seed3Row scan; PostRow post; };
+int prepare_half(PairHalf &H)
+{
+	pcr_ctx *const ctx = H.ctx; PassJob &J = *H.J; SeqSet &S = *H.S;
+	const bool ctrl_was_clean = begin_pass(S);
+	int rc;
+	HostTimer timer(ctx, 1);
+	if((rc = stage_pass(ctx, J, ctrl_was_clean, H.T)) != PCR_OK) return rc;
+	timer.next(2);
+	if((rc = size_attempt(ctx, S, J, 0, H.sink)) != PCR_OK) return rc;
+	if(!J.fa.staged || H.sink.cap != POST_CAP){ g_err = "pcr_screen_device: a paired pass lost its fused tail"; return PCR_ERR_STATE; }   // (pass_is_pairable: cannot happen)
+	if(ctx->prof) ++ctx->prof_pass;                       // (not bracketed: pass_is_pairable)
+	// the launch's only seed group, as launch_seed_groups makes it
+	const PlanLists &L = J.L;
+	Seed2Tables Tg = H.T.ST2;
+	Tg.n_seeds = L.s2_group_end[0]; Tg.masks = H.T.ST2.masks + (size_t)L.s2_group_or[0]; Tg.floors = H.T.ST2.floors + L.s2_group_or[0];
+	Tg.n_or = L.s2_group_nor[0]; Tg.or_base = L.s2_group_or[0];
+	H.scan.IA = group_irr_args(S, J.P, L.s2_group_offmask[0], true, J.P.s3_with_irr);
+	seed3_args(S, Tg, H.T.d_s3_prefix, H.T.d_s3_spans, L.s3_launch[0], H.scan.IA, H.scan.T3, H.scan.Q);
+	H.scan.T3.per_wg *= 2u; H.scan.T3.slice_cap = J.pair_slice_cap; H.scan.T3.n_irr_wg = (H.scan.T3.n_irr_wg + 1u)/2u;
+	H.scan.cand_fwd = ctx->d_cand_fwd; H.scan.cand_floor = ctx->d_cand_floor; H.scan.sink = H.sink;
+	H.scan.Z = group_clear(H.T, &J.fa, H.sink, true);
+	H.post = post_row_args(ctx, S, H.sink, &J.fa, J.seq);
+	return PCR_OK;
+}
+
+// Stage B of two passes at once (launcher thread): each prepared, the two joint launches, each one's bookkeeping.
+int run_pass_pair(PassJob &JA, PassJob &JB)
+{
+	PairHalf H[2];
+	H[0].ctx = JA.ctx; H[0].J = &JA; H[1].ctx = JB.ctx; H[1].J = &JB;
+	int rc;
+	for(PairHalf &h : H){
+		h.S = &h.ctx->sets[h.J->which];
+		if((rc = prepare_half(h)) != PCR_OK) return rc;
+	}
+	pcr_ctx *const ctx = JA.ctx;
+	HostTimer timer(ctx, 2);
+	const uint32_t Gx = seed3_grid(ctx)/2;
+	const size_t dyn3 = std::max(seed3_lds(H[0].scan.T3), seed3_lds(H[1].scan.T3));
+	if(!ctx->s3_pair_attr_set){
+		HIP_TRY(hipFuncSetAttribute((const void *)k_seed3_pair<S3_WG_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 128*1024));
+		ctx->s3_pair_attr_set = true;
+	}
+	const uint32_t Px = (std::max(H[0].S->n, H[1].S->n) + 7u)/8u;
+	if(ctx->debug_log) fprintf(stderr, "[pcramp] paired launch: passes %u + %u, scan grid %u x 2 (irregular workgroups %u + %u, slice_cap' %u + %u, %zu B of LDS), tail grid %u x 2\n",
+		JA.seq, JB.seq, Gx, H[0].scan.T3.n_irr_wg, H[1].scan.T3.n_irr_wg, H[0].scan.T3.slice_cap, H[1].scan.T3.slice_cap, dyn3, Px);
+	hipLaunchKernelGGL(k_seed3_pair<S3_WG_THREADS>, dim3(Gx, 2), dim3(S3_WG_THREADS), dyn3, ctx->stream, H[0].scan, JA.pair_W, H[1].scan, JB.pair_W);
+	HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_post_pair<8>, dim3(Px, 2), dim3(64*8), 0, ctx->stream, H[0].post, H[1].post);
+	HIP_TRY(hipGetLastError());
+	for(PairHalf &h : H){
+		h.S->ctrl_clean = true; h.S->touched_from_seg = true;          // (as fused_tail)
+		h.J->fa.posted = true; h.S->touched_built = false;
+		pass_enqueued(*h.S, POST_CAP);
+	}
+	return PCR_OK;
+}
+
 void fill_job(pcr_ctx *ctx, PassJob &J, pcr_set which, int optimize_5, int optimize_3, float threshold, uint32_t min_oligo_length, bool async, const FusedAmp *fa)
 {
 	J.ctx = ctx; J.which = (int)which; J.opt5 = optimize_5; J.opt3 = optimize_3; J.thr = threshold; J.min_len = min_oligo_length; J.async = async;
 	J.has_fa = fa != nullptr;
 	if(fa){ J.fa = *fa; J.args = *fa->a; J.fa.a = &J.args; }            // (the job outlives the call: it keeps the arguments by value)
 }
+
+// Before a pass is launched from the calling thread: every pass queued on the handle's stream -- by whichever handle; the launcher
+// thread may be holding one for a partner -- is launched first, so that the passes of a stream reach it in call order.
+void quiesce_stream(pcr_ctx *ctx);
 
 // pcr_select_words proper, and the inline pcr_screen_device pass: stage A and stage B on the calling thread, with a job on the
 // stack.  fa: in/out (staged, posted, pub_*).
@@ -1036,6 +1204,7 @@ int select_impl(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_p
 	HIP_TRY(hipSetDevice(ctx->device));
 	if(n_entries_out) *n_entries_out = 0;
 	assert(ctx->lq_client.queued.load() == 0);           // inline: every caller came through DRAIN or flush_launcher
+	quiesce_stream(ctx);
 	PassJob J;
 	fill_job(ctx, J, which, optimize_5, optimize_3, threshold, min_oligo_length, async, fa);
 	J.ctrl_was_clean = begin_pass(ctx->sets[which]); J.begun = true;
@@ -1053,9 +1222,41 @@ int select_impl(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_p
 struct Launcher {
 	int device; hipStream_t stream; unsigned refs = 0;
 	cpu_set_t near; bool have_near = false;     // where the thread should run: see near_cpus()
+	// the passes this thread has put on the stream and not yet seen published (launcher thread; forget_handle under the lock)
+	struct InFlight { const pcr_ctx *ctx; const PassMail *slot; uint32_t seq; };
+	std::mutex inflight_m; std::vector<InFlight> inflight;
 	pcrq::LaunchQueue q;
 	Launcher(int dev, hipStream_t st, unsigned spin_us);
+	void forget_published()                          // (under inflight_m)
+	{
+		inflight.erase(std::remove_if(inflight.begin(), inflight.end(), [](const InFlight &f){
+			const uint32_t v = __atomic_load_n((const uint32_t *)&f.slot->seq, __ATOMIC_ACQUIRE);
+			return v >= f.seq && (v - f.seq) % pcr_ctx::MAIL_RING == 0; }), inflight.end());
+	}
+	void launched(const PassJob &J)
+	{
+		std::lock_guard<std::mutex> lk(inflight_m);
+		// (nobody asks for the backlog of a stream that never holds a pass: the list must not grow there.  A handle has at most
+		// MAIL_RING passes unpublished, so what is left beyond a few rings' worth belongs to a stream that has stopped publishing)
+		if(inflight.size() >= 4*pcr_ctx::MAIL_RING){ forget_published(); if(inflight.size() >= 4*pcr_ctx::MAIL_RING) inflight.erase(inflight.begin()); }
+		inflight.push_back(InFlight{ J.ctx, J.ctx->mail.host + (J.seq % pcr_ctx::MAIL_RING), J.seq });
+	}
+	// passes on the stream whose tail has not started (k_post publishes at its start): the GPU's backlog
+	size_t backlog()
+	{
+		std::lock_guard<std::mutex> lk(inflight_m);
+		forget_published();
+		return inflight.size();
+	}
+	void forget_handle(const pcr_ctx *ctx)            // pcr_destroy, after the handle's flush: its mailbox is about to go
+	{
+		std::lock_guard<std::mutex> lk(inflight_m);
+		inflight.erase(std::remove_if(inflight.begin(), inflight.end(), [&](const InFlight &f){ return f.ctx == ctx; }), inflight.end());
+	}
 };
+// A lone pairable pass is held at most this long (the backlog rule or a flush end the hold long before; PCRAMP_PAIR=force and a
+// stream that has stopped publishing after a device error are what it bounds).
+constexpr unsigned PAIR_HOLD_CAP_US = 20000;
 std::mutex g_launchers_m;
 std::vector<Launcher *> g_launchers;
 
@@ -1125,11 +1326,13 @@ bool near_cpus(cpu_set_t &out)
 }
 
 Launcher::Launcher(int dev, hipStream_t st, unsigned spin_us) : device(dev), stream(st),
-	q([](void *job, std::string &err) -> int {
+	q([this](void *job, std::string &err) -> int {
 		PassJob &J = *(PassJob *)job;
 		assert(J.seq != 0 && J.ctx->launcher);
+		if(J.ctx->debug_log) fprintf(stderr, "[pcramp] single launch: pass %u of handle %p (%s)\n", J.seq, (void *)J.ctx, pass_is_pairable(J.ctx, J) ? "pairable" : "not pairable");
 		const int rc = run_pass(J.ctx, J, nullptr);
 		if(rc != PCR_OK) err = g_err;                     // (this thread's: the handle's next call copies it into its own)
+		else launched(J);
 		return rc;
 	},
 	[](void *job){ PassJob *J = (PassJob *)job; release_job(J->ctx, J); },
@@ -1141,6 +1344,27 @@ Launcher::Launcher(int dev, hipStream_t st, unsigned spin_us) : device(dev), str
 {
 	const char *v = getenv("PCRAMP_LAUNCH_PIN");           // =0: leave the thread's placement to the scheduler (A/B)
 	have_near = !(v && v[0] == '0') && near_cpus(near);
+	// Pairs (run_pass_pair).  This thread is faster than the callers, so its queue is normally empty and the backlog sits in the
+	// stream: a lone pairable pass is held only while the GPU still has two passes to start -- holding then costs nothing -- or,
+	// with PCRAMP_PAIR=force, until something ends the hold (pcr_launch_queue.hpp).
+	pcrq::LaunchQueue::Pairing pr;
+	pr.holdable = [](void *job){ const PassJob &J = *(const PassJob *)job; return pass_is_pairable(J.ctx, J); };
+	pr.may_hold = [this](void *job){ return ((const PassJob *)job)->ctx->pair_mode == 2 || backlog() >= 2; };
+	pr.can_pair = [](void *a, void *b){
+		PassJob &A = *(PassJob *)a, &B = *(PassJob *)b;
+		const bool ok = passes_can_pair(A, B);
+		if(!ok && A.ctx->debug_log) fprintf(stderr, "[pcramp] pass %u of handle %p does not pair with pass %u of handle %p behind it\n", A.seq, (void *)A.ctx, B.seq, (void *)B.ctx);
+		return ok;
+	};
+	pr.run_pair = [this](void *a, void *b, std::string &err) -> int {
+		PassJob &A = *(PassJob *)a, &B = *(PassJob *)b;
+		const int rc = run_pass_pair(A, B);
+		if(rc != PCR_OK) err = g_err;
+		else{ launched(A); launched(B); }
+		return rc;
+	};
+	pr.cap_us = PAIR_HOLD_CAP_US;
+	q.set_pairing(std::move(pr));
 }
 
 Launcher *attach_launcher(pcr_ctx *ctx)
@@ -1163,6 +1387,7 @@ void detach_launcher(pcr_ctx *ctx)
 	Launcher *L = ctx->launcher;
 	if(!L) return;
 	ctx->launcher = nullptr;
+	L->forget_handle(ctx);
 	{
 		std::lock_guard<std::mutex> lk(g_launchers_m);
 		if(--L->refs) return;
@@ -1170,6 +1395,13 @@ void detach_launcher(pcr_ctx *ctx)
 	}
 	L->q.stop();                                          // joins the thread
 	delete L;
+}
+
+void quiesce_stream(pcr_ctx *ctx)
+{
+	if(ctx->launcher){ ctx->launcher->q.wait_empty(); return; }
+	std::lock_guard<std::mutex> lk(g_launchers_m);       // (a handle that has not pipelined a pass yet: the stream's launcher, if another handle made one)
+	for(Launcher *L : g_launchers){ if(L->device == ctx->device && L->stream == ctx->stream){ L->q.wait_empty(); return; } }
 }
 
 // Wait for the handle's queued passes to be launched.  One of them failed: its error comes back here, once, with the message in
@@ -1229,6 +1461,8 @@ int screen_pass(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_p
 		return PCR_OK;
 	}
 	assert(ctx->lq_client.queued.load() == 0);           // stage B on this thread: the launcher thread holds no pass of the handle
+	if(ctx->debug_log) fprintf(stderr, "[pcramp] inline pass of handle %p\n", (void *)ctx);
+	quiesce_stream(ctx);
 	const uint32_t seq0 = ctx->mail_seq;
 	rc = run_pass(ctx, *J, nullptr);
 	if(rc == PCR_OK && !J->fa.posted) rc = amplify_launch(ctx, S, pairs, n_pairs, args, d_bits_fr, d_bits_rf, &J->fa);
