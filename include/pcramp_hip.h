@@ -772,6 +772,65 @@ int64_t pcr_pool_products_tm(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, 
 	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor,
 	uint32_t *oligo_id, pcr_product_tm *out, uint64_t cap, uint64_t *bits_fr, uint64_t *bits_rf);
 
+/* ---- Products of a pool under a 3'-end extension rule */
+
+/* What a product's two sites must show at the 3' end of their primers, the end the polymerase extends from. */
+typedef struct {
+	uint32_t min_clamp3;                /* 0 = off */
+	uint32_t window;                    /* 0 .. 32: how many slots at the 3' end max_end_mismatch looks at */
+	uint32_t max_end_mismatch;          /* mismatching slots allowed inside the window */
+	int32_t  use_taq_mama;              /* 0 / 1: id_plus / id_minus carry update_identity's TaqMAMA factor */
+	float    ident_threshold;           /* 0 = off; else keep iff sqrtf(id_plus * id_minus) >= ident_threshold */
+} pcr_end3_rule;
+
+/* One product with the Tm and the 3' end of its plus site and of its minus site (64 bytes). */
+typedef struct {
+	uint32_t plus_oligo, minus_oligo, sequence;
+	int32_t  begin, end, inner_start, inner_length;
+	uint32_t intended;
+	float    tm_plus, tm_minus;
+	uint32_t flags;                     /* PCR_PRODUCT_* */
+	uint32_t reserved;                  /* 0; the twelve fields of pcr_product_tm, same meaning, same bytes (48) */
+	uint8_t  clamp3_plus, clamp3_minus; /* consecutive matching slots from the oligo's last slot downwards */
+	uint8_t  end_mismatch_plus, end_mismatch_minus;   /* mismatching slots among the last min(window, length) */
+	float    id_plus, id_minus;         /* update_identity's score of the oligo at the site */
+	uint32_t reserved2;                 /* 0 */
+} pcr_product_end3;
+
+/* pcr_pool_products_tm with a rule on where the mismatches of the two sites lie: a site whose only mismatch is under the
+ * primer's last base melts a degree or two below the exact site and is the textbook site that does not extend.
+ *   Products, Tm, floor, order, bitsets, oligo_id.  Exactly pcr_pool_products_tm's for the same handle state and arguments.
+ * args may be NULL: no thermodynamics run, both Tm are 0 and flags is 0; tm_floor > 0 is then refused, and no concentration
+ * or salt is looked at (as pcr_site_variants without args).
+ *   Per-site quantities.  Taken from the entry pcr_site_tm reads the site from (among the entries sharing the site's loc and
+ * strand and matching the oligo, the one with the most occupied slots in the oligo's window; on a tie the lowest slot masks),
+ * so they agree with the site's pcr_site_variants record.  For oligo c with slots start .. stop and that entry's word w, slot k
+ * matches iff c and w share a base there (Word & Word per slot); an empty slot of w -- a site hanging over a sequence end --
+ * is a mismatch.  clamp3: the consecutive matching slots from stop downwards (= pcr_site_variant.clamp3).  end_mismatch: the
+ * mismatching slots among the last min(window, length) slots, 0 with window = 0.  id: (float)matches * float(1.0/length) in
+ * float, matches as pcr_site.matches; with use_taq_mama times update_identity's factor (optimize.cpp:209-261), min(1,
+ * c_taq_mama[template's last two][primer's last two]), in float, applied only when the oligo's last two slots and the word's
+ * two slots under them each hold exactly one base.  That is the score pcr_amplify tests for the same oligo and word.
+ *   Rule.  A product that passes the Tm floor is kept iff for both sites clamp3 >= min(min_clamp3, length) and, with window >
+ * 0, end_mismatch <= max_end_mismatch; and ident_threshold == 0 or sqrtf(id_plus * id_minus) >= ident_threshold (product and
+ * root in float, correctly rounded: pcr_amplify's test).  rule = NULL or an all-zero rule keeps everything: the first 48
+ * bytes of every record are then pcr_pool_products_tm's record and the bitsets are its bitsets.  Records, the return value
+ * and the bitsets are of the kept products; *n_before_rule (may be NULL) receives the number past the Tm floor before the
+ * rule.  cap, out, bits_fr / bits_rf and the condition under which the thermodynamics run (with args) are
+ * pcr_pool_products_tm's: cap = 0 counts, a count above cap leaves out unspecified, rows are written in full whenever the
+ * call returns >= 0 and are reduced on the device from the join.
+ *   PCR_ERR_ARG, from the arguments alone and before the handle: pcr_pool_products_tm's checks in its order, the
+ * concentration and salt ones only with args; after the tm_floor that is not finite: window, min_clamp3 or max_end_mismatch
+ * above 32; use_taq_mama neither 0 nor 1; ident_threshold not finite or outside [0, 1]; tm_floor > 0 without args; then a
+ * null handle.  PCR_ERR_STATE, PCR_ERR_CAPACITY (also for 2^31 or more products before the rule) and PCR_ERR_RANGE as
+ * pcr_pool_products_tm.  Changes nothing other calls read.  On a handle with a target shard attached, sequence indices are
+ * local to the rank's block and no collective is made.  pcr_pool_anneal_profile, pcr_pool_conflicts and pcr_pool_probe_hits
+ * do not take the rule. */
+int64_t pcr_pool_products_end3(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args /* may be NULL */, float template_strand, float tm_floor,
+	const pcr_end3_rule *rule, uint32_t *oligo_id, pcr_product_end3 *out, uint64_t cap,
+	uint64_t *bits_fr, uint64_t *bits_rf, uint64_t *n_before_rule /* may be NULL */);
+
 /* ---- Annealing profile: what a pool amplifies at every temperature of a gradient, from one melt and one join */
 
 #define PCR_ANNEAL_MAX_TEMPS 256

@@ -102,6 +102,11 @@ PRODUCT_TM_DTYPE = np.dtype([("plus_oligo", np.uint32), ("minus_oligo", np.uint3
                              ("tm_plus", np.float32), ("tm_minus", np.float32), ("flags", np.uint32), ("reserved", np.uint32)])
 PRODUCT_PLUS_NO_TM, PRODUCT_MINUS_NO_TM = 1, 2   # PCR_PRODUCT_*_NO_TM
 
+# pcr_product_end3: pcr_product_tm's twelve fields, then the 3' end of the two sites (Screener.pool_products_end3); 64 bytes
+PRODUCT_END3_DTYPE = np.dtype(PRODUCT_TM_DTYPE.descr + [("clamp3_plus", np.uint8), ("clamp3_minus", np.uint8),
+                                                        ("end_mismatch_plus", np.uint8), ("end_mismatch_minus", np.uint8),
+                                                        ("id_plus", np.float32), ("id_minus", np.float32), ("reserved2", np.uint32)])
+
 # pcr_anneal_point: one temperature of an annealing profile (Screener.anneal_profile)
 ANNEAL_POINT_DTYPE = np.dtype([("temperature", np.float32), ("reserved", np.uint32), ("products_intended", np.uint64),
                                ("products_spurious", np.uint64), ("cells", np.uint64), ("spurious_sequences", np.uint64)])
@@ -171,6 +176,11 @@ class AssayRecord(C.Structure):
                 ("num_active_background", C.c_uint32), ("target_match", C.c_void_p), ("background_match", C.c_void_p)]
 
 
+class End3Rule(C.Structure):
+    _fields_ = [("min_clamp3", C.c_uint32), ("window", C.c_uint32), ("max_end_mismatch", C.c_uint32),
+                ("use_taq_mama", C.c_int32), ("ident_threshold", C.c_float)]
+
+
 class AmplifyArgs(C.Structure):
     _fields_ = [("collect_threshold", C.c_float), ("ident_threshold", C.c_float), ("amp_min", C.c_int32),
                 ("amp_max", C.c_int32), ("use_taq_mama", C.c_int32)]
@@ -193,7 +203,7 @@ ABI_SYMBOLS = [
     "pcr_thermo", "pcr_valid_words", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers",
-    "pcr_pool_products_tm", "pcr_pool_anneal_profile", "pcr_pool_conflicts", "pcr_pool_probe_hits", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants", "pcr_site_repair",
+    "pcr_pool_products_tm", "pcr_pool_products_end3", "pcr_pool_anneal_profile", "pcr_pool_conflicts", "pcr_pool_probe_hits", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants", "pcr_site_repair",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats", "pcr_live_resources",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -297,6 +307,10 @@ def load_library():
     L.pcr_pool_products_tm.restype = C.c_int64
     L.pcr_pool_products_tm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
                                        C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.pcr_pool_products_end3.restype = C.c_int64
+    L.pcr_pool_products_end3.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
+                                         C.c_float, C.c_float, C.POINTER(End3Rule), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.c_void_p, C.POINTER(C.c_uint64)]
     L.pcr_pool_anneal_profile.restype = C.c_int64
     L.pcr_pool_anneal_profile.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
                                           C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1209,6 +1223,59 @@ class Screener:
                 rec = out[:n].copy()
                 return (ids[:2 * len(pool)].copy(), rec, fr, rf) if bits else (ids[:2 * len(pool)].copy(), rec)
             cap = int(n)                                                   # the count: one retry
+
+    def pool_products_end3(self, pool, threshold=1.0, tm_floor=0.0, min_clamp3=0, window=0, max_end_mismatch=0,
+                           use_taq_mama=False, ident_threshold=0.0, salt=0.05, primer_strand=9e-7,
+                           template_strand=0.0, thermo=True, amp_min=80, amp_max=200, which=TARGET,
+                           select=False, cap=None, bits=False):
+        """pool_products_tm under a 3'-end extension rule (pcr_pool_products_end3) -> (oligo_id uint32[2 * len(pool)], records:
+        PRODUCT_END3_DTYPE array in pool_products' order[, fr, rf], n_before_rule).
+
+        The first twelve fields of a record are pool_products_tm's.  clamp3_plus / clamp3_minus: how many slots match without
+        a break from the primer's 3' end at the plus / minus site; end_mismatch_*: the mismatching slots among the last
+        `window` slots; id_*: matches / length in float, with use_taq_mama times the TaqMAMA factor of the last two bases
+        (the score find_target_match tests).  A product past tm_floor is kept iff both sites have clamp3 >= min(min_clamp3,
+        length) and, with window > 0, end_mismatch <= max_end_mismatch, and (ident_threshold > 0) sqrt(id_plus * id_minus)
+        >= ident_threshold.  All zero keeps pool_products_tm's products.  n_before_rule counts the products past the floor
+        before the rule.  thermo=False melts nothing (both Tm 0, flags 0; tm_floor must be 0).  cap=None asks for the
+        count first, else as pool_products_tm's; `select` and `bits` as there.  anneal_profile, pool_conflicts and
+        probe_hits do not take the rule."""
+        thr2 = float(np.float32(threshold) * np.float32(threshold))
+        if isinstance(select, str):
+            if select != "all":
+                raise ValueError("pool_products_end3: select must be True, False or 'all'")
+            self.select_sites(pool, thr2, which=which)
+        elif select:
+            self.select_words(pool, thr2, which=which)
+        a = W.pairs_array(pool)
+        ids = np.zeros(max(2 * len(pool), 1), np.uint32)
+        args = self._targs(salt, primer_strand, 0.0, 0.0, 0.0, 0.0)
+        rule = End3Rule(int(min_clamp3), int(window), int(max_end_mismatch), int(use_taq_mama), float(ident_threshold))
+        words = int(self.bitset_words(which))
+        fr = np.zeros((len(pool), words), np.uint64) if bits else None
+        rf = np.zeros((len(pool), words), np.uint64) if bits else None
+        before = C.c_uint64(0)
+
+        def call(out, room):
+            n = self.L.pcr_pool_products_end3(self.h, which, a.ctypes.data, len(pool), float(threshold), int(amp_min), int(amp_max),
+                                              C.byref(args) if thermo else None, float(template_strand), float(tm_floor),
+                                              C.byref(rule), ids.ctypes.data, out.ctypes.data if out is not None else None, room,
+                                              fr.ctypes.data if bits else None, rf.ctypes.data if bits else None, C.byref(before))
+            if n < 0:
+                raise PcrError(_err(self.L))
+            return int(n)
+
+        counted = cap is None
+        if counted:
+            cap = call(None, 0)                                            # the count
+        while True:
+            out = np.zeros(max(cap, 1), PRODUCT_END3_DTYPE)
+            n = 0 if counted and cap == 0 else call(out, cap)              # (a count of 0 has written the rows already)
+            if n <= cap:
+                rec = out[:n].copy()
+                head = (ids[:2 * len(pool)].copy(), rec)
+                return head + ((fr, rf) if bits else ()) + (int(before.value),)
+            cap = n                                                        # the count: one retry
 
     def anneal_profile(self, pool, temps, threshold=1.0, salt=0.05, primer_strand=9e-7, template_strand=0.0,
                        amp_min=80, amp_max=200, which=TARGET, select=False, melt=False):

@@ -32,6 +32,7 @@
 //   k_rp_candidates, k_rp_weigh, k_rp_step : a greedy union of variants into each oligo, every (oligo, candidate) weighed by what its union holds (pcr_site_repair.inc)
 //   k_pool_dimer, k_pool_dimer_reduce : the same engine over every ordered oligo pair of a pool, jobs derived from the job number (pcr_pool_dimers.inc)
 //   k_item_tm, k_products_join : k_site_tm's Tm per item, and k_pool_join's geometry with the two sites' Tm, the floor and the pool's bit rows (pcr_products_tm.inc)
+//   k_item_end3, k_end3_join : the 3' end of every item's site (clamp, mismatches in a window, identity with the TaqMAMA factor), and k_products_join with a rule on the two sites' ends (pcr_products_end3.inc)
 //   k_anneal_join, k_anneal_rows : the same join without a floor: per (pool pair, sequence) the highest min-Tm by integer atomicMax, LDS histograms over an ascending temperature list (pcr_anneal_profile.inc)
 //   k_probe_products, k_probe_hits : the kept products of the primers compacted, then a wave per product over the probe items inside it (pcr_probe_hits.inc)
 //   k_amp_scan, k_amp_verify, k_amp_extract : eight lanes per product record over its bases: G+C, a hash of its spelling, equality with its group's first, the packed text (pcr_pool_amplicons.inc)
@@ -883,6 +884,10 @@ struct pcr_ctx {
 	// The one scratch set of pcr_pool_products_tm, pcr_pool_probe_hits, pcr_pool_anneal_profile and pcr_pool_conflicts: each call overwrites what the
 	// last one left.  pool_*, site_* and sv_* are apart: they keep their places above, and SvRun hands pointers into site_* / sv_* to pcr_site_repair.
 	ItemScratch shared;
+	// pcr_pool_products_end3 (pcr_products_end3.inc), beside `shared`: the 3' end of every item's site (an ItemEnd each, kept as uint2: the
+	// struct is that file's), the per-item counts before the rule, their sum and its scratch, the pool's bit rows, records, sort keys and order.
+	DevBuf<uint2> pe3_end; DevBuf<uint32_t> pe3_before, pe3_ord; DevBuf<uint64_t> pe3_sum, pe3_keys, pe3_bits; DevBuf<uint8_t> pe3_tmp;
+	DevBuf<pcr_product_end3> pe3_rec;
 };
 
 namespace {
@@ -2208,6 +2213,7 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_site_repair.inc"
 #include "pcr_pool_dimers.inc"
 #include "pcr_products_tm.inc"
+#include "pcr_products_end3.inc"
 #include "pcr_anneal_profile.inc"
 #include "pcr_pool_conflicts.inc"
 #include "pcr_probe_hits.inc"

@@ -21,6 +21,42 @@ namespace {
 struct ProductPair { uint32_t key, fr_row, rf_row, pad; };                      // key = plus*n_ol + minus -> the rows of the first pool pair (F, R) / (R, F) that it is
 constexpr uint32_t PTM_NO_ROW = 0xFFFFFFFFu;
 
+// What the join's bits need of a pool: the intended bitmap over (plus*n_ol + minus), and (plus, minus) -> the rows of the first pool
+// pair that is (F, R) = (plus, minus) / (R, F) = (plus, minus), in key order (tab: what the device bisects).  Host side only;
+// pcr_pool_products_end3 builds the same table.
+struct PairTable {
+	uint32_t n_ol;
+	std::vector<uint32_t> intended;
+	std::map<uint32_t, ProductPair> of;
+	std::vector<ProductPair> tab;
+	PairTable(const uint32_t *oligo_id, uint32_t n_pool, uint32_t n_oligos) : n_ol(n_oligos), intended(((size_t)n_oligos*n_oligos + 31)/32, 0)
+	{
+		for(uint32_t i = 0;i < n_pool;++i){
+			const uint32_t f = oligo_id[2*i], r = oligo_id[2*i + 1];
+			for(uint32_t b : {f*n_ol + r, r*n_ol + f}) intended[b >> 5] |= 1u << (b & 31);
+			for(int o = 0;o < 2;++o){
+				const uint32_t b = o ? r*n_ol + f : f*n_ol + r;
+				ProductPair fresh; fresh.key = b; fresh.fr_row = fresh.rf_row = PTM_NO_ROW; fresh.pad = 0;
+				ProductPair &pp = of.insert(std::make_pair(b, fresh)).first->second;
+				uint32_t &row = o ? pp.rf_row : pp.fr_row;
+				if(row == PTM_NO_ROW) row = i;
+			}
+		}
+		tab.reserve(of.size());
+		for(const auto &kv : of) tab.push_back(kv.second);                       // (key order)
+	}
+	// a pool pair that repeats an earlier one has that pair's rows (the device filled the first copy only)
+	void copy_repeated_rows(const uint32_t *oligo_id, uint32_t n_pool, uint32_t words, uint64_t *bits_fr, uint64_t *bits_rf)
+	{
+		for(uint32_t i = 0;i < n_pool && (bits_fr || bits_rf);++i){
+			const uint32_t f = oligo_id[2*i], r = oligo_id[2*i + 1];
+			const uint32_t fr_first = of[f*n_ol + r].fr_row, rf_first = of[r*n_ol + f].rf_row;
+			if(bits_fr && fr_first != i) memcpy(bits_fr + (size_t)i*words, bits_fr + (size_t)fr_first*words, words*sizeof(uint64_t));
+			if(bits_rf && rf_first != i) memcpy(bits_rf + (size_t)i*words, bits_rf + (size_t)rf_first*words, words*sizeof(uint64_t));
+		}
+	}
+};
+
 // k_pool_join with the two sites' Tm: one thread per item k, join_walk.  item_tm = NULL: no Tm is read and nothing is floored (the
 // plain count).  <false>: count[k], and with bits != NULL the bit of every kept product of a pool pair; <true>: records, (begin, end)
 // sort keys and identity indices at rec_off[k] ..
@@ -124,23 +160,9 @@ int64_t pcr_pool_products_tm(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, 
 	if(S.n_entries == 0 || S.n_touched == 0){ zero_rows(); return 0; }
 	const uint32_t n_ol = (uint32_t)ol.size();
 	const bool melt = tm_floor > 0.0f || cap > 0 || want_bits;                   // else: pcr_pool_products' count, no DP
-	// the intended bitmap, and (plus, minus) -> the rows of the first pool pair that is (F, R) = (plus, minus) / (R, F) = (plus, minus)
-	std::vector<uint32_t> intended(((size_t)n_ol*n_ol + 31)/32, 0);
-	std::map<uint32_t, ProductPair> tab_of;
-	for(uint32_t i = 0;i < n_pool;++i){
-		const uint32_t f = oligo_id[2*i], r = oligo_id[2*i + 1];
-		for(uint32_t b : {f*n_ol + r, r*n_ol + f}) intended[b >> 5] |= 1u << (b & 31);
-		for(int o = 0;o < 2;++o){
-			const uint32_t b = o ? r*n_ol + f : f*n_ol + r;
-			ProductPair fresh; fresh.key = b; fresh.fr_row = fresh.rf_row = PTM_NO_ROW; fresh.pad = 0;
-			ProductPair &pp = tab_of.insert(std::make_pair(b, fresh)).first->second;
-			uint32_t &row = o ? pp.rf_row : pp.fr_row;
-			if(row == PTM_NO_ROW) row = i;
-		}
-	}
-	std::vector<ProductPair> tab;
-	tab.reserve(tab_of.size());
-	for(const auto &kv : tab_of) tab.push_back(kv.second);                       // (key order)
+	PairTable pair_rows(oligo_id, n_pool, n_ol);
+	const std::vector<uint32_t> &intended = pair_rows.intended;
+	const std::vector<ProductPair> &tab = pair_rows.tab;
 	int rc;
 	const size_t ol_bytes = ol.size()*sizeof(PoolOligo), tab_bytes = tab.size()*sizeof(ProductPair), olx_bytes = olx.size()*sizeof(SiteOligoX),
 		int_bytes = intended.size()*sizeof(uint32_t);
@@ -190,13 +212,7 @@ int64_t pcr_pool_products_tm(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, 
 		return PCR_OK;
 	})) != PCR_OK) return rc;
 	if(bad & 1u){ g_err = "pcr_pool_products_tm: internal trace-back error"; return PCR_ERR_RANGE; }
-	// a pool pair that repeats an earlier one has that pair's rows (the device filled the first copy only)
-	for(uint32_t i = 0;i < n_pool && want_bits;++i){
-		const uint32_t f = oligo_id[2*i], r = oligo_id[2*i + 1];
-		const uint32_t fr_first = tab_of[f*n_ol + r].fr_row, rf_first = tab_of[r*n_ol + f].rf_row;
-		if(bits_fr && fr_first != i) memcpy(bits_fr + (size_t)i*words, bits_fr + (size_t)fr_first*words, words*sizeof(uint64_t));
-		if(bits_rf && rf_first != i) memcpy(bits_rf + (size_t)i*words, bits_rf + (size_t)rf_first*words, words*sizeof(uint64_t));
-	}
+	pair_rows.copy_repeated_rows(oligo_id, n_pool, words, bits_fr, bits_rf);
 	if(total >= POOL_MAX_ITEMS){ g_err = "pcr_pool_products_tm: too many products"; return PCR_ERR_CAPACITY; }
 	if(total == 0 || total > cap) return (int64_t)total;                         // count only: out is left as it is
 	// ---- 4'. emit at the scanned offsets; 5. the key order
