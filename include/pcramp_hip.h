@@ -824,8 +824,8 @@ typedef struct {
  * above 32; use_taq_mama neither 0 nor 1; ident_threshold not finite or outside [0, 1]; tm_floor > 0 without args; then a
  * null handle.  PCR_ERR_STATE, PCR_ERR_CAPACITY (also for 2^31 or more products before the rule) and PCR_ERR_RANGE as
  * pcr_pool_products_tm.  Changes nothing other calls read.  On a handle with a target shard attached, sequence indices are
- * local to the rank's block and no collective is made.  pcr_pool_anneal_profile, pcr_pool_conflicts and pcr_pool_probe_hits
- * do not take the rule. */
+ * local to the rank's block and no collective is made.  pcr_pool_anneal_profile_end3, pcr_pool_conflicts_end3 and
+ * pcr_pool_probe_hits_end3 apply the same rule inside their joins. */
 int64_t pcr_pool_products_end3(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
 	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args /* may be NULL */, float template_strand, float tm_floor,
 	const pcr_end3_rule *rule, uint32_t *oligo_id, pcr_product_end3 *out, uint64_t cap,
@@ -886,6 +886,26 @@ int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *poo
 	float *melt_fr, float *melt_rf,       /* n_pool x pcr_num_sequences(ctx, which) each; either may be NULL */
 	float *melt_spurious);                /* pcr_num_sequences(ctx, which); may be NULL */
 
+/* pcr_pool_anneal_profile over the products that pass a 3'-end rule: the product set is the one pcr_pool_products_end3 keeps
+ * for the same handle state, pool, threshold, amplicon range, args, template_strand and rule.
+ *   Rule.  The per-site quantities (clamp3, end_mismatch over the last min(window, length) slots, the identity score with or
+ * without the TaqMAMA factor) and the test (both sites, then ident_threshold == 0 or sqrtf(id_plus * id_minus) >=
+ * ident_threshold) are pcr_pool_products_end3's.  The rule does not depend on temperature: a product that fails it is absent
+ * from points, pair_sequences, cells, spurious_sequences and the three melt matrices at every temperature, and its cell stays
+ * PCR_ANNEAL_NO_PRODUCT unless another product fills it.  For every finite T, the rows of melt_fr / melt_rf with value >= T
+ * (all rows with a product where T <= 0) are bits_fr / bits_rf of pcr_pool_products_end3 at tm_floor = T with the same rule.
+ *   Returns the number of products that pass the rule with no floor, or a negative error.  rule = NULL or an all-zero rule:
+ * every output buffer and the return value are pcr_pool_anneal_profile's, byte for byte, and nothing is computed per site.
+ * args stays mandatory.
+ *   PCR_ERR_ARG, from the arguments alone and before the handle: pcr_pool_anneal_profile's checks in its order; then window,
+ * min_clamp3 or max_end_mismatch above 32; use_taq_mama neither 0 nor 1; ident_threshold not finite or outside [0, 1]; then a
+ * null handle.  PCR_ERR_STATE, PCR_ERR_CAPACITY and PCR_ERR_RANGE as pcr_pool_anneal_profile.  Changes nothing other calls
+ * read.  On a handle with a target shard attached, sequence indices are local to the rank's block and no collective is made. */
+int64_t pcr_pool_anneal_profile_end3(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, const pcr_end3_rule *rule,
+	const float *temps, uint32_t n_temps, uint32_t *oligo_id, pcr_anneal_point *points, uint32_t *pair_sequences,
+	float *melt_fr, float *melt_rf, float *melt_spurious);
+
 /* ---- Pool conflicts: which assays of a pool cannot share a tube */
 
 typedef struct {                          /* one unordered pair of pool rows (48 bytes) */
@@ -938,6 +958,23 @@ typedef struct {                          /* one unordered pair of pool rows (48
 int64_t pcr_pool_conflicts(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
 	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor,
 	int dimer_rule, float dimer_floor, uint32_t *oligo_id, pcr_pool_conflict *out, uint64_t cap);
+
+/* pcr_pool_conflicts over the products that pass a 3'-end rule: the products that take part are the spurious ones
+ * pcr_pool_products_end3 keeps for the same handle state, pool, threshold, amplicon range, args, template_strand, tm_floor
+ * and rule (its per-site quantities and its test, after the floor).  Only those are attributed; products, sequences, melt,
+ * melt_sequence and PCR_CONFLICT_PRODUCT follow from them, so two allele-specific assays whose only cross product cannot be
+ * extended no longer conflict.  The dimer half is untouched: dimer_tm, dimer_query, dimer_target and PCR_CONFLICT_DIMER are
+ * pcr_pool_conflicts' for the same arguments, and so is which cells a dimer rule keeps.
+ *   Returns the number of records or a negative error; cap and out as pcr_pool_conflicts.  rule = NULL or an all-zero rule:
+ * out and the return value are pcr_pool_conflicts', byte for byte, and nothing is computed per site.  args stays mandatory.
+ *   PCR_ERR_ARG, from the arguments alone and before the handle: pcr_pool_conflicts' checks in its order, the dimer ones
+ * included; then window, min_clamp3 or max_end_mismatch above 32; use_taq_mama neither 0 nor 1; ident_threshold not finite or
+ * outside [0, 1]; then a null handle.  PCR_ERR_STATE, PCR_ERR_CAPACITY and PCR_ERR_RANGE as pcr_pool_conflicts.  Changes
+ * nothing other calls read.  On a handle with a target shard attached, sequence indices are local to the rank's block and no
+ * collective is made. */
+int64_t pcr_pool_conflicts_end3(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor,
+	const pcr_end3_rule *rule, int dimer_rule, float dimer_floor, uint32_t *oligo_id, pcr_pool_conflict *out, uint64_t cap);
 
 /* ---- Probe hits: which products of a pool a panel's hydrolysis probes bind inside, and which sequences each assay detects */
 
@@ -999,6 +1036,24 @@ int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, c
 	float threshold, int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float probe_strand_conc, float template_strand,
 	float tm_floor, float probe_tm_floor, uint32_t *oligo_id, uint32_t *probe_id, pcr_probe_hit *out, uint64_t cap,
 	uint64_t *detected);
+
+/* pcr_pool_probe_hits inside the products that pass a 3'-end rule: the products are the ones pcr_pool_products_end3 keeps for
+ * the same handle state, pool, threshold, amplicon range, args, template_strand, tm_floor and rule (its per-site quantities
+ * and its test, after the floor).  The rule applies to the two primer sites of a product, never to the probe site: probe
+ * sites, probe_tm_floor and the hit condition are pcr_pool_probe_hits'.  Hits exist only inside products that pass the rule,
+ * and detected is reduced from those products: a row of a pair with a probe from their hits, a row of a pair without a probe
+ * is bits_fr | bits_rf of pcr_pool_products_end3 at the same tm_floor and rule.
+ *   Returns the number of hits or a negative error; cap, out and detected as pcr_pool_probe_hits.  rule = NULL or an
+ * all-zero rule: out, detected and the return value are pcr_pool_probe_hits', byte for byte, and nothing is computed per
+ * site.  args stays mandatory.
+ *   PCR_ERR_ARG, from the arguments alone and before the handle: pcr_pool_probe_hits' checks in its order; then window,
+ * min_clamp3 or max_end_mismatch above 32; use_taq_mama neither 0 nor 1; ident_threshold not finite or outside [0, 1]; then a
+ * null handle.  PCR_ERR_STATE, PCR_ERR_CAPACITY and PCR_ERR_RANGE as pcr_pool_probe_hits.  Changes nothing other calls read.
+ * On a handle with a target shard attached, sequence indices are local to the rank's block and no collective is made. */
+int64_t pcr_pool_probe_hits_end3(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, const pcr_word128 *probes, uint32_t n_pool,
+	float threshold, int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float probe_strand_conc, float template_strand,
+	float tm_floor, float probe_tm_floor, const pcr_end3_rule *rule, uint32_t *oligo_id, uint32_t *probe_id, pcr_probe_hit *out,
+	uint64_t cap, uint64_t *detected);
 
 /* ---- Amplicons: the bases of products, their length and G+C, and which records spell one and the same amplicon */
 

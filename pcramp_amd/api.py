@@ -203,7 +203,8 @@ ABI_SYMBOLS = [
     "pcr_thermo", "pcr_valid_words", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers",
-    "pcr_pool_products_tm", "pcr_pool_products_end3", "pcr_pool_anneal_profile", "pcr_pool_conflicts", "pcr_pool_probe_hits", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants", "pcr_site_repair",
+    "pcr_pool_products_tm", "pcr_pool_products_end3", "pcr_pool_anneal_profile", "pcr_pool_conflicts", "pcr_pool_probe_hits",
+    "pcr_pool_anneal_profile_end3", "pcr_pool_conflicts_end3", "pcr_pool_probe_hits_end3", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants", "pcr_site_repair",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats", "pcr_live_resources",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -315,13 +316,24 @@ def load_library():
     L.pcr_pool_anneal_profile.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
                                           C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]
+    L.pcr_pool_anneal_profile_end3.restype = C.c_int64
+    L.pcr_pool_anneal_profile_end3.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32,
+                                               C.POINTER(ThermoArgs), C.c_float, C.POINTER(End3Rule), C.c_void_p, C.c_uint32, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcr_pool_conflicts.restype = C.c_int64
     L.pcr_pool_conflicts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
                                      C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.pcr_pool_conflicts_end3.restype = C.c_int64
+    L.pcr_pool_conflicts_end3.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
+                                          C.c_float, C.c_float, C.POINTER(End3Rule), C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64]
     L.pcr_pool_probe_hits.restype = C.c_int64
     L.pcr_pool_probe_hits.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32,
                                       C.POINTER(ThermoArgs), C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_uint64, C.c_void_p]
+    L.pcr_pool_probe_hits_end3.restype = C.c_int64
+    L.pcr_pool_probe_hits_end3.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32,
+                                           C.POINTER(ThermoArgs), C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(End3Rule),
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.pcr_pool_amplicons.restype = C.c_int64
     L.pcr_pool_amplicons.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -606,6 +618,14 @@ def bits_to_bool(words, n):
     w = np.ascontiguousarray(words, dtype=np.uint64)
     b = np.unpackbits(w.view(np.uint8), bitorder="little")
     return b[:n].astype(bool)
+
+
+def _end3_rule(min_clamp3, window, max_end_mismatch, use_taq_mama, ident_threshold):
+    """The five rule keywords of anneal_profile, pool_conflicts and probe_hits -> an End3Rule, or None when all are at their
+    defaults (the wrapper then calls the entry point without a rule, as before the keywords existed)."""
+    if not (min_clamp3 or window or max_end_mismatch or use_taq_mama or ident_threshold):
+        return None
+    return End3Rule(int(min_clamp3), int(window), int(max_end_mismatch), int(use_taq_mama), float(ident_threshold))
 
 
 def melt_to_bits(melt, tm_floor):
@@ -1239,7 +1259,7 @@ class Screener:
         >= ident_threshold.  All zero keeps pool_products_tm's products.  n_before_rule counts the products past the floor
         before the rule.  thermo=False melts nothing (both Tm 0, flags 0; tm_floor must be 0).  cap=None asks for the
         count first, else as pool_products_tm's; `select` and `bits` as there.  anneal_profile, pool_conflicts and
-        probe_hits do not take the rule."""
+        probe_hits take the same five rule keywords."""
         thr2 = float(np.float32(threshold) * np.float32(threshold))
         if isinstance(select, str):
             if select != "all":
@@ -1278,7 +1298,8 @@ class Screener:
             cap = n                                                        # the count: one retry
 
     def anneal_profile(self, pool, temps, threshold=1.0, salt=0.05, primer_strand=9e-7, template_strand=0.0,
-                       amp_min=80, amp_max=200, which=TARGET, select=False, melt=False):
+                       amp_min=80, amp_max=200, which=TARGET, select=False, melt=False, min_clamp3=0, window=0,
+                       max_end_mismatch=0, use_taq_mama=False, ident_threshold=0.0):
         """What the pool amplifies at every temperature of an annealing gradient (pcr_pool_anneal_profile) -> (oligo_id uint32
         [2 * len(pool)], points: ANNEAL_POINT_DTYPE array of len(temps), pair_sequences uint32 [len(pool), len(temps)]), and
         with melt=True also (melt_fr, melt_rf, melt_spurious): float32 [len(pool), n_seq], [len(pool), n_seq] and [n_seq].
@@ -1288,7 +1309,10 @@ class Screener:
         there (the population of pool_products_tm's fr[i] | rf[i]).  melt_fr[i][s] is the highest min(tm_plus, tm_minus) of
         the products of (F_i, R_i) on sequence s, ANNEAL_NO_PRODUCT where there is none: melt_to_bits(melt_fr, T) is
         pool_products_tm's fr at the floor T, for any T.  melt_spurious[s] is the same over the products on s that are no
-        pool pair's.  The sites are melted once and joined once, whatever len(temps).  `select` as for pool_products_tm."""
+        pool pair's.  The sites are melted once and joined once, whatever len(temps).  `select` as for pool_products_tm.
+        min_clamp3, window, max_end_mismatch, use_taq_mama and ident_threshold are pool_products_end3's 3'-end rule
+        (pcr_pool_anneal_profile_end3): with any of them set, every count and matrix is over the products that pass it, and
+        melt_to_bits(melt_fr, T) is pool_products_end3's fr at the floor T under the same rule."""
         thr2 = float(np.float32(threshold) * np.float32(threshold))
         if isinstance(select, str):
             if select != "all":
@@ -1306,17 +1330,22 @@ class Screener:
         fr = np.zeros((len(pool), n_seq), np.float32) if melt else None
         rf = np.zeros((len(pool), n_seq), np.float32) if melt else None
         sp = np.zeros(n_seq, np.float32) if melt else None
-        n = self.L.pcr_pool_anneal_profile(self.h, which, a.ctypes.data, len(pool), float(threshold), int(amp_min), int(amp_max),
-                                           C.byref(args), float(template_strand), t.ctypes.data, len(t), ids.ctypes.data,
-                                           points.ctypes.data, pair_seq.ctypes.data, fr.ctypes.data if melt else None,
-                                           rf.ctypes.data if melt else None, sp.ctypes.data if melt else None)
+        head = (self.h, which, a.ctypes.data, len(pool), float(threshold), int(amp_min), int(amp_max), C.byref(args), float(template_strand))
+        tail = (t.ctypes.data, len(t), ids.ctypes.data, points.ctypes.data, pair_seq.ctypes.data, fr.ctypes.data if melt else None,
+                rf.ctypes.data if melt else None, sp.ctypes.data if melt else None)
+        rule = _end3_rule(min_clamp3, window, max_end_mismatch, use_taq_mama, ident_threshold)
+        if rule is None:
+            n = self.L.pcr_pool_anneal_profile(*head, *tail)
+        else:
+            n = self.L.pcr_pool_anneal_profile_end3(*head, C.byref(rule), *tail)
         if n < 0:
             raise PcrError(_err(self.L))
         out = (ids[:2 * len(pool)].copy(), points[:len(t)].copy(), pair_seq)
         return out + (fr, rf, sp) if melt else out
 
     def pool_conflicts(self, pool, threshold=1.0, tm_floor=0.0, salt=0.05, primer_strand=9e-7, template_strand=0.0,
-                       amp_min=80, amp_max=200, dimers="pool", dimer_floor=0.0, which=TARGET, select=False, cap=None):
+                       amp_min=80, amp_max=200, dimers="pool", dimer_floor=0.0, which=TARGET, select=False, cap=None,
+                       min_clamp3=0, window=0, max_end_mismatch=0, use_taq_mama=False, ident_threshold=0.0):
         """Which assays of the pool cannot share a tube (pcr_pool_conflicts) -> (oligo_id uint32[2 * len(pool)], conflicts:
         POOL_CONFLICT_DTYPE array sorted by (row_a, row_b)).
 
@@ -1328,7 +1357,10 @@ class Screener:
         (dimer_query, dimer_target); with "pool", multiplex_compatible holds for the two assays in both orders iff dimer_tm <
         max_dimer.  dimers=None runs no dimer thermodynamics.  Records: the cells with a product, and with dimers those with
         dimer_tm >= dimer_floor (dimer_floor <= 0: every cell).  `select` as for pool_products_tm.  conflict_matrix and
-        assign_tubes turn the records into a split of the pool."""
+        assign_tubes turn the records into a split of the pool.  min_clamp3, window, max_end_mismatch, use_taq_mama and
+        ident_threshold are pool_products_end3's 3'-end rule (pcr_pool_conflicts_end3): with any of them set, only spurious
+        products that also pass it are attributed -- a cross product the polymerase does not extend is no conflict.  The
+        dimer fields do not depend on the rule."""
         rules = {"pool": DIMER_RULE_POOL, "assay": DIMER_RULE_ASSAY, None: CONFLICT_NO_DIMERS, DIMER_RULE_POOL: DIMER_RULE_POOL,
                  DIMER_RULE_ASSAY: DIMER_RULE_ASSAY, CONFLICT_NO_DIMERS: CONFLICT_NO_DIMERS}
         if dimers not in rules:
@@ -1343,9 +1375,14 @@ class Screener:
         a = W.pairs_array(pool)
         ids = np.zeros(max(2 * len(pool), 1), np.uint32)
         args = self._targs(salt, primer_strand, 0.0, 0.0, 0.0, 0.0)
-        call = lambda out, cap: self.L.pcr_pool_conflicts(self.h, which, a.ctypes.data, len(pool), float(threshold), int(amp_min),
-                                                          int(amp_max), C.byref(args), float(template_strand), float(tm_floor),
-                                                          rules[dimers], float(dimer_floor), ids.ctypes.data, out, cap)
+        head = (self.h, which, a.ctypes.data, len(pool), float(threshold), int(amp_min), int(amp_max), C.byref(args), float(template_strand),
+                float(tm_floor))
+        rule = _end3_rule(min_clamp3, window, max_end_mismatch, use_taq_mama, ident_threshold)
+        if rule is None:
+            call = lambda out, cap: self.L.pcr_pool_conflicts(*head, rules[dimers], float(dimer_floor), ids.ctypes.data, out, cap)
+        else:
+            call = lambda out, cap: self.L.pcr_pool_conflicts_end3(*head, C.byref(rule), rules[dimers], float(dimer_floor),
+                                                                   ids.ctypes.data, out, cap)
         if cap is None:                                                    # the count sizes the buffer
             n = call(None, 0)
             if n < 0:
@@ -1362,7 +1399,8 @@ class Screener:
 
     def probe_hits(self, pool, probes, threshold=1.0, tm_floor=0.0, probe_tm_floor=0.0, salt=0.05, primer_strand=9e-7,
                    probe_strand=2.5e-7, template_strand=0.0, amp_min=80, amp_max=200, which=TARGET, select=False,
-                   bits=False, cap=1 << 16):
+                   bits=False, cap=1 << 16, min_clamp3=0, window=0, max_end_mismatch=0, use_taq_mama=False,
+                   ident_threshold=0.0):
         """Which products of the pool a probe binds inside (pcr_pool_probe_hits) -> (oligo_id uint32[2 * len(pool)], probe_id
         uint32[len(pool)], records: PROBE_HIT_DTYPE array sorted by (plus_oligo, minus_oligo, sequence, begin, end, probe,
         probe_loc5, probe_strand)), and with bits=True also detected: uint64 [len(pool), bitset_words], pcr_amplify's layout.
@@ -1375,7 +1413,10 @@ class Screener:
         is that pair's.  detected[i]: the sequences on which pair i's primers (either orientation) form a kept product with
         pair i's probe inside; for a pair without a probe, the sequences its primers amplify (pool_products_tm's fr | rf).
         `select`: "all" first runs select_sites over the pool plus (P, P) per distinct probe -- the DB must hold the probes'
-        sites --, True the same with select_words (both REPLACE the set's word DB), False reads the DB as it stands."""
+        sites --, True the same with select_words (both REPLACE the set's word DB), False reads the DB as it stands.
+        min_clamp3, window, max_end_mismatch, use_taq_mama and ident_threshold are pool_products_end3's 3'-end rule
+        (pcr_pool_probe_hits_end3): with any of them set, the products are pool_products_end3's under that rule.  The rule
+        looks at the two primer sites, never at the probe site."""
         if len(probes) != len(pool):
             raise ValueError("probe_hits: one probe entry (or None) per pool pair")
         pr = np.zeros((max(len(pool), 1), 2), np.uint64)
@@ -1394,12 +1435,16 @@ class Screener:
         pid = np.zeros(max(len(pool), 1), np.uint32)
         args = self._targs(salt, primer_strand, 0.0, 0.0, 0.0, 0.0)
         detected = np.zeros((len(pool), int(self.bitset_words(which))), np.uint64) if bits else None
+        head = (self.h, which, a.ctypes.data, pr.ctypes.data, len(pool), float(threshold), int(amp_min), int(amp_max), C.byref(args),
+                float(probe_strand), float(template_strand), float(tm_floor), float(probe_tm_floor))
+        rule = _end3_rule(min_clamp3, window, max_end_mismatch, use_taq_mama, ident_threshold)
         while True:
             out = np.zeros(max(cap, 1), PROBE_HIT_DTYPE)
-            n = self.L.pcr_pool_probe_hits(self.h, which, a.ctypes.data, pr.ctypes.data, len(pool), float(threshold), int(amp_min),
-                                           int(amp_max), C.byref(args), float(probe_strand), float(template_strand), float(tm_floor),
-                                           float(probe_tm_floor), ids.ctypes.data, pid.ctypes.data, out.ctypes.data, cap,
-                                           detected.ctypes.data if bits else None)
+            tail = (ids.ctypes.data, pid.ctypes.data, out.ctypes.data, cap, detected.ctypes.data if bits else None)
+            if rule is None:
+                n = self.L.pcr_pool_probe_hits(*head, *tail)
+            else:
+                n = self.L.pcr_pool_probe_hits_end3(*head, C.byref(rule), *tail)
             if n < 0:
                 raise PcrError(_err(self.L))
             if n <= cap:

@@ -19,6 +19,8 @@
 //      spurious_sequences[t].
 //   6. The host turns hist into the points' product counts (products at t = sum of hist[.][u] over u > t).
 // The number of launches and copies does not depend on n_temps.  Steps 1-3 work in pcr_ctx::shared, the rest in pcr_ctx::anp_*.
+// pcr_pool_anneal_profile_end3 is the same call over the products that pass a 3'-end rule (pcr_products_end3.inc, included before
+// this file): k_item_end3 fills an ItemEnd per item before the melt, and the join's functor makes k_end3_join's tests.
 
 namespace {
 
@@ -40,8 +42,10 @@ __device__ __forceinline__ uint32_t anneal_prefix(const float *ts, uint32_t n, f
 }
 
 // k_products_join<false> without a floor: one thread per item k, join_walk.  Every product: hist[intended][u], and its cell of
-// `melt` (intended: the row of its key) or of the last row (spurious) raised to v.
-__global__ __launch_bounds__(POOL_THREADS) void k_anneal_join(const JoinIn J, const ItemTm *__restrict__ item_tm, const uint32_t *__restrict__ intended,
+// `melt` (intended: the row of its key) or of the last row (spurious) raised to v.  item_end != NULL: only the products that pass
+// the 3'-end rule R (k_end3_join's tests; the rule knows no temperature, so a product that fails it is absent at every one).
+__global__ __launch_bounds__(POOL_THREADS) void k_anneal_join(const JoinIn J, const ItemTm *__restrict__ item_tm, const ItemEnd *__restrict__ item_end,
+	const End3Rule R, const uint32_t *__restrict__ intended,
 	const uint32_t *__restrict__ key_tab, uint32_t n_tab, const float *__restrict__ temps, uint32_t n_temps, int *__restrict__ melt, uint32_t n_seq,
 	unsigned long long *__restrict__ out)
 {
@@ -59,7 +63,13 @@ __global__ __launch_bounds__(POOL_THREADS) void k_anneal_join(const JoinIn J, co
 		const DevEntry ei = J.db[i];
 		if(ei.strand == 1){
 			const ItemTm tp = item_tm[k];
-			join_walk<false>(J, ss, g, x, i, ei, 0u, [&](uint64_t t, uint32_t y, uint32_t, int32_t, int32_t, int32_t, int32_t){
+			ItemEnd ep; ep.clamp3 = ep.end_mismatch = ep.length = ep.pad = 0; ep.id = 0.0f;
+			if(item_end) ep = item_end[k];
+			const bool plus_ok = !item_end || end3_site_ok(ep, R);
+			// (a plus site that fails its own half of the rule keeps no product: it walks nothing)
+			if(plus_ok) join_walk<false>(J, ss, g, x, i, ei, 0u, [&](uint64_t t, uint32_t y, uint32_t, int32_t, int32_t, int32_t, int32_t){
+				ItemEnd em;
+				if(item_end && !end3_product_ok(item_end, R, plus_ok, ep, t, em)) return;
 				const ItemTm tm = item_tm[t];
 				const float v = ((tp.tm < tm.tm) ? tp.tm : tm.tm) + 0.0f;            // k_products_join's min; + 0.0f: -0 -> +0 (contraction is off)
 				const uint32_t u = anneal_prefix(ts, n_temps, v);
@@ -119,37 +129,38 @@ __global__ __launch_bounds__(ANP_ROW_THREADS) void k_anneal_rows(const int *__re
 	}
 }
 
-} // namespace
-
-extern "C" {
-
-int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
-	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand,
+// pcr_pool_anneal_profile (rule = NULL) and pcr_pool_anneal_profile_end3; who: the entry point's name, for the refusals
+int64_t anneal_profile_impl(const std::string &who, pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, const pcr_end3_rule *rule,
 	const float *temps, uint32_t n_temps, uint32_t *oligo_id, pcr_anneal_point *points, uint32_t *pair_sequences,
 	float *melt_fr, float *melt_rf, float *melt_spurious)
 {
 	static_assert(sizeof(pcr_anneal_point) == 40, "record layout");
 	static_assert(sizeof(PoolOligo) == 32 && sizeof(SiteOligoX) == 8, "table layout");
 	// ---- the arguments, before the handle (pcr_pool_products_tm's checks in its order, the oligo table, then the temperatures)
-	if(!set_ok(which)){ g_err = "pcr_pool_anneal_profile: unknown sequence set"; return PCR_ERR_ARG; }
-	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = "pcr_pool_anneal_profile: PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
-	if(!args || !temps || !points || (n_pool && (!pool || !oligo_id))){ g_err = "pcr_pool_anneal_profile: bad argument"; return PCR_ERR_ARG; }
-	if(n_pool > PCR_POOL_MAX_PAIRS){ g_err = "pcr_pool_anneal_profile: pool larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
-	if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f)){ g_err = "pcr_pool_anneal_profile: negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
-	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = "pcr_pool_anneal_profile: salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
+	if(!set_ok(which)){ g_err = who + ": unknown sequence set"; return PCR_ERR_ARG; }
+	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = who + ": PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
+	if(!args || !temps || !points || (n_pool && (!pool || !oligo_id))){ g_err = who + ": bad argument"; return PCR_ERR_ARG; }
+	if(n_pool > PCR_POOL_MAX_PAIRS){ g_err = who + ": pool larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
+	if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f)){ g_err = who + ": negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
+	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = who + ": salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
 	std::vector<PoolOligo> ol;
 	std::vector<SiteOligoX> olx;
-	if(site_oligo_table("pcr_pool_anneal_profile", "an oligo", "primer_strand", pool, n_pool, threshold, args, template_strand, oligo_id, ol, olx) != PCR_OK) return PCR_ERR_ARG;
-	if(n_temps == 0 || n_temps > PCR_ANNEAL_MAX_TEMPS){ g_err = "pcr_pool_anneal_profile: n_temps is 0 or larger than PCR_ANNEAL_MAX_TEMPS"; return PCR_ERR_ARG; }
+	if(site_oligo_table(who, "an oligo", "primer_strand", pool, n_pool, threshold, args, template_strand, oligo_id, ol, olx) != PCR_OK) return PCR_ERR_ARG;
+	if(n_temps == 0 || n_temps > PCR_ANNEAL_MAX_TEMPS){ g_err = who + ": n_temps is 0 or larger than PCR_ANNEAL_MAX_TEMPS"; return PCR_ERR_ARG; }
 	for(uint32_t t = 0;t < n_temps;++t){
-		if(!std::isfinite(temps[t])){ g_err = "pcr_pool_anneal_profile: a temperature is not finite"; return PCR_ERR_ARG; }
-		if(t && !(temps[t] > temps[t - 1])){ g_err = "pcr_pool_anneal_profile: temps is not strictly ascending"; return PCR_ERR_ARG; }
+		if(!std::isfinite(temps[t])){ g_err = who + ": a temperature is not finite"; return PCR_ERR_ARG; }
+		if(t && !(temps[t] > temps[t - 1])){ g_err = who + ": temps is not strictly ascending"; return PCR_ERR_ARG; }
 	}
-	if(!ctx){ g_err = "pcr_pool_anneal_profile: null handle"; return PCR_ERR_ARG; }
+	End3Rule R;
+	int use_taq;
+	if(end3_rule_of(who, rule, R, use_taq) != PCR_OK) return PCR_ERR_ARG;
+	const bool ruled = end3_ruled(R);                                            // else: no ItemEnd is computed, the join is the base call's
+	if(!ctx){ g_err = who + ": null handle"; return PCR_ERR_ARG; }
 	{ const int drc = drain(ctx); if(drc != PCR_OK) return drc; }
 	HIP_TRY(hipSetDevice(ctx->device));
 	SeqSet &S = ctx->sets[which];
-	if(!S.have_db){ g_err = "pcr_pool_anneal_profile: no word DB (call pcr_select_words or pcr_select_sites first)"; return PCR_ERR_STATE; }
+	if(!S.have_db){ g_err = who + ": no word DB (call pcr_select_words or pcr_select_sites first)"; return PCR_ERR_STATE; }
 	const size_t n_seq = S.n;
 	// whatever the count, everything asked for is written in full: no product anywhere
 	auto write_empty = [&](){
@@ -189,19 +200,22 @@ int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *poo
 		const size_t have = free_b + ctx->anp_melt.cap*sizeof(float);             // (ensure gives the old buffer back first)
 		const size_t headroom = size_t(256) << 20;
 		if(have < headroom || melt_elems*sizeof(float) > have - headroom){
-			g_err = "pcr_pool_anneal_profile: the melt rows of the pool's distinct (F, R) would not fit in device memory"; return PCR_ERR_CAPACITY;
+			g_err = who + ": the melt rows of the pool's distinct (F, R) would not fit in device memory"; return PCR_ERR_CAPACITY;
 		}
 	}
 	if((rc = ctx->anp_melt.ensure(melt_elems)) != PCR_OK) return rc;
 	const size_t ol_bytes = ol.size()*sizeof(PoolOligo), olx_bytes = olx.size()*sizeof(SiteOligoX), map_bytes = row_map.size()*sizeof(uint2),
 		tab_bytes = key_tab.size()*sizeof(uint32_t), int_bytes = intended.size()*sizeof(uint32_t), temp_bytes = (size_t)n_temps*sizeof(float);
-	std::vector<uint8_t> blob(ol_bytes + olx_bytes + map_bytes + tab_bytes + int_bytes + temp_bytes);   // 32-, 8-, 8-, 4-, 4- and 4-byte records, in that order: each is aligned
+	const std::vector<float> norm = ruled ? end3_norms(ol) : std::vector<float>();   // (k_item_end3's; only a rule reads it)
+	const size_t norm_bytes = norm.size()*sizeof(float);
+	std::vector<uint8_t> blob(ol_bytes + olx_bytes + map_bytes + tab_bytes + int_bytes + temp_bytes + norm_bytes);   // 32-, 8-, 8-, 4-, 4-, 4- and 4-byte records, in that order: each is aligned
 	memcpy(blob.data(), ol.data(), ol_bytes);
 	memcpy(blob.data() + ol_bytes, olx.data(), olx_bytes);
 	memcpy(blob.data() + ol_bytes + olx_bytes, row_map.data(), map_bytes);
 	memcpy(blob.data() + ol_bytes + olx_bytes + map_bytes, key_tab.data(), tab_bytes);
 	memcpy(blob.data() + ol_bytes + olx_bytes + map_bytes + tab_bytes, intended.data(), int_bytes);
 	memcpy(blob.data() + ol_bytes + olx_bytes + map_bytes + tab_bytes + int_bytes, temps, temp_bytes);
+	if(norm_bytes) memcpy(blob.data() + ol_bytes + olx_bytes + map_bytes + tab_bytes + int_bytes + temp_bytes, norm.data(), norm_bytes);
 	ItemScratch &X = ctx->shared;
 	const ItemBufs B = X.bufs();
 	if((rc = X.in.ensure(blob.size())) != PCR_OK) return rc;
@@ -211,18 +225,22 @@ int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *poo
 	const uint32_t *d_tab = (const uint32_t *)(X.in.p + ol_bytes + olx_bytes + map_bytes);
 	const uint32_t *d_intended = (const uint32_t *)(X.in.p + ol_bytes + olx_bytes + map_bytes + tab_bytes);
 	const float *d_temps = (const float *)(X.in.p + ol_bytes + olx_bytes + map_bytes + tab_bytes + int_bytes);
+	const float *d_norm = (const float *)(X.in.p + ol_bytes + olx_bytes + map_bytes + tab_bytes + int_bytes + temp_bytes);
 	HIP_TRY(hipMemcpyAsync(X.in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
 	// ---- 1. the items (item_count waits: blob is read by then)
 	uint64_t n_items = 0;
 	if((rc = item_count(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
-	if(n_items >= POOL_MAX_ITEMS){ g_err = "pcr_pool_anneal_profile: too many (entry, oligo) hits"; return PCR_ERR_CAPACITY; }
+	if(n_items >= POOL_MAX_ITEMS){ g_err = who + ": too many (entry, oligo) hits"; return PCR_ERR_CAPACITY; }
 	if(n_items == 0){ write_empty(); return 0; }
 	if((rc = item_fill(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
 	const uint32_t ni = (uint32_t)n_items;
 	const unsigned grid_i = (ni + POOL_THREADS - 1)/POOL_THREADS;
 	if((rc = X.cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;                // (the entry counts are spent)
+	// ---- with a rule: the 3' end per item (pcr_pool_products_end3's step 2)
+	const ItemEnd *d_item_end = nullptr;
+	if(ruled && (rc = end3_items(ctx, S, ni, d_ol, d_norm, R.window, use_taq, d_item_end)) != PCR_OK) return rc;
 	// ---- 2. job offsets, the jobs; 3. Tm per item
-	if((rc = melt_items("pcr_pool_anneal_profile", ctx, S, d_ol, d_olx, ni, args->salt, B)) != PCR_OK) return rc;
+	if((rc = melt_items(who, ctx, S, d_ol, d_olx, ni, args->salt, B)) != PCR_OK) return rc;
 	// ---- 4. the join: histograms and melt rows
 	if((rc = ctx->anp_out.ensure(ANP_OUT_WORDS)) != PCR_OK) return rc;
 	if((rc = ctx->anp_pairseq.ensure((size_t)n_pool*n_temps)) != PCR_OK) return rc;
@@ -230,7 +248,7 @@ int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *poo
 	HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ctx->anp_melt.p, (int)0xBF800000u, melt_elems, ctx->stream));   // -1.0f
 	const JoinIn J{S.db.p, S.db_cap, S.touched.p, S.d_seg_hi, X.items.p, ni, X.eoff.p, d_ol, n_ol, S.planes.p, S.d_blk_off.p, S.d_len.p,
 		S.d_has_eos.p, amp_min, amp_max};
-	hipLaunchKernelGGL(k_anneal_join, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, (const ItemTm *)X.item_tm.p, d_intended, d_tab, n_tab,
+	hipLaunchKernelGGL(k_anneal_join, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, (const ItemTm *)X.item_tm.p, d_item_end, R, d_intended, d_tab, n_tab,
 		d_temps, n_temps, (int *)ctx->anp_melt.p, (uint32_t)n_seq, (unsigned long long *)ctx->anp_out.p);
 	HIP_TRY(hipGetLastError());
 	// ---- 5. the rows' histograms
@@ -250,10 +268,10 @@ int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *poo
 	}
 	else if(melt_spurious) HIP_TRY(hipMemcpyAsync(melt_spurious, ctx->anp_melt.p + (size_t)n_tab*n_seq, n_seq*sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
-	if(bad & 1u){ g_err = "pcr_pool_anneal_profile: internal trace-back error"; return PCR_ERR_RANGE; }
+	if(bad & 1u){ g_err = who + ": internal trace-back error"; return PCR_ERR_RANGE; }
 	uint64_t total = 0;
 	for(uint32_t b = 0;b < 2*ANP_BINS;++b) total += small[b];
-	if(total >= POOL_MAX_ITEMS){ g_err = "pcr_pool_anneal_profile: too many products"; return PCR_ERR_CAPACITY; }
+	if(total >= POOL_MAX_ITEMS){ g_err = who + ": too many products"; return PCR_ERR_CAPACITY; }
 	// ---- 6. the points: a product with u kept temperatures counts at every t < u
 	uint64_t kept[2] = {0, 0};
 	for(uint32_t t = n_temps;t-- > 0;){
@@ -272,6 +290,28 @@ int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *poo
 		if(melt_spurious) memcpy(melt_spurious, host_melt.data() + (size_t)n_tab*n_seq, n_seq*sizeof(float));
 	}
 	return (int64_t)total;
+}
+
+} // namespace
+
+extern "C" {
+
+int64_t pcr_pool_anneal_profile(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand,
+	const float *temps, uint32_t n_temps, uint32_t *oligo_id, pcr_anneal_point *points, uint32_t *pair_sequences,
+	float *melt_fr, float *melt_rf, float *melt_spurious)
+{
+	return anneal_profile_impl("pcr_pool_anneal_profile", ctx, which, pool, n_pool, threshold, amp_min, amp_max, args, template_strand, nullptr,
+		temps, n_temps, oligo_id, points, pair_sequences, melt_fr, melt_rf, melt_spurious);
+}
+
+int64_t pcr_pool_anneal_profile_end3(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, const pcr_end3_rule *rule,
+	const float *temps, uint32_t n_temps, uint32_t *oligo_id, pcr_anneal_point *points, uint32_t *pair_sequences,
+	float *melt_fr, float *melt_rf, float *melt_spurious)
+{
+	return anneal_profile_impl("pcr_pool_anneal_profile_end3", ctx, which, pool, n_pool, threshold, amp_min, amp_max, args, template_strand, rule,
+		temps, n_temps, oligo_id, points, pair_sequences, melt_fr, melt_rf, melt_spurious);
 }
 
 } // extern "C"

@@ -20,6 +20,9 @@
 //      the lowest (q, t) on a tie, and sets the flags and the keep word; an exclusive scan and k_conflict_compact put the kept
 //      cells into (row_a, row_b) order.
 // Steps 1-4 work in pcr_ctx::shared (its flag holds two words here), the rest in pcr_ctx::pcf_*; the dG table is the handle's (th_dg, keyed by its salt).
+// pcr_pool_conflicts_end3 is the same call with a 3'-end rule (pcr_products_end3.inc, included before this file) on the products
+// of steps 1-6: k_item_end3 fills an ItemEnd per item before the melt, and the join's functor makes k_end3_join's tests behind
+// the floor.  Steps 7 and 8 do not know the rule.
 
 #include <rocprim/device/device_reduce_by_key.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -65,10 +68,11 @@ struct PcfMerge {
 };
 
 // k_products_join with the floor, over the spurious kept products only: one thread per item k, join_walk.  Every attribution of a
-// product to a cell: <false> counts it, <true> writes its key and the bits of v at att_off[k] ..
+// product to a cell: <false> counts it, <true> writes its key and the bits of v at att_off[k] ..  item_end != NULL: only the
+// products that also pass the 3'-end rule R (k_end3_join's tests, after the floor).
 template<bool EMIT>
 __global__ __launch_bounds__(POOL_THREADS) void k_conflict_join(const JoinIn J, const ItemTm *__restrict__ item_tm, float tm_floor,
-	const uint32_t *__restrict__ intended, const uint32_t *__restrict__ rows_off, const uint32_t *__restrict__ rows, const uint2 *__restrict__ row_ol,
+	const ItemEnd *__restrict__ item_end, const End3Rule R, const uint32_t *__restrict__ intended, const uint32_t *__restrict__ rows_off, const uint32_t *__restrict__ rows, const uint2 *__restrict__ row_ol,
 	uint32_t n_pool, uint32_t seq_bits, uint32_t *__restrict__ count, const uint64_t *__restrict__ att_off, uint64_t *__restrict__ key,
 	uint32_t *__restrict__ val)
 {
@@ -86,12 +90,17 @@ __global__ __launch_bounds__(POOL_THREADS) void k_conflict_join(const JoinIn J, 
 		const ItemTm tp = item_tm[k];
 		const bool floored = tm_floor > 0.0f;
 		const uint32_t x0 = rows_off[x], x1 = rows_off[x + 1];
+		ItemEnd ep; ep.clamp3 = ep.end_mismatch = ep.length = ep.pad = 0; ep.id = 0.0f;
+		if(item_end) ep = item_end[k];
+		const bool plus_ok = !item_end || end3_site_ok(ep, R);
 		auto keep = [&](uint64_t t, uint32_t y, uint32_t, int32_t, int32_t, int32_t, int32_t){
 			const uint32_t b = x*J.n_ol + y;
 			if((intended[b >> 5] >> (b & 31)) & 1u) return;                      // a pool pair's own product is no conflict
 			const ItemTm tm = item_tm[t];
 			const float v = ((tp.tm < tm.tm) ? tp.tm : tm.tm) + 0.0f;            // k_products_join's min; + 0.0f: -0 -> +0 (contraction is off)
 			if(floored && !(v >= tm_floor)) return;
+			ItemEnd em;
+			if(item_end && !end3_product_ok(item_end, R, plus_ok, ep, t, em)) return;
 			const uint32_t y0 = rows_off[y], y1 = rows_off[y + 1];
 			for(uint32_t ia = x0;ia < x1;++ia){
 				const uint32_t ri = rows[ia];
@@ -112,7 +121,8 @@ __global__ __launch_bounds__(POOL_THREADS) void k_conflict_join(const JoinIn J, 
 				}
 			}
 		};
-		if(!(floored && tp.tm < tm_floor)) join_walk<false>(J, ss, g, x, i, ei, 0u, keep);   // (a plus site below the floor keeps no product)
+		// (a plus site below the floor keeps no product, nor does one that fails its own half of the rule)
+		if(!(floored && tp.tm < tm_floor) && plus_ok) join_walk<false>(J, ss, g, x, i, ei, 0u, keep);
 	}
 	if(!EMIT) count[k] = c;
 }
@@ -180,8 +190,10 @@ __global__ __launch_bounds__(POOL_THREADS) void k_conflict_compact(const pcr_poo
 }
 
 // Steps 1-6: the aggregates of the spurious kept products in ctx->pcf_dense[0 .. n_cells) (zero where a cell has none).
-int conflict_products(pcr_ctx *ctx, SeqSet &S, const std::vector<PoolOligo> &ol, const std::vector<SiteOligoX> &olx, const uint32_t *oligo_id,
-	uint32_t n_pool, int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float tm_floor, uint32_t n_cells)
+// ruled: the products must pass R as well (the 3' end per item: pcr_pool_products_end3's step 2, before the melt).
+int conflict_products(const std::string &who, pcr_ctx *ctx, SeqSet &S, const std::vector<PoolOligo> &ol, const std::vector<SiteOligoX> &olx, const uint32_t *oligo_id,
+	uint32_t n_pool, int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float tm_floor, const End3Rule &R, bool ruled, int use_taq,
+	uint32_t n_cells)
 {
 	int rc;
 	const uint32_t n_ol = (uint32_t)ol.size();
@@ -207,13 +219,16 @@ int conflict_products(pcr_ctx *ctx, SeqSet &S, const std::vector<PoolOligo> &ol,
 	}
 	const size_t ol_bytes = ol.size()*sizeof(PoolOligo), olx_bytes = olx.size()*sizeof(SiteOligoX), rol_bytes = row_ol.size()*sizeof(uint2),
 		int_bytes = intended.size()*sizeof(uint32_t), off_bytes = rows_off.size()*sizeof(uint32_t), rows_bytes = rows.size()*sizeof(uint32_t);
-	std::vector<uint8_t> blob(ol_bytes + olx_bytes + rol_bytes + int_bytes + off_bytes + rows_bytes);   // 32-, 8-, 8-, 4-, 4- and 4-byte records, in that order: each is aligned
+	const std::vector<float> norm = ruled ? end3_norms(ol) : std::vector<float>();   // (k_item_end3's; only a rule reads it)
+	const size_t norm_bytes = norm.size()*sizeof(float);
+	std::vector<uint8_t> blob(ol_bytes + olx_bytes + rol_bytes + int_bytes + off_bytes + rows_bytes + norm_bytes);   // 32-, 8-, 8-, 4-, 4-, 4- and 4-byte records, in that order: each is aligned
 	memcpy(blob.data(), ol.data(), ol_bytes);
 	memcpy(blob.data() + ol_bytes, olx.data(), olx_bytes);
 	memcpy(blob.data() + ol_bytes + olx_bytes, row_ol.data(), rol_bytes);
 	memcpy(blob.data() + ol_bytes + olx_bytes + rol_bytes, intended.data(), int_bytes);
 	memcpy(blob.data() + ol_bytes + olx_bytes + rol_bytes + int_bytes, rows_off.data(), off_bytes);
 	memcpy(blob.data() + ol_bytes + olx_bytes + rol_bytes + int_bytes + off_bytes, rows.data(), rows_bytes);
+	if(norm_bytes) memcpy(blob.data() + ol_bytes + olx_bytes + rol_bytes + int_bytes + off_bytes + rows_bytes, norm.data(), norm_bytes);
 	ItemScratch &X = ctx->shared;
 	const ItemBufs B = X.bufs();
 	if((rc = X.in.ensure(blob.size())) != PCR_OK) return rc;
@@ -223,25 +238,29 @@ int conflict_products(pcr_ctx *ctx, SeqSet &S, const std::vector<PoolOligo> &ol,
 	const uint32_t *d_intended = (const uint32_t *)(X.in.p + ol_bytes + olx_bytes + rol_bytes);
 	const uint32_t *d_rows_off = (const uint32_t *)(X.in.p + ol_bytes + olx_bytes + rol_bytes + int_bytes);
 	const uint32_t *d_rows = (const uint32_t *)(X.in.p + ol_bytes + olx_bytes + rol_bytes + int_bytes + off_bytes);
+	const float *d_norm = (const float *)(X.in.p + ol_bytes + olx_bytes + rol_bytes + int_bytes + off_bytes + rows_bytes);
 	HIP_TRY(hipMemcpyAsync(X.in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
 	HIP_TRY(hipStreamSynchronize(ctx->stream));                                   // (blob is this function's)
 	if(S.n_entries == 0 || S.n_touched == 0) return PCR_OK;
 	// ---- 1. the items
 	uint64_t n_items = 0;
 	if((rc = item_count(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
-	if(n_items >= POOL_MAX_ITEMS){ g_err = "pcr_pool_conflicts: too many (entry, oligo) hits"; return PCR_ERR_CAPACITY; }
+	if(n_items >= POOL_MAX_ITEMS){ g_err = who + ": too many (entry, oligo) hits"; return PCR_ERR_CAPACITY; }
 	if(n_items == 0) return PCR_OK;
 	if((rc = item_fill(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
 	const uint32_t ni = (uint32_t)n_items;
 	const unsigned grid_i = (ni + POOL_THREADS - 1)/POOL_THREADS;
 	if((rc = X.cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;                // (the entry counts are spent)
+	// ---- with a rule: the 3' end per item
+	const ItemEnd *d_item_end = nullptr;
+	if(ruled && (rc = end3_items(ctx, S, ni, d_ol, d_norm, R.window, use_taq, d_item_end)) != PCR_OK) return rc;
 	// ---- 2. job offsets, the jobs; 3. Tm per item
-	if((rc = melt_items("pcr_pool_conflicts", ctx, S, d_ol, d_olx, ni, args->salt, B)) != PCR_OK) return rc;
+	if((rc = melt_items(who, ctx, S, d_ol, d_olx, ni, args->salt, B)) != PCR_OK) return rc;
 	// ---- 4. the join: count, scan, emit
 	const uint32_t seq_bits = pool_bits(S.n);
 	const JoinIn J{S.db.p, S.db_cap, S.touched.p, S.d_seg_hi, X.items.p, ni, X.eoff.p, d_ol, n_ol, S.planes.p, S.d_blk_off.p, S.d_len.p,
 		S.d_has_eos.p, amp_min, amp_max};
-	hipLaunchKernelGGL(k_conflict_join<false>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, (const ItemTm *)X.item_tm.p, tm_floor, d_intended,
+	hipLaunchKernelGGL(k_conflict_join<false>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, (const ItemTm *)X.item_tm.p, tm_floor, d_item_end, R, d_intended,
 		d_rows_off, d_rows, d_row_ol, n_pool, seq_bits, X.cnt.p, (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr);
 	HIP_TRY(hipGetLastError());
 	uint64_t total = 0;
@@ -250,15 +269,15 @@ int conflict_products(pcr_ctx *ctx, SeqSet &S, const std::vector<PoolOligo> &ol,
 		HIP_TRY(hipMemcpyAsync(&bad, X.flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
 		return PCR_OK;
 	})) != PCR_OK) return rc;
-	if(bad & 1u){ g_err = "pcr_pool_conflicts: internal trace-back error"; return PCR_ERR_RANGE; }
-	if(total >= PCF_MAX_ATTRIBUTIONS){ g_err = "pcr_pool_conflicts: 2^31 or more (product, cell) attributions"; return PCR_ERR_CAPACITY; }
+	if(bad & 1u){ g_err = who + ": internal trace-back error"; return PCR_ERR_RANGE; }
+	if(total >= PCF_MAX_ATTRIBUTIONS){ g_err = who + ": 2^31 or more (product, cell) attributions"; return PCR_ERR_CAPACITY; }
 	if(total == 0) return PCR_OK;
 	const uint32_t na = (uint32_t)total;
 	if((rc = ctx->pcf_keys.ensure(2*(size_t)na)) != PCR_OK) return rc;
 	if((rc = ctx->pcf_vals.ensure(2*(size_t)na)) != PCR_OK) return rc;
 	uint64_t *k0 = ctx->pcf_keys.p, *k1 = k0 + na;
 	uint32_t *v0 = ctx->pcf_vals.p, *v1 = v0 + na;
-	hipLaunchKernelGGL(k_conflict_join<true>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, (const ItemTm *)X.item_tm.p, tm_floor, d_intended,
+	hipLaunchKernelGGL(k_conflict_join<true>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, (const ItemTm *)X.item_tm.p, tm_floor, d_item_end, R, d_intended,
 		d_rows_off, d_rows, d_row_ol, n_pool, seq_bits, (uint32_t *)nullptr, (const uint64_t *)ctx->pcf_aoff.p, k0, v0);
 	HIP_TRY(hipGetLastError());
 	// ---- 5. (cell, sequence) order, then one aggregate per cell
@@ -287,7 +306,7 @@ int conflict_products(pcr_ctx *ctx, SeqSet &S, const std::vector<PoolOligo> &ol,
 
 // Step 7: tm_max of every ordered cell of pcr_pool_dimers' matrix (tm_floor = 0) in ctx->pcf_dmat[n_ol*n_ol].  The plan is
 // pcr_pool_dimers', restated: the kernels read it as that call uploads it.
-int conflict_dimers(pcr_ctx *ctx, const pcr_thermo_args *args, const std::vector<DimerOligo> &ol, const std::vector<uint32_t> &pref, const std::vector<uint32_t> &row, const std::vector<float> &logs, uint32_t n_cls)
+int conflict_dimers(const std::string &who, pcr_ctx *ctx, const pcr_thermo_args *args, const std::vector<DimerOligo> &ol, const std::vector<uint32_t> &pref, const std::vector<uint32_t> &row, const std::vector<float> &logs, uint32_t n_cls)
 {
 	int rc;
 	const uint32_t n = (uint32_t)ol.size();
@@ -348,30 +367,27 @@ int conflict_dimers(pcr_ctx *ctx, const pcr_thermo_args *args, const std::vector
 	uint32_t bad = 0;
 	HIP_TRY(hipMemcpyAsync(&bad, ctx->shared.flag.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
-	if(bad & 1u){ g_err = "pcr_pool_conflicts: internal trace-back error"; return PCR_ERR_RANGE; }
+	if(bad & 1u){ g_err = who + ": internal trace-back error"; return PCR_ERR_RANGE; }
 	return PCR_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int64_t pcr_pool_conflicts(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
-	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor,
+// pcr_pool_conflicts (rule = NULL) and pcr_pool_conflicts_end3; who: the entry point's name, for the refusals
+int64_t pool_conflicts_impl(const std::string &who, pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor, const pcr_end3_rule *rule,
 	int dimer_rule, float dimer_floor, uint32_t *oligo_id, pcr_pool_conflict *out, uint64_t cap)
 {
 	static_assert(sizeof(pcr_pool_conflict) == 48, "record layout");
 	static_assert(sizeof(ConflictAgg) == 16 && sizeof(uint4) == 16, "the dense array is kept as uint4");
 	// ---- the arguments, before the handle (pcr_pool_products_tm's checks in its order, the oligo table, then the dimer arguments)
-	if(!set_ok(which)){ g_err = "pcr_pool_conflicts: unknown sequence set"; return PCR_ERR_ARG; }
-	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = "pcr_pool_conflicts: PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
-	if(!args || (n_pool && (!pool || !oligo_id)) || (cap && !out)){ g_err = "pcr_pool_conflicts: bad argument"; return PCR_ERR_ARG; }
-	if(n_pool > PCR_POOL_MAX_PAIRS){ g_err = "pcr_pool_conflicts: pool larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
-	if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f)){ g_err = "pcr_pool_conflicts: negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
-	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = "pcr_pool_conflicts: salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
+	if(!set_ok(which)){ g_err = who + ": unknown sequence set"; return PCR_ERR_ARG; }
+	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = who + ": PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
+	if(!args || (n_pool && (!pool || !oligo_id)) || (cap && !out)){ g_err = who + ": bad argument"; return PCR_ERR_ARG; }
+	if(n_pool > PCR_POOL_MAX_PAIRS){ g_err = who + ": pool larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
+	if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f)){ g_err = who + ": negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
+	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = who + ": salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
 	std::vector<PoolOligo> ol;
 	std::vector<SiteOligoX> olx;
-	if(site_oligo_table("pcr_pool_conflicts", "an oligo", "primer_strand", pool, n_pool, threshold, args, template_strand, oligo_id, ol, olx) != PCR_OK) return PCR_ERR_ARG;
+	if(site_oligo_table(who, "an oligo", "primer_strand", pool, n_pool, threshold, args, template_strand, oligo_id, ol, olx) != PCR_OK) return PCR_ERR_ARG;
 	std::vector<DimerOligo> dol;                                                 // pcr_pool_dimers' records of the same oligos
 	for(uint32_t s = 0;s < 2*n_pool;++s){
 		if(oligo_id[s] != dol.size()) continue;                                  // (ids count up in order of first appearance)
@@ -381,17 +397,17 @@ int64_t pcr_pool_conflicts(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, ui
 		q.n_exp = olx[dol.size()].n_exp; q.cls = 0;
 		dol.push_back(q);
 	}
-	if(!std::isfinite(tm_floor)){ g_err = "pcr_pool_conflicts: tm_floor is not finite"; return PCR_ERR_ARG; }
+	if(!std::isfinite(tm_floor)){ g_err = who + ": tm_floor is not finite"; return PCR_ERR_ARG; }
 	if(dimer_rule != PCR_DIMER_RULE_POOL && dimer_rule != PCR_DIMER_RULE_ASSAY && dimer_rule != PCR_CONFLICT_NO_DIMERS){
-		g_err = "pcr_pool_conflicts: unknown dimer_rule (PCR_DIMER_RULE_POOL, PCR_DIMER_RULE_ASSAY or PCR_CONFLICT_NO_DIMERS)"; return PCR_ERR_ARG;
+		g_err = who + ": unknown dimer_rule (PCR_DIMER_RULE_POOL, PCR_DIMER_RULE_ASSAY or PCR_CONFLICT_NO_DIMERS)"; return PCR_ERR_ARG;
 	}
-	if(!std::isfinite(dimer_floor)){ g_err = "pcr_pool_conflicts: dimer_floor is not finite"; return PCR_ERR_ARG; }
+	if(!std::isfinite(dimer_floor)){ g_err = who + ": dimer_floor is not finite"; return PCR_ERR_ARG; }
 	const bool dimers = dimer_rule != PCR_CONFLICT_NO_DIMERS;
 	// with a dimer rule, what pcr_pool_dimers asks of the arguments: its strand concentrations, per pair of degeneracy classes
 	std::vector<uint32_t> cls_degen, pref, row;
 	std::vector<float> logs;
 	if(dimers){
-		if(!(args->primer_strand > 0.0f)){ g_err = "pcr_pool_conflicts: with a dimer rule primer_strand must be positive (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
+		if(!(args->primer_strand > 0.0f)){ g_err = who + ": with a dimer rule primer_strand must be positive (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
 		for(DimerOligo &q : dol){
 			const auto at = std::find(cls_degen.begin(), cls_degen.end(), q.n_exp);
 			q.cls = (uint32_t)(at - cls_degen.begin());
@@ -405,19 +421,23 @@ int64_t pcr_pool_conflicts(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, ui
 				const float cb = (float)(args->primer_strand/(double)cls_degen[b]);
 				const float strand = (dimer_rule == PCR_DIMER_RULE_POOL) ? args->primer_strand                  // pcr_assay.cpp:819-821
 					: ((ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca);                                            // pcr_assay.cpp:244, nuc_cruc.h:832-837
-				if(!(strand > 0.0f)){ g_err = "pcr_pool_conflicts: primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
+				if(!(strand > 0.0f)){ g_err = who + ": primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
 				logs[(size_t)a*n_cls + b] = logf(strand);
 			}
 			const float own = (dimer_rule == PCR_DIMER_RULE_POOL) ? args->primer_strand : ca;                   // valid_pcr.cpp:13
-			if(!(own > 0.0f)){ g_err = "pcr_pool_conflicts: primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
+			if(!(own > 0.0f)){ g_err = who + ": primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
 			logs[(size_t)n_cls*n_cls + a] = logf(own);
 		}
 	}
-	if(!ctx){ g_err = "pcr_pool_conflicts: null handle"; return PCR_ERR_ARG; }
+	End3Rule R;
+	int use_taq;
+	if(end3_rule_of(who, rule, R, use_taq) != PCR_OK) return PCR_ERR_ARG;
+	const bool ruled = end3_ruled(R);                                            // else: no ItemEnd is computed, the join is the base call's
+	if(!ctx){ g_err = who + ": null handle"; return PCR_ERR_ARG; }
 	{ const int drc = drain(ctx); if(drc != PCR_OK) return drc; }
 	HIP_TRY(hipSetDevice(ctx->device));
 	SeqSet &S = ctx->sets[which];
-	if(!S.have_db){ g_err = "pcr_pool_conflicts: no word DB (call pcr_select_words or pcr_select_sites first)"; return PCR_ERR_STATE; }
+	if(!S.have_db){ g_err = who + ": no word DB (call pcr_select_words or pcr_select_sites first)"; return PCR_ERR_STATE; }
 	if(n_pool == 0) return 0;
 	const uint32_t n_ol = (uint32_t)ol.size();
 	if(dimers){
@@ -428,7 +448,7 @@ int64_t pcr_pool_conflicts(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, ui
 		for(uint32_t q = 0;q < n_ol;++q){
 			row[q] = (uint32_t)total;
 			total += (uint64_t)dol[q].n_exp*(pref[n_ol] - dol[q].n_exp) + dol[q].n_exp;
-			if(total >= (uint64_t(1) << 31)){ g_err = "pcr_pool_conflicts: the pool's duplexes number 2^31 or more"; return PCR_ERR_CAPACITY; }
+			if(total >= (uint64_t(1) << 31)){ g_err = who + ": the pool's duplexes number 2^31 or more"; return PCR_ERR_CAPACITY; }
 		}
 		row[n_ol] = (uint32_t)total;
 	}
@@ -439,8 +459,8 @@ int64_t pcr_pool_conflicts(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, ui
 	HIP_TRY(hipMemsetAsync(ctx->shared.flag.p + 1, 0, sizeof(uint32_t), ctx->stream));
 	if((rc = ctx->pcf_dense.ensure(n_cells)) != PCR_OK) return rc;
 	HIP_TRY(hipMemsetAsync(ctx->pcf_dense.p, 0, (size_t)n_cells*sizeof(uint4), ctx->stream));
-	if((rc = conflict_products(ctx, S, ol, olx, oligo_id, n_pool, amp_min, amp_max, args, tm_floor, n_cells)) != PCR_OK) return rc;
-	if(dimers && (rc = conflict_dimers(ctx, args, dol, pref, row, logs, (uint32_t)cls_degen.size())) != PCR_OK) return rc;
+	if((rc = conflict_products(who, ctx, S, ol, olx, oligo_id, n_pool, amp_min, amp_max, args, tm_floor, R, ruled, use_taq, n_cells)) != PCR_OK) return rc;
+	if(dimers && (rc = conflict_dimers(who, ctx, args, dol, pref, row, logs, (uint32_t)cls_degen.size())) != PCR_OK) return rc;
 	// ---- 8. the records, the kept ones in (row_a, row_b) order
 	const size_t ol_bytes = ol.size()*sizeof(PoolOligo), olx_bytes = olx.size()*sizeof(SiteOligoX);
 	const uint2 *d_row_ol = (const uint2 *)(ctx->shared.in.p + ol_bytes + olx_bytes);   // (conflict_products' upload)
@@ -460,6 +480,26 @@ int64_t pcr_pool_conflicts(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, ui
 	HIP_TRY(hipMemcpyAsync(out, ctx->pcf_out.p, (size_t)kept*sizeof(pcr_pool_conflict), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
 	return (int64_t)kept;
+}
+
+} // namespace
+
+extern "C" {
+
+int64_t pcr_pool_conflicts(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor,
+	int dimer_rule, float dimer_floor, uint32_t *oligo_id, pcr_pool_conflict *out, uint64_t cap)
+{
+	return pool_conflicts_impl("pcr_pool_conflicts", ctx, which, pool, n_pool, threshold, amp_min, amp_max, args, template_strand, tm_floor, nullptr,
+		dimer_rule, dimer_floor, oligo_id, out, cap);
+}
+
+int64_t pcr_pool_conflicts_end3(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor,
+	const pcr_end3_rule *rule, int dimer_rule, float dimer_floor, uint32_t *oligo_id, pcr_pool_conflict *out, uint64_t cap)
+{
+	return pool_conflicts_impl("pcr_pool_conflicts_end3", ctx, which, pool, n_pool, threshold, amp_min, amp_max, args, template_strand, tm_floor, rule,
+		dimer_rule, dimer_floor, oligo_id, out, cap);
 }
 
 } // extern "C"

@@ -17,6 +17,9 @@
 //      record lands does not depend on scheduling).
 //   6. The record order: three stable radix sorts, least significant key first -- (probe, probe_loc5, probe_strand), (begin, end),
 //      (plus_oligo, minus_oligo, sequence) -- and a gather.
+// pcr_pool_probe_hits_end3 is the same call with a 3'-end rule (pcr_products_end3.inc, included before this file) in step 4:
+// k_item_end3 fills an ItemEnd per item before the melt (the probes' too; nobody reads them), and k_probe_products' functor makes
+// k_end3_join's tests behind the floor.  Step 5 sees fewer products and is what it was.
 // Steps 1-3 work in the scratch set shared with pcr_pool_products_tm and the others (pcr_ctx::shared), the rest in pcr_ctx::pph_*; the dG table is the handle's (th_dg, keyed by its salt as for every thermo call).
 
 namespace {
@@ -40,10 +43,11 @@ __device__ __forceinline__ uint32_t probe_assay_row(const ProbeAssay *__restrict
 
 // k_products_join over the primer items (oligo < n_prim) of a table that also lists probes: join_walk<true> with n_minus = n_prim.
 // <false>: count[k], and with bits != NULL the bit of every kept product whose (plus, minus) is a pool pair without a probe;
-// <true>: the kept products at prod_off[k] .. as {k, t, plus slot, minus slot}.
+// <true>: the kept products at prod_off[k] .. as {k, t, plus slot, minus slot}.  item_end != NULL: a kept product also passes the
+// 3'-end rule R on its two primer sites (k_end3_join's tests, after the floor); a probe's ItemEnd is never read.
 template<bool EMIT>
 __global__ __launch_bounds__(POOL_THREADS) void k_probe_products(const JoinIn J, uint32_t n_prim, const ItemTm *__restrict__ item_tm, float tm_floor,
-	const uint32_t *__restrict__ intended, const ProbeAssay *__restrict__ tab, uint32_t n_tab, unsigned long long *__restrict__ bits, uint32_t words,
+	const ItemEnd *__restrict__ item_end, const End3Rule R, const uint32_t *__restrict__ intended, const ProbeAssay *__restrict__ tab, uint32_t n_tab, unsigned long long *__restrict__ bits, uint32_t words,
 	uint32_t *__restrict__ count, const uint64_t *__restrict__ prod_off, uint4 *__restrict__ prod)
 {
 	__shared__ int2 ss[POOL_MAX_OLIGOS];
@@ -60,9 +64,14 @@ __global__ __launch_bounds__(POOL_THREADS) void k_probe_products(const JoinIn J,
 		if(ei.strand == 1){
 			const ItemTm tp = item_tm[k];
 			const bool floored = tm_floor > 0.0f;
+			ItemEnd ep; ep.clamp3 = ep.end_mismatch = ep.length = ep.pad = 0; ep.id = 0.0f;
+			if(item_end) ep = item_end[k];
+			const bool plus_ok = !item_end || end3_site_ok(ep, R);
 			auto keep = [&](uint64_t t, uint32_t y, uint32_t j, int32_t, int32_t, int32_t, int32_t){
 				const ItemTm tm = item_tm[t];
 				if(floored && !(((tp.tm < tm.tm) ? tp.tm : tm.tm) >= tm_floor)) return;   // min(tm_plus, tm_minus) >= tm_floor
+				ItemEnd em;
+				if(item_end && !end3_product_ok(item_end, R, plus_ok, ep, t, em)) return;
 				if(EMIT) prod[w++] = make_uint4(k, (uint32_t)t, i, j);
 				else{
 					++c;
@@ -73,7 +82,8 @@ __global__ __launch_bounds__(POOL_THREADS) void k_probe_products(const JoinIn J,
 					}
 				}
 			};
-			if(!(floored && tp.tm < tm_floor)) join_walk<true>(J, ss, g, x, i, ei, n_prim, keep);   // (a plus site below the floor keeps no product)
+			// (a plus site below the floor keeps no product, nor does one that fails its own half of the rule)
+			if(!(floored && tp.tm < tm_floor) && plus_ok) join_walk<true>(J, ss, g, x, i, ei, n_prim, keep);
 		}
 	}
 	if(!EMIT) count[k] = c;
@@ -189,29 +199,26 @@ __global__ void k_probe_gather(const pcr_probe_hit *__restrict__ rec, const uint
 	if(r < n) out[r] = rec[ord[r]];
 }
 
-} // namespace
-
-extern "C" {
-
-int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, const pcr_word128 *probes, uint32_t n_pool,
+// pcr_pool_probe_hits (rule = NULL) and pcr_pool_probe_hits_end3; who: the entry point's name, for the refusals
+int64_t probe_hits_impl(const std::string &who, pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, const pcr_word128 *probes, uint32_t n_pool,
 	float threshold, int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float probe_strand_conc, float template_strand,
-	float tm_floor, float probe_tm_floor, uint32_t *oligo_id, uint32_t *probe_id, pcr_probe_hit *out, uint64_t cap,
+	float tm_floor, float probe_tm_floor, const pcr_end3_rule *rule, uint32_t *oligo_id, uint32_t *probe_id, pcr_probe_hit *out, uint64_t cap,
 	uint64_t *detected)
 {
 	static_assert(sizeof(pcr_probe_hit) == 64, "record layout");
 	static_assert(sizeof(ProbeAssay) == 16, "table layout");
 	// ---- the arguments, before the handle (pcr_pool_products_tm's checks in its order, the probes after the primers)
-	if(!set_ok(which)){ g_err = "pcr_pool_probe_hits: unknown sequence set"; return PCR_ERR_ARG; }
-	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = "pcr_pool_probe_hits: PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
-	if(!args || (n_pool && (!pool || !probes || !oligo_id || !probe_id)) || (cap && !out)){ g_err = "pcr_pool_probe_hits: bad argument"; return PCR_ERR_ARG; }
-	if(n_pool > PCR_POOL_MAX_PAIRS){ g_err = "pcr_pool_probe_hits: pool larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
-	if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f) || !(probe_strand_conc >= 0.0f)){ g_err = "pcr_pool_probe_hits: negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
-	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = "pcr_pool_probe_hits: salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
+	if(!set_ok(which)){ g_err = who + ": unknown sequence set"; return PCR_ERR_ARG; }
+	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = who + ": PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
+	if(!args || (n_pool && (!pool || !probes || !oligo_id || !probe_id)) || (cap && !out)){ g_err = who + ": bad argument"; return PCR_ERR_ARG; }
+	if(n_pool > PCR_POOL_MAX_PAIRS){ g_err = who + ": pool larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
+	if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f) || !(probe_strand_conc >= 0.0f)){ g_err = who + ": negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
+	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = who + ": salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
 	// the distinct primers in order of first appearance (as pcr_pool_products), then the distinct probes in theirs
 	std::vector<PoolOligo> ol;
 	std::vector<SiteOligoX> olx;
 	const float thr2 = threshold*threshold;                                      // pcr_assay.cpp:775-776
-	if(site_oligo_table("pcr_pool_probe_hits", "a primer", "its concentration", pool, n_pool, threshold, args, template_strand, oligo_id, ol, olx) != PCR_OK) return PCR_ERR_ARG;
+	if(site_oligo_table(who, "a primer", "its concentration", pool, n_pool, threshold, args, template_strand, oligo_id, ol, olx) != PCR_OK) return PCR_ERR_ARG;
 	const uint32_t n_prim = (uint32_t)ol.size();
 	std::map<std::pair<uint64_t, uint64_t>, uint32_t> probe_of;
 	for(uint32_t i = 0;i < n_pool;++i){
@@ -220,19 +227,23 @@ int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, c
 		auto ins = probe_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)probe_of.size()));
 		if(ins.second){
 			PoolOligo p; SiteOligoX x;
-			if(!site_oligo("pcr_pool_probe_hits", "a probe", wd, thr2, true, probe_strand_conc, "its concentration", template_strand, p, x)) return PCR_ERR_ARG;
+			if(!site_oligo(who, "a probe", wd, thr2, true, probe_strand_conc, "its concentration", template_strand, p, x)) return PCR_ERR_ARG;
 			ol.push_back(p); olx.push_back(x);
 		}
 		probe_id[i] = ins.first->second;
 	}
-	if(ol.size() > POOL_MAX_OLIGOS){ g_err = "pcr_pool_probe_hits: too many distinct oligos (primers plus probes over 2*PCR_POOL_MAX_PAIRS)"; return PCR_ERR_ARG; }
-	if(!std::isfinite(tm_floor)){ g_err = "pcr_pool_probe_hits: tm_floor is not finite"; return PCR_ERR_ARG; }
-	if(!std::isfinite(probe_tm_floor)){ g_err = "pcr_pool_probe_hits: probe_tm_floor is not finite"; return PCR_ERR_ARG; }
-	if(!ctx){ g_err = "pcr_pool_probe_hits: null handle"; return PCR_ERR_ARG; }
+	if(ol.size() > POOL_MAX_OLIGOS){ g_err = who + ": too many distinct oligos (primers plus probes over 2*PCR_POOL_MAX_PAIRS)"; return PCR_ERR_ARG; }
+	if(!std::isfinite(tm_floor)){ g_err = who + ": tm_floor is not finite"; return PCR_ERR_ARG; }
+	if(!std::isfinite(probe_tm_floor)){ g_err = who + ": probe_tm_floor is not finite"; return PCR_ERR_ARG; }
+	End3Rule R;
+	int use_taq;
+	if(end3_rule_of(who, rule, R, use_taq) != PCR_OK) return PCR_ERR_ARG;
+	const bool ruled = end3_ruled(R);                                            // else: no ItemEnd is computed, the join is the base call's
+	if(!ctx){ g_err = who + ": null handle"; return PCR_ERR_ARG; }
 	{ const int drc = drain(ctx); if(drc != PCR_OK) return drc; }
 	HIP_TRY(hipSetDevice(ctx->device));
 	SeqSet &S = ctx->sets[which];
-	if(!S.have_db){ g_err = "pcr_pool_probe_hits: no word DB (call pcr_select_sites over the pool and its probes first)"; return PCR_ERR_STATE; }
+	if(!S.have_db){ g_err = who + ": no word DB (call pcr_select_sites over the pool and its probes first)"; return PCR_ERR_STATE; }
 	if(n_pool == 0) return 0;
 	const uint32_t words = (uint32_t)((S.n + 63)/64);
 	const size_t row_words = (size_t)n_pool*words;
@@ -258,11 +269,14 @@ int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, c
 	int rc;
 	const size_t ol_bytes = ol.size()*sizeof(PoolOligo), tab_bytes = tab.size()*sizeof(ProbeAssay), olx_bytes = olx.size()*sizeof(SiteOligoX),
 		int_bytes = intended.size()*sizeof(uint32_t);
-	std::vector<uint8_t> blob(ol_bytes + tab_bytes + olx_bytes + int_bytes);     // 32-, 16-, 8- and 4-byte records, in that order: each is aligned
+	const std::vector<float> norm = ruled ? end3_norms(ol) : std::vector<float>();   // (k_item_end3's, the probes included; only a rule reads it)
+	const size_t norm_bytes = norm.size()*sizeof(float);
+	std::vector<uint8_t> blob(ol_bytes + tab_bytes + olx_bytes + int_bytes + norm_bytes);   // 32-, 16-, 8-, 4- and 4-byte records, in that order: each is aligned
 	memcpy(blob.data(), ol.data(), ol_bytes);
 	memcpy(blob.data() + ol_bytes, tab.data(), tab_bytes);
 	memcpy(blob.data() + ol_bytes + tab_bytes, olx.data(), olx_bytes);
 	memcpy(blob.data() + ol_bytes + tab_bytes + olx_bytes, intended.data(), int_bytes);
+	if(norm_bytes) memcpy(blob.data() + ol_bytes + tab_bytes + olx_bytes + int_bytes, norm.data(), norm_bytes);
 	ItemScratch &X = ctx->shared;
 	const ItemBufs B = X.bufs();
 	if((rc = X.in.ensure(blob.size())) != PCR_OK) return rc;
@@ -270,19 +284,23 @@ int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, c
 	const ProbeAssay *d_tab = (const ProbeAssay *)(X.in.p + ol_bytes);
 	const SiteOligoX *d_olx = (const SiteOligoX *)(X.in.p + ol_bytes + tab_bytes);
 	const uint32_t *d_intended = (const uint32_t *)(X.in.p + ol_bytes + tab_bytes + olx_bytes);
+	const float *d_norm = (const float *)(X.in.p + ol_bytes + tab_bytes + olx_bytes + int_bytes);
 	const uint32_t n_tab = (uint32_t)tab.size();
 	HIP_TRY(hipMemcpyAsync(X.in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
 	// ---- 1. the items (item_count waits: blob is read by then)
 	uint64_t n_items = 0;
 	if((rc = item_count(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
-	if(n_items >= POOL_MAX_ITEMS){ g_err = "pcr_pool_probe_hits: too many (entry, oligo) hits"; return PCR_ERR_CAPACITY; }
+	if(n_items >= POOL_MAX_ITEMS){ g_err = who + ": too many (entry, oligo) hits"; return PCR_ERR_CAPACITY; }
 	if(n_items == 0){ zero_rows(); return 0; }
 	if((rc = item_fill(ctx, S, d_ol, n_ol, B, n_items)) != PCR_OK) return rc;
 	const uint32_t ni = (uint32_t)n_items;
 	const unsigned grid_i = (ni + POOL_THREADS - 1)/POOL_THREADS;
 	if((rc = X.cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;                // (the entry counts are spent)
+	// ---- with a rule: the 3' end per item (the probes' too: every item has one, the join reads the primers')
+	const ItemEnd *d_item_end = nullptr;
+	if(ruled && (rc = end3_items(ctx, S, ni, d_ol, d_norm, R.window, use_taq, d_item_end)) != PCR_OK) return rc;
 	// ---- 2. job offsets, the jobs; 3. Tm per item
-	if((rc = melt_items("pcr_pool_probe_hits", ctx, S, d_ol, d_olx, ni, args->salt, B)) != PCR_OK) return rc;
+	if((rc = melt_items(who, ctx, S, d_ol, d_olx, ni, args->salt, B)) != PCR_OK) return rc;
 	const ItemTm *d_item_tm = (const ItemTm *)X.item_tm.p;
 	// ---- 4. the kept products: count (and the rows of the pairs without a probe), scan, compact
 	unsigned long long *d_bits = nullptr;
@@ -293,18 +311,18 @@ int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, c
 	}
 	const JoinIn J{S.db.p, S.db_cap, S.touched.p, S.d_seg_hi, X.items.p, ni, X.eoff.p, d_ol, n_ol, S.planes.p, S.d_blk_off.p, S.d_len.p,
 		S.d_has_eos.p, amp_min, amp_max};
-	hipLaunchKernelGGL(k_probe_products<false>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, n_prim, d_item_tm, tm_floor, d_intended, d_tab, n_tab,
+	hipLaunchKernelGGL(k_probe_products<false>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, n_prim, d_item_tm, tm_floor, d_item_end, R, d_intended, d_tab, n_tab,
 		d_bits, words, X.cnt.p, (const uint64_t *)nullptr, (uint4 *)nullptr);
 	HIP_TRY(hipGetLastError());
 	uint64_t n_prod64 = 0;
 	if((rc = scan_total(ctx, X.cnt.p, X.ioff, X.tmp, ni, n_prod64)) != PCR_OK) return rc;
-	if(n_prod64 >= POOL_MAX_ITEMS){ g_err = "pcr_pool_probe_hits: too many products"; return PCR_ERR_CAPACITY; }
+	if(n_prod64 >= POOL_MAX_ITEMS){ g_err = who + ": too many products"; return PCR_ERR_CAPACITY; }
 	const uint32_t np = (uint32_t)n_prod64;
 	uint64_t total = 0;
 	unsigned grid_p = 0;
 	if(np){
 		if((rc = ctx->pph_prod.ensure(np)) != PCR_OK) return rc;
-		hipLaunchKernelGGL(k_probe_products<true>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, n_prim, d_item_tm, tm_floor, d_intended, d_tab, n_tab,
+		hipLaunchKernelGGL(k_probe_products<true>, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, J, n_prim, d_item_tm, tm_floor, d_item_end, R, d_intended, d_tab, n_tab,
 			(unsigned long long *)nullptr, words, (uint32_t *)nullptr, (const uint64_t *)X.ioff.p, ctx->pph_prod.p);
 		HIP_TRY(hipGetLastError());
 		// ---- 5. the hits: a wave per product; count (and the rows of the pairs with a probe), scan
@@ -326,11 +344,11 @@ int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, c
 		if((rc = flag_and_rows()) != PCR_OK) return rc;
 		HIP_TRY(hipStreamSynchronize(ctx->stream));
 	}
-	if(bad & 1u){ g_err = "pcr_pool_probe_hits: internal trace-back error"; return PCR_ERR_RANGE; }
+	if(bad & 1u){ g_err = who + ": internal trace-back error"; return PCR_ERR_RANGE; }
 	// a pool pair that repeats an earlier assay has that pair's row (the device filled the first copy only)
 	for(uint32_t i = 0;i < n_pool && detected;++i)
 		if(first_row[i] != i) memcpy(detected + (size_t)i*words, detected + (size_t)first_row[i]*words, words*sizeof(uint64_t));
-	if(total >= POOL_MAX_ITEMS){ g_err = "pcr_pool_probe_hits: too many hits"; return PCR_ERR_CAPACITY; }
+	if(total >= POOL_MAX_ITEMS){ g_err = who + ": too many hits"; return PCR_ERR_CAPACITY; }
 	if(total == 0 || total > cap) return (int64_t)total;                         // count only: out is left as it is
 	// ---- 5'. emit at the scanned offsets; 6. the key order
 	const uint32_t nr = (uint32_t)total;
@@ -363,6 +381,28 @@ int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, c
 	HIP_TRY(hipMemcpyAsync(out, r1, (size_t)nr*sizeof(pcr_probe_hit), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
 	return (int64_t)total;
+}
+
+} // namespace
+
+extern "C" {
+
+int64_t pcr_pool_probe_hits(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, const pcr_word128 *probes, uint32_t n_pool,
+	float threshold, int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float probe_strand_conc, float template_strand,
+	float tm_floor, float probe_tm_floor, uint32_t *oligo_id, uint32_t *probe_id, pcr_probe_hit *out, uint64_t cap,
+	uint64_t *detected)
+{
+	return probe_hits_impl("pcr_pool_probe_hits", ctx, which, pool, probes, n_pool, threshold, amp_min, amp_max, args, probe_strand_conc, template_strand,
+		tm_floor, probe_tm_floor, nullptr, oligo_id, probe_id, out, cap, detected);
+}
+
+int64_t pcr_pool_probe_hits_end3(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, const pcr_word128 *probes, uint32_t n_pool,
+	float threshold, int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float probe_strand_conc, float template_strand,
+	float tm_floor, float probe_tm_floor, const pcr_end3_rule *rule, uint32_t *oligo_id, uint32_t *probe_id, pcr_probe_hit *out, uint64_t cap,
+	uint64_t *detected)
+{
+	return probe_hits_impl("pcr_pool_probe_hits_end3", ctx, which, pool, probes, n_pool, threshold, amp_min, amp_max, args, probe_strand_conc,
+		template_strand, tm_floor, probe_tm_floor, rule, oligo_id, probe_id, out, cap, detected);
 }
 
 } // extern "C"

@@ -14,6 +14,8 @@
 //   5. The record order: product_order (pcr_pool.inc).
 // A plus site that fails its own half of the rule keeps no product: it walks nothing (in the count pass only where the before-rule
 // count is not asked for).  Items, jobs and Tm live in pcr_ctx::shared; the ItemEnd array and the join's buffers are pcr_ctx::pe3_*.
+// The files included after this one (pcr_anneal_profile.inc, pcr_pool_conflicts.inc, pcr_probe_hits.inc) apply the same rule in
+// their joins through end3_rule_of, end3_norms, end3_items (step 2 into pe3_end), end3_site_ok and end3_product_ok below.
 #include <rocprim/device/device_reduce.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
@@ -58,6 +60,51 @@ __device__ __forceinline__ bool end3_site_ok(const ItemEnd &e, const End3Rule &R
 	return (uint32_t)e.clamp3 >= min(R.min_clamp3, (uint32_t)e.length) && !(R.window > 0u && (uint32_t)e.end_mismatch > R.max_end_mismatch);
 }
 
+// The rule on a product's two sites, as the keep lambdas of the joins make it after their floor test: the plus half is the caller's
+// (plus_ok, tested once per plus item), the minus item's ItemEnd is loaded only past it.
+__device__ __forceinline__ bool end3_product_ok(const ItemEnd *__restrict__ item_end, const End3Rule &R, bool plus_ok, const ItemEnd &ep, uint64_t t, ItemEnd &em)
+{
+	if(!plus_ok) return false;
+	em = item_end[t];
+	if(!end3_site_ok(em, R)) return false;
+	return R.ident_threshold == 0.0f || sqrtf(__fmul_rn(ep.id, em.id)) >= R.ident_threshold;   // sqrtf: see identity()
+}
+
+// The caller's rule, checked (NULL: the zero rule); the refusals carry the entry point's name.
+int end3_rule_of(const std::string &who, const pcr_end3_rule *rule, End3Rule &R, int &use_taq)
+{
+	R = End3Rule{0u, 0u, 0u, 0.0f};
+	use_taq = 0;
+	if(!rule) return PCR_OK;
+	if(rule->window > 32u || rule->min_clamp3 > 32u || rule->max_end_mismatch > 32u){ g_err = who + ": window, min_clamp3 or max_end_mismatch above 32"; return PCR_ERR_ARG; }
+	if(rule->use_taq_mama != 0 && rule->use_taq_mama != 1){ g_err = who + ": use_taq_mama is neither 0 nor 1"; return PCR_ERR_ARG; }
+	if(!std::isfinite(rule->ident_threshold) || !(rule->ident_threshold >= 0.0f && rule->ident_threshold <= 1.0f)){ g_err = who + ": ident_threshold is not finite or outside [0, 1]"; return PCR_ERR_ARG; }
+	R.min_clamp3 = rule->min_clamp3; R.window = rule->window; R.max_end_mismatch = rule->max_end_mismatch; R.ident_threshold = rule->ident_threshold;
+	use_taq = rule->use_taq_mama;
+	return PCR_OK;
+}
+// a rule that can drop a product (max_end_mismatch alone tests nothing: its window is empty)
+inline bool end3_ruled(const End3Rule &R) { return R.min_clamp3 > 0u || R.window > 0u || R.ident_threshold != 0.0f; }
+// 1/length per oligo (optimize.cpp:221, as fill_oligo_planes): what k_item_end3 reads as norm[]
+inline std::vector<float> end3_norms(const std::vector<PoolOligo> &ol)
+{
+	std::vector<float> norm(ol.size());
+	for(size_t o = 0;o < ol.size();++o) norm[o] = (float)(1.0/(unsigned)(ol[o].stop - ol[o].start + 1));
+	return norm;
+}
+
+// k_item_end3 over the items of the shared scratch set, into ctx->pe3_end (enqueued; nothing waits)
+int end3_items(pcr_ctx *ctx, SeqSet &S, uint32_t ni, const PoolOligo *d_ol, const float *d_norm, uint32_t window, int use_taq, const ItemEnd *&d_item_end)
+{
+	int rc;
+	if((rc = ctx->pe3_end.ensure(ni)) != PCR_OK) return rc;
+	hipLaunchKernelGGL(k_item_end3, dim3((ni + POOL_THREADS - 1)/POOL_THREADS), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
+		(const uint2 *)ctx->shared.items.p, ni, d_ol, d_norm, window, use_taq, (ItemEnd *)ctx->pe3_end.p);
+	HIP_TRY(hipGetLastError());
+	d_item_end = (const ItemEnd *)ctx->pe3_end.p;
+	return PCR_OK;
+}
+
 // k_products_join with the rule: one thread per item k, join_walk.  item_tm = NULL: no Tm is read and nothing is floored; item_end =
 // NULL: no rule (the plain count).  <false>: count[k], with before != NULL the products past the floor before the rule in
 // before[k], and with bits != NULL the bit of every kept product of a pool pair; <true>: records, (begin, end) sort keys and identity
@@ -92,12 +139,7 @@ __global__ __launch_bounds__(POOL_THREADS) void k_end3_join(const JoinIn J, cons
 			if(floored && !(((tp.tm < tm.tm) ? tp.tm : tm.tm) >= tm_floor)) return;   // min(tm_plus, tm_minus) >= tm_floor
 			++cb;
 			ItemEnd em; em.clamp3 = em.end_mismatch = em.length = em.pad = 0; em.id = 0.0f;
-			if(item_end){
-				if(!plus_ok) return;
-				em = item_end[t];
-				if(!end3_site_ok(em, R)) return;
-				if(R.ident_threshold != 0.0f && !(sqrtf(__fmul_rn(ep.id, em.id)) >= R.ident_threshold)) return;   // sqrtf: see identity()
-			}
+			if(item_end && !end3_product_ok(item_end, R, plus_ok, ep, t, em)) return;
 			if(EMIT){
 				pcr_product_end3 r;
 				r.plus_oligo = x; r.minus_oligo = y; r.sequence = ei.seq; r.begin = p5; r.end = m3;
@@ -168,15 +210,9 @@ int64_t pcr_pool_products_end3(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool
 	std::vector<SiteOligoX> olx;
 	if(site_oligo_table("pcr_pool_products_end3", "an oligo", "primer_strand", pool, n_pool, threshold, args, template_strand, oligo_id, ol, olx) != PCR_OK) return PCR_ERR_ARG;
 	if(!std::isfinite(tm_floor)){ g_err = "pcr_pool_products_end3: tm_floor is not finite"; return PCR_ERR_ARG; }
-	End3Rule R = {0u, 0u, 0u, 0.0f};
-	int use_taq = 0;
-	if(rule){
-		if(rule->window > 32u || rule->min_clamp3 > 32u || rule->max_end_mismatch > 32u){ g_err = "pcr_pool_products_end3: window, min_clamp3 or max_end_mismatch above 32"; return PCR_ERR_ARG; }
-		if(rule->use_taq_mama != 0 && rule->use_taq_mama != 1){ g_err = "pcr_pool_products_end3: use_taq_mama is neither 0 nor 1"; return PCR_ERR_ARG; }
-		if(!std::isfinite(rule->ident_threshold) || !(rule->ident_threshold >= 0.0f && rule->ident_threshold <= 1.0f)){ g_err = "pcr_pool_products_end3: ident_threshold is not finite or outside [0, 1]"; return PCR_ERR_ARG; }
-		R.min_clamp3 = rule->min_clamp3; R.window = rule->window; R.max_end_mismatch = rule->max_end_mismatch; R.ident_threshold = rule->ident_threshold;
-		use_taq = rule->use_taq_mama;
-	}
+	End3Rule R;
+	int use_taq;
+	if(end3_rule_of("pcr_pool_products_end3", rule, R, use_taq) != PCR_OK) return PCR_ERR_ARG;
 	if(!args && tm_floor > 0.0f){ g_err = "pcr_pool_products_end3: tm_floor > 0 without args (no thermodynamics to floor)"; return PCR_ERR_ARG; }
 	if(!ctx){ g_err = "pcr_pool_products_end3: null handle"; return PCR_ERR_ARG; }
 	{ const int drc = drain(ctx); if(drc != PCR_OK) return drc; }
@@ -197,14 +233,13 @@ int64_t pcr_pool_products_end3(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool
 	if(S.n_entries == 0 || S.n_touched == 0){ zero_rows(); return 0; }
 	const uint32_t n_ol = (uint32_t)ol.size();
 	const bool melt = args && (tm_floor > 0.0f || cap > 0 || want_bits);         // pcr_pool_products_tm's condition
-	const bool ruled = R.min_clamp3 > 0u || R.window > 0u || R.ident_threshold != 0.0f;
+	const bool ruled = end3_ruled(R);
 	const bool ends = ruled || cap > 0;                                          // else: nothing reads an ItemEnd
 	// the intended bitmap and the rows of the first pool pair per (plus, minus): pcr_pool_products_tm's (PairTable); then 1/length per oligo
 	PairTable pair_rows(oligo_id, n_pool, n_ol);
 	const std::vector<uint32_t> &intended = pair_rows.intended;
 	const std::vector<ProductPair> &tab = pair_rows.tab;
-	std::vector<float> norm(n_ol);
-	for(uint32_t o = 0;o < n_ol;++o) norm[o] = (float)(1.0/(unsigned)(ol[o].stop - ol[o].start + 1));   // optimize.cpp:221, as fill_oligo_planes
+	const std::vector<float> norm = end3_norms(ol);
 	int rc;
 	const size_t ol_bytes = ol.size()*sizeof(PoolOligo), tab_bytes = tab.size()*sizeof(ProductPair), olx_bytes = olx.size()*sizeof(SiteOligoX),
 		int_bytes = intended.size()*sizeof(uint32_t), norm_bytes = norm.size()*sizeof(float);
@@ -234,13 +269,7 @@ int64_t pcr_pool_products_end3(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool
 	if((rc = X.cnt.ensure((size_t)ni + 1)) != PCR_OK) return rc;                // (the entry counts are spent)
 	// ---- 2. the 3' end per item
 	const ItemEnd *d_item_end = nullptr;
-	if(ends){
-		if((rc = ctx->pe3_end.ensure(ni)) != PCR_OK) return rc;
-		hipLaunchKernelGGL(k_item_end3, dim3(grid_i), dim3(POOL_THREADS), 0, ctx->stream, S.db.p, S.db_cap, S.touched.p, S.d_seg_hi,
-			(const uint2 *)X.items.p, ni, d_ol, d_norm, R.window, use_taq, (ItemEnd *)ctx->pe3_end.p);
-		HIP_TRY(hipGetLastError());
-		d_item_end = (const ItemEnd *)ctx->pe3_end.p;
-	}
+	if(ends && (rc = end3_items(ctx, S, ni, d_ol, d_norm, R.window, use_taq, d_item_end)) != PCR_OK) return rc;
 	// ---- 3. job offsets, the jobs, Tm per item
 	if(melt && (rc = melt_items("pcr_pool_products_end3", ctx, S, d_ol, d_olx, ni, args->salt, B)) != PCR_OK) return rc;
 	const ItemTm *d_item_tm = melt ? (const ItemTm *)X.item_tm.p : nullptr;
