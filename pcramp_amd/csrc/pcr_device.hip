@@ -64,6 +64,7 @@
 
 #include "../../include/pcramp_hip.h"
 #include "pcr_host.hpp"
+#include "pcr_seed_lists.hpp"
 #include "pcr_launch_queue.hpp"
 
 using pcrhost::Planes;
@@ -732,21 +733,17 @@ struct pcr_ctx {
 	DevBuf<uint32_t> best, counters, mask, status;
 	int scan_version = 3;
 	bool force_seed1 = false;   // PCRAMP_SEED=1: the first form of the seed scan (A/B)
-	// second form of the seed scan: the per-oligo seed cache (the pass's lists live in its PassJob: PlanLists, pcr_select.inc)
+	// second and third forms of the seed scan: the per-oligo seed caches, their positional memos and the listing's scratch
+	// (pcr_seed_lists.hpp; the pass's lists live in its PassJob: PlanLists, pcr_select.inc).  Caller-thread state: stage A alone
+	// reads and writes it.  The third form has a cache of its own (the oligo's FOLDED seeds, pcrhost::orientation_fold_seeds, are other
+	// lists under the same key), with a span byte per seed and the running 64-entry chunks of the seeds' spans in the sets whose
+	// position index has one of the last S3_CHUNK_SETS generations.
+	pcrseed::Lister seed_lists;                   // PCRAMP_SEED_MEMO=0: every orientation through the hash (A/B)
+	static constexpr int S3_CHUNK_SETS = pcrseed::CHUNK_SETS;
 	struct S2Key { uint32_t a, c, g, t, floor_; bool operator==(const S2Key &o) const { return a == o.a && c == o.c && g == o.g && t == o.t && floor_ == o.floor_; } };
 	struct S2KeyHash { size_t operator()(const S2Key &k) const { uint64_t h = 0x9E3779B97F4A7C15ull; for(uint32_t v : {k.a, k.c, k.g, k.t, k.floor_}){ h ^= v; h *= 0x100000001B3ull; h ^= h >> 29; } return (size_t)h; } };
-	struct S2Entry { std::vector<uint32_t> seeds; /* code << 14 | off << 9 */ uint32_t off_mask; bool seedable; uint4 mask; /* the orientation's interleaved mask entry (k_seed2 / k_seed3) */ };
-	std::unordered_map<S2Key, S2Entry, S2KeyHash> s2_cache;
+	struct S2Entry { std::vector<uint32_t> seeds; /* code | off << 16 */ uint32_t off_mask; bool seedable; };   // (first form: s1_cache)
 	std::vector<pcrhost::Seed> s2_tmp;
-	// third form: the oligo's FOLDED seeds (pcrhost::orientation_fold_seeds; a cache of its own: the second form's 9-gram lists are other
-	// lists under the same key), a span byte per seed, and the running 64-entry chunks of the seeds' spans in the sets whose position
-	// index has these generations -- the last S3_CHUNK_SETS of them, so that sets which alternate (the targets and backgrounds of a
-	// design iteration, a caller rotating over sets) do not recompute them pass after pass
-	static constexpr int S3_CHUNK_SETS = 4;
-	struct S3Chunks { uint64_t gen = 0; uint32_t total = 0; std::vector<uint32_t> run; };
-	struct S3Entry : S2Entry { std::vector<uint8_t> spans; /* lo | hi << 2 */ S3Chunks chunks[S3_CHUNK_SETS]; uint32_t next_slot = 0; };
-	std::unordered_map<S2Key, S3Entry, S2KeyHash> s3_cache;
-	std::vector<pcrhost::FoldSeed> s3_tmp;
 	struct S3Launch { Seed3Slices W; uint32_t n_chunks, per_wg, slice_cap, n_irr_wg; };
 	int pair_mode = 1; bool s3_pair_attr_set = false;   // PCRAMP_PAIR: 0 never pair two handles' passes into one launch (A/B), 1 by the backlog rule, 2 "force" (tests: hold until a partner, a flush or the time cap)
 	bool no_seed3 = false, s3_attr_set = false;   // PCRAMP_SEED3=0: second form (A/B)
@@ -834,6 +831,7 @@ struct pcr_ctx {
 		pcr_amplify_args args; uint64_t *d_fr, *d_rf;
 	};
 	std::vector<Pending> pending;
+	std::vector<std::vector<pcr_pair> > pair_pool;   // pair lists of drained passes, recycled by the next ones (caller thread)
 	// The default pcr_screen_device pass is planned on the caller's thread and staged and launched by the stream's launcher thread
 	// (pcr_select.inc: PassJob lists who owns what meanwhile).  launcher: attached by the first pipelined pass, shared by the handles
 	// of the stream; lq_client: this handle's jobs in its queue and the error of one that failed.
@@ -1548,6 +1546,7 @@ pcr_ctx *pcr_create(int device, void *hip_stream, const pcr_params *params)
 	if(const char *v = getenv("PCRAMP_IRR_INDEX")) ctx->no_irr_index = v[0] == '0';
 	if(const char *v = getenv("PCRAMP_SEED3")) ctx->no_seed3 = v[0] == '0';
 	if(const char *v = getenv("PCRAMP_S3_NEXT")) ctx->s3_next = v[0] != '0';
+	if(const char *v = getenv("PCRAMP_SEED_MEMO")) ctx->seed_lists.use_memo = v[0] != '0';
 	if(const char *v = getenv("PCRAMP_LAUNCH_THREAD")) ctx->launch_thread = v[0] != '0';   // A/B, and for callers that want no helper thread
 	if(const char *v = getenv("PCRAMP_PAIR")) ctx->pair_mode = (v[0] == '0') ? 0 : (strcmp(v, "force") == 0) ? 2 : 1;
 	if(const char *v = getenv("PCRAMP_SCAN")){ if(v[0] == '1') ctx->scan_version = 1; else if(v[0] == '2') ctx->scan_version = 2; }   // A/B: 1 = popcount scan, 2 = bit-sliced only

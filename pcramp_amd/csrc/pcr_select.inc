@@ -2,13 +2,10 @@ namespace {
 
 // The lists a pass's planners make and its launches read (plan_seed2, plan_seed3_slices, plan_seed1).  They belong to the pass
 // (PassJob), not to the handle: the caller's thread may plan the next pass while the launcher thread still reads this one's.
-struct PlanLists {
-	// second form of the seed scan: the seed list in groups of whole orientations, each within one launch's LDS budget; mask entries, floors
-	std::vector<uint32_t> s2_seeds; std::vector<uint4> s2_masks; std::vector<uint8_t> s2_floors;
-	std::vector<uint32_t> s2_group_end, s2_group_offmask, s2_group_or, s2_group_nor;   // per group: end in the seed list, forward-seed slot offsets, first orientation, orientations spanned
+struct PlanLists : pcrseed::SeedLists {
+	// second form of the seed scan: the lists of pcrseed::SeedLists (pcr_seed_lists.hpp) and the floors
+	std::vector<uint8_t> s2_floors;
 	std::vector<pcr_ctx::S3Launch> s3_launch;      // third form: per launch group, the workgroups' slices of the chunk list
-	std::vector<uint32_t> s3_prefix;               // third form: the pass's chunk list
-	std::vector<uint8_t> s3_spans;                 // third form: per seed of s2_seeds the next bases it reads, lo | hi << 2
 	std::vector<uint32_t> s1_seeds;                // first form, tables built on the device: the pass's seed list
 	void clear()
 	{
@@ -16,13 +13,6 @@ struct PlanLists {
 		s3_launch.clear(); s3_prefix.clear(); s3_spans.clear(); s1_seeds.clear();
 	}
 };
-
-inline uint32_t spread16(uint32_t v)               // bit i of the low half -> bit 2i
-{
-	v &= 0xFFFFu;
-	v = (v | (v << 8)) & 0x00FF00FFu; v = (v | (v << 4)) & 0x0F0F0F0Fu;
-	v = (v | (v << 2)) & 0x33333333u; return (v | (v << 1)) & 0x55555555u;
-}
 
 // The seeds of a pass for the second form of the seed scan: per orientation from the cache (derived on a miss), listed as
 // code << 14 | slot offset << 9 | orientation WITHIN ITS GROUP, in groups of at most S2_MAX_OR whole orientations, each of which
@@ -32,151 +22,36 @@ inline uint32_t spread16(uint32_t v)               // bit i of the low half -> b
 // tables: 21 ms per select_words on a C5 shard).  false: an orientation whose seeds alone exceed one launch.
 constexpr uint32_t S2_MAX_GROUPS = 4096;
 // S3 (optional): the set whose position index the third form will read.  The seeds are then the oligo's FOLDED seeds, from a cache
-// of their own (ctx->s3_cache; PCRAMP_S3_NEXT=0: the plain 9-gram list with span A..T), listed in the same u32 form with a span
-// byte per seed beside them (L.s3_spans), and the chunk list of every launch group (L.s3_prefix: the running number of 64-entry
-// chunks of the group's seeds' spans, its total behind it) is made alongside, from chunk counts cached beside each oligo's seeds
-// for the sets last used.
+// of their own (ctx->seed_lists.third; PCRAMP_S3_NEXT=0: the plain 9-gram list with span A..T), listed in the same u32 form with a
+// span byte per seed beside them (L.s3_spans), and the chunk list of every launch group (L.s3_prefix: the running number of
+// 64-entry chunks of the group's seeds' spans, its total behind it) is made alongside, from chunk counts cached beside each
+// oligo's seeds for the sets last used.  The listing itself is plain C++: pcrseed::list_seeds (pcr_seed_lists.hpp).
+static_assert(sizeof(pcrseed::Mask16) == sizeof(uint4) && alignof(pcrseed::Mask16) <= alignof(uint4), "the mask entry is the device's uint4");
+static_assert(offsetof(pcrseed::Mask16, y) == offsetof(uint4, y) && offsetof(pcrseed::Mask16, w) == offsetof(uint4, w), "the mask entry is the device's uint4");
+static_assert(S2_Q == 9, "pcrseed::derive lists 9-gram seeds");
+static_assert(pcrseed::CHUNK_SETS == pcr_ctx::S3_CHUNK_SETS, "generations kept per cache entry");
 bool plan_seed2(pcr_ctx *ctx, PlanLists &L, const std::vector<pcrhost::Candidate> &cand, std::vector<uint32_t> &or_seed, std::vector<uint32_t> &or_plain, uint32_t &irr_off_mask,
 	const SeqSet *S3 = nullptr)
 {
-	std::vector<uint32_t> &pf = L.s3_prefix;
-	pf.clear();
-	uint32_t pf_run = 0;
-	const uint32_t n_or = 2*(uint32_t)cand.size();
-	std::vector<uint32_t> &out = L.s2_seeds;
-	out.clear(); L.s2_group_end.clear(); L.s2_group_offmask.clear(); L.s2_group_or.clear(); L.s2_group_nor.clear();
-	irr_off_mask = 0;
-	L.s2_masks.resize(n_or);
-	if(ctx->s2_cache.size() > 16384) ctx->s2_cache.clear();
-	size_t group_begin = 0; uint32_t group_mask = 0, group_or0 = 0, group_last = 0;
 	// the tables of a launch must fit one CU's LDS; the third form keeps only the masks and a slice of the lists there: more orientations
 	// (9-bit ids) and as many seeds as the pass has -- plan_seed3_slices() checks its LDS need afterwards
-	auto fits = [&](size_t n, uint32_t g_or){
-		if(S3) return g_or <= S3_MAX_OR && n <= S3_MAX_SEEDS;
-		return g_or <= S2_MAX_OR && n <= S2_MAX_SEEDS && sizeof(S2Shared) + 17*(size_t)g_or + 8*n + 1024 <= 160*1024;
-	};
-	// per orientation ONE 16-byte mask entry: the four base-set planes, slots 0..15 spread to the even bits (slot k -> bit 2k) and
-	// slots 16..31 to the odd bits (slot 16 + k -> bit 2k + 1): both halves of a window are counted by one multiplexer pass
-	// (s2_count) from one LDS read
-	auto mask_of = [](const Planes &m){
-		return make_uint4(spread16(m.a) | (spread16(m.a >> 16) << 1), spread16(m.c) | (spread16(m.c >> 16) << 1),
-		                  spread16(m.g) | (spread16(m.g >> 16) << 1), spread16(m.t) | (spread16(m.t >> 16) << 1));
-	};
-	std::vector<uint8_t> &spans = L.s3_spans;
-	spans.clear();
-	if(ctx->s3_cache.size() > 16384) ctx->s3_cache.clear();
-	for(uint32_t o = 0;o < n_or;++o){
-		const pcrhost::Candidate &c = cand[o >> 1];
-		const Planes &m = (o & 1u) ? c.rc : c.fwd;
-		const pcr_ctx::S2Key key = {m.a, m.c, m.g, m.t, c.floor_};
-		pcr_ctx::S3Entry *e3 = nullptr; const pcr_ctx::S2Entry *e2 = nullptr;
-		if(S3){
-			auto it = ctx->s3_cache.find(key);
-			if(it == ctx->s3_cache.end()){
-				pcr_ctx::S3Entry e; e.off_mask = 0;
-				ctx->s3_tmp.clear(); ctx->s2_tmp.clear();
-				e.seedable = pcrhost::orientation_index_seeds(m, c.floor_, ctx->s3_next, ctx->s3_tmp, ctx->s2_tmp);
-				e.mask = mask_of(m);
-				e.seeds.reserve(ctx->s3_tmp.size()); e.spans.reserve(ctx->s3_tmp.size());
-				for(const pcrhost::FoldSeed &sd : ctx->s3_tmp){
-					e.seeds.push_back((sd.code << 14) | ((uint32_t)sd.off << 9)); e.spans.push_back((uint8_t)(sd.lo | (sd.hi << 2))); e.off_mask |= 1u << sd.off;
-				}
-				it = ctx->s3_cache.emplace(key, std::move(e)).first;
-			}
-			e3 = &it->second; e2 = e3;
-		}
-		else{
-			auto it = ctx->s2_cache.find(key);
-			if(it == ctx->s2_cache.end()){
-				pcr_ctx::S2Entry e; e.off_mask = 0;
-				ctx->s2_tmp.clear();
-				e.seedable = pcrhost::orientation_seeds(m, c.floor_, 0, ctx->s2_tmp, nullptr, S2_Q);
-				e.mask = mask_of(m);
-				e.seeds.reserve(ctx->s2_tmp.size());
-				for(const pcrhost::Seed &sd : ctx->s2_tmp){ e.seeds.push_back((sd.code << 14) | ((uint32_t)sd.off << 9)); e.off_mask |= 1u << sd.off; }
-				it = ctx->s2_cache.emplace(key, std::move(e)).first;
-			}
-			e2 = &it->second;
-		}
-		const pcr_ctx::S2Entry &e = *e2;
-		L.s2_masks[o] = e.mask;
-		if(!e.seedable){ or_plain.push_back(o); continue; }
-		or_seed.push_back(o);
-		// the group spans orientations [group_or0, o]: unseedable ones in between only take an (unused) id
-		if(!fits(out.size() - group_begin + e.seeds.size(), o - group_or0 + 1)){   // close the group, open the next at this orientation
-			if(!fits(e.seeds.size(), 1) || L.s2_group_end.size() + 1 >= S2_MAX_GROUPS) return false;
-			L.s2_group_end.push_back((uint32_t)out.size()); L.s2_group_offmask.push_back(group_mask); L.s2_group_or.push_back(group_or0); L.s2_group_nor.push_back(group_last - group_or0 + 1);
-			group_begin = out.size(); group_mask = 0; group_or0 = o;
-			if(S3){ pf.push_back(pf_run); pf_run = 0; }                                // the group's total; the next one starts at 0
-		}
-		group_last = o;
-		const size_t at = out.size();
-		out.resize(at + e.seeds.size());
-		for(size_t k = 0;k < e.seeds.size();++k) out[at + k] = e.seeds[k] | (o - group_or0);
-		if(S3){
-			spans.insert(spans.end(), e3->spans.begin(), e3->spans.end());
-			// exclusive running chunk counts of the oligo's seeds in this set: kept for the last S3_CHUNK_SETS index generations
-			pcr_ctx::S3Chunks *ch = nullptr;
-			for(pcr_ctx::S3Chunks &x : e3->chunks){ if(x.gen == S3->pix_generation){ ch = &x; break; } }
-			if(!ch){
-				ch = &e3->chunks[e3->next_slot]; e3->next_slot = (e3->next_slot + 1u) % pcr_ctx::S3_CHUNK_SETS;
-				ch->run.resize(e.seeds.size());
-				const uint32_t *const start = S3->pix_start_h.data();
-				uint32_t run = 0;
-				for(size_t k = 0;k < e.seeds.size();++k){
-					const uint32_t key4 = (e.seeds[k] >> 14) << 2, sp = e3->spans[k];
-					ch->run[k] = run; run += (start[key4 + (sp >> 2) + 1u] - start[key4 + (sp & 3u)] + 63u) >> 6;
-				}
-				ch->total = run; ch->gen = S3->pix_generation;
-			}
-			const size_t pa = pf.size();
-			pf.resize(pa + ch->run.size());
-			for(size_t k = 0;k < ch->run.size();++k) pf[pa + k] = pf_run + ch->run[k];
-			pf_run += ch->total;
-		}
-		if(!(o & 1u)){ irr_off_mask |= e.off_mask; group_mask |= e.off_mask; }   // slot offsets at which forward seeds sit (irregular-word scan)
-	}
-	L.s2_group_end.push_back((uint32_t)out.size()); L.s2_group_offmask.push_back(group_mask); L.s2_group_or.push_back(group_or0);
-	L.s2_group_nor.push_back(or_seed.empty() ? 0u : group_last - group_or0 + 1);
-	if(S3) pf.push_back(pf_run);
-	return true;
+	const pcrseed::Limits lim2 = { S2_MAX_OR, S2_MAX_SEEDS, sizeof(S2Shared) + 1024, 160*1024, S2_MAX_GROUPS };
+	const pcrseed::Limits lim3 = { S3_MAX_OR, S3_MAX_SEEDS, 0, ~size_t(0), S2_MAX_GROUPS };
+	pcrseed::SetIndex ix = { nullptr, 0 };
+	if(S3){ ix.start = S3->pix_start_h.data(); ix.generation = S3->pix_generation; }
+	return pcrseed::list_seeds(ctx->seed_lists, S3 ? lim3 : lim2, cand.data(), cand.size(), S3 ? &ix : nullptr, ctx->s3_next, L, or_seed, or_plain, irr_off_mask);
 }
 
 // Third form: the chunks of every launch group dealt to G workgroups in equal contiguous shares, and per workgroup the first seed of its
-// share (a merge walk over the group's chunk list).  false: some group's largest slice does not fit the LDS (many seeds whose runs are
-// empty side by side: tiny target sets) -- the caller plans again within the second form's limits.
+// share (pcrseed::plan_slices: a merge walk over the group's chunk list).  false: some group's largest slice does not fit the LDS (many
+// seeds whose runs are empty side by side: tiny target sets) -- the caller plans again within the second form's limits.
 constexpr size_t S3_LDS_BUDGET = 120*1024;
 // 1024-thread workgroups, two per CU (512 threads x 4 per CU: within the spread of the repeated default, profiles/dbg/r03_ab_s3_grid.txt)
 constexpr uint32_t S3_WG_THREADS = 1024;
 uint32_t seed3_grid(const pcr_ctx *ctx) { return std::min<uint32_t>(2*ctx->n_cu, S3_MAX_WG); }
 bool plan_seed3_slices(pcr_ctx *ctx, PlanLists &PL, bool with_irr)
 {
-	const uint32_t G_all = seed3_grid(ctx), seeds_per_turn = 16u*(S3_WG_THREADS/64);
-	PL.s3_launch.resize(PL.s2_group_end.size());
-	size_t g_begin = 0, g_prefix = 0;
-	for(size_t g = 0;g < PL.s2_group_end.size();++g){
-		const uint32_t ns = PL.s2_group_end[g] - (uint32_t)g_begin;
-		g_begin = PL.s2_group_end[g];
-		const uint32_t *P = PL.s3_prefix.data() + g_prefix;                  // the group's chunk list, [ns + 1]
-		g_prefix += (size_t)ns + 1;
-		pcr_ctx::S3Launch &L = PL.s3_launch[g];
-		// the launch's first workgroups look the irregular words up (16 seeds per wave turn) and leave the chunks to the others: the two
-		// chains of dependent loads then run side by side; at most a quarter of the launch
-		L.n_irr_wg = with_irr ? std::min<uint32_t>((ns + seeds_per_turn - 1u)/seeds_per_turn, G_all/4u) : 0u;
-		const uint32_t G = (G_all - L.n_irr_wg) & ~1u;                       // even: a paired launch gives two neighbours' shares to one workgroup (pair_slices)
-		L.n_chunks = P[ns]; L.per_wg = std::max<uint32_t>(1u, (L.n_chunks + G - 1u)/G); L.slice_cap = 2;
-		if(ns == 0) continue;
-		uint32_t at = 0;
-		for(uint32_t w = 0;w <= G;++w){
-			const uint64_t target = (uint64_t)w*L.per_wg;
-			while(at + 1u < ns && P[at + 1u] <= target) ++at;
-			L.W.start[w] = at;
-		}
-		for(uint32_t w = G + 1;w <= S3_MAX_WG;++w) L.W.start[w] = at;
-		for(uint32_t w = 0;w < G;++w) L.slice_cap = std::max(L.slice_cap, std::min(L.W.start[w + 1] + 2u, ns + 1u) - L.W.start[w]);
-		if(17*(size_t)PL.s2_group_nor[g] + 9*(size_t)L.slice_cap + 64 > S3_LDS_BUDGET) return false;   // masks, floors | slice of the chunk list, the seeds and their spans
-	}
-	return true;
+	return pcrseed::plan_slices(PL, PL.s3_launch, seed3_grid(ctx), 16u*(S3_WG_THREADS/64), S3_MAX_WG, S3_LDS_BUDGET, with_irr);
 }
 
 // The seeds of a pass for the first form with device-built tables: per orientation from the cache (8-gram seeds), listed as
@@ -506,7 +381,8 @@ int choose_scan_form(pcr_ctx *ctx, SeqSet &S, const std::vector<pcrhost::Candida
 //
 // WHO OWNS WHAT while a handle has jobs in its stream's launch queue
 //   caller thread (stage A): argument checks; build_candidates; the planning half of choose_scan_form with the per-oligo caches
-//     (s2_cache, s1_cache, s2_tmp, seed_count/own/fill); plan_seed3_slices; prepare_tables (candidate planes, floors, build_oligos);
+//     (seed_lists: the second and third forms' caches, each with its positional memo, and the listing's scratch; s1_cache, s2_tmp,
+//     seed_count/own/fill); plan_seed3_slices; prepare_tables (candidate planes, floors, build_oligos);
 //     pending[]; mail_seq (a pipelined pass's sequence number is reserved at enqueue: the passes of a handle are strictly FIFO);
 //     the job free list (under job_m).
 //   launcher thread (stage B): the Stager rings with their wait_published spin; the sizing of S.ctrl / hits / S.db / best / S.touched;
@@ -634,7 +510,7 @@ int stage_tables(pcr_ctx *ctx, SeqSet &S, const PassJob &J, FusedAmp *fa, bool a
 	}
 	if(seed2){
 		T.ST2.seeds = st.put(L.s2_seeds.data(), L.s2_seeds.size());
-		T.ST2.masks = st.put(L.s2_masks.data(), L.s2_masks.size());
+		T.ST2.masks = st.put(reinterpret_cast<const uint4 *>(L.s2_masks.data()), L.s2_masks.size());
 		T.ST2.floors = st.put(L.s2_floors.data(), L.s2_floors.size());
 		T.ST2.n_seeds = (uint32_t)L.s2_seeds.size(); T.ST2.n_or = n_or;
 		if(seed3){ T.d_s3_prefix = st.put(L.s3_prefix.data(), L.s3_prefix.size()); T.d_s3_spans = st.put(L.s3_spans.data(), L.s3_spans.size()); }
@@ -1449,6 +1325,7 @@ int screen_pass(pcr_ctx *ctx, pcr_set which, const pcr_pair *pairs, uint32_t n_p
 		return rc;
 	}
 	pcr_ctx::Pending p;
+	if(!ctx->pair_pool.empty()){ p.pairs.swap(ctx->pair_pool.back()); ctx->pair_pool.pop_back(); }   // (storage of a drained pass: no allocation per pass)
 	p.which = (int)which; p.pairs.assign(pairs, pairs + n_pairs); p.opt5 = optimize_5; p.opt3 = optimize_3;
 	p.thr = select_threshold; p.min_len = min_oligo_length; p.args = *args; p.d_fr = d_bits_fr; p.d_rf = d_bits_rf;
 	if(!inline_pass){
@@ -1484,6 +1361,16 @@ int drain(pcr_ctx *ctx)
 	if(ctx->pending.empty()) return PCR_OK;
 	std::vector<pcr_ctx::Pending> pend;
 	pend.swap(ctx->pending);
+	// however this returns: the drained passes' pair lists, and the list of passes itself, keep their storage for the next ones
+	struct Recycle {
+		pcr_ctx *ctx; std::vector<pcr_ctx::Pending> &pend;
+		~Recycle()
+		{
+			for(pcr_ctx::Pending &q : pend){ if(ctx->pair_pool.size() < pcr_ctx::MAIL_RING) ctx->pair_pool.push_back(std::move(q.pairs)); }
+			pend.clear();
+			if(ctx->pending.empty() && ctx->pending.capacity() < pend.capacity()) ctx->pending.swap(pend);
+		}
+	} recycle{ctx, pend};
 	int rc;
 	for(size_t i = 0;i < pend.size();++i){
 		uint32_t c[4];
