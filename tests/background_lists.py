@@ -41,6 +41,7 @@ tests/test_background_lists_host.py holds the oracle to the planted counts and t
 runs the cases on the device.
 """
 import random
+import re
 from collections import namedtuple
 
 from testdata import rand_seq, revcomp
@@ -290,3 +291,18 @@ def oracle_answers(lib, c):
             bits[(ev, taq)] = rows
     _ANSWERS[key] = Answers(so, so.db_entries(), counts, sum(counts[o] for o in c.origin), bits)
     return _ANSWERS[key]
+
+
+# The "[pcramp] background_match:" line pcr_background_match writes per attempt under PCRAMP_DEBUG=1
+LINE = re.compile(r"\[pcramp\] background_match: attempt (\d+), (emit<\d+>), (\d+)-slot buckets, (\d+) pairs, list of (\d+) records "
+                  r"in sub-lists of (\d+), (\d+) records emitted, (\d+) kept, overflow (\d): ([a-z ]+)")
+FIELDS = ("attempt", "form", "slots", "pairs", "cap", "sub_cap", "emitted", "kept", "overflow", "end")
+
+
+def debug_lines(err):
+    """The debug lines of a call's stderr -> one dict per attempt: the form that ran, the capacities, the records, how it ended."""
+    out = []
+    for m in LINE.finditer(err):
+        g = m.groups()
+        out.append(dict(zip(FIELDS, [int(g[0]), g[1]] + [int(x) for x in g[2:9]] + [g[9].strip()])))
+    return out

@@ -18,18 +18,8 @@ from pcramp_amd import api
 
 pytestmark = pytest.mark.gpu
 
-LINE = re.compile(r"\[pcramp\] background_match: attempt (\d+), (emit<\d+>), (\d+)-slot buckets, (\d+) pairs, list of (\d+) records "
-                  r"in sub-lists of (\d+), (\d+) records emitted, (\d+) kept, overflow (\d): ([a-z ]+)")
 CAND = re.compile(r"\[pcramp\] candidate_amplicons: attempt (\d+), (\d+) pairs, list of (\d+) records, (\d+) records emitted: (\w+)")
-FIELDS = ("attempt", "form", "slots", "pairs", "cap", "sub_cap", "emitted", "kept", "overflow", "end")
-
-
-def _lines(err):
-    out = []
-    for m in LINE.finditer(err):
-        g = m.groups()
-        out.append(dict(zip(FIELDS, [int(g[0]), g[1]] + [int(x) for x in g[2:9]] + [g[9].strip()])))
-    return out
+_lines = BL.debug_lines
 
 
 @pytest.fixture(scope="module")

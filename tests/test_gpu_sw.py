@@ -129,6 +129,8 @@ def test_sw_known_answers(dev, oracle):
                                 dict(bg_threshold=0.4, bg_multiplier=0.8, use_taq_mama=0, amp_max=400),
                                 dict(bg_threshold=0.35, bg_multiplier=1.0, use_taq_mama=1)])
 def test_background_match(dev, oracle, kw):
+    """Random mutated families at four fixed thresholds: the candidate lists and the verdicts as a whole.  The score the verdict
+    rests on -- k_sw_bg's alignments, value by value -- is pinned in tests/test_gpu_background_scores.py."""
     rng = random.Random(41)
     roots = family_targets(rng, 3, 1, 700, div=0.0)
     seqs = [mutate(rng, r, 0.05) for r in roots for _ in range(5)]
