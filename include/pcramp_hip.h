@@ -724,6 +724,72 @@ typedef struct {
 int64_t pcr_pool_dimers(pcr_ctx *ctx, const pcr_pair *pool, uint32_t n_pool, const pcr_thermo_args *args, int rule,
 	float tm_floor, uint32_t *oligo_id, pcr_pool_dimer *out, uint64_t cap);
 
+/* ---- Which oligos of a pool extend on each other: 3'-anchored dimers */
+
+/* One qualifying placement of a duplex: the query's 3' end paired on the target, with template to copy (40 bytes). */
+typedef struct {
+	uint32_t query_oligo, target_oligo;   /* distinct-oligo ids (as pcr_pool_dimers); equal: the oligo on a second copy of itself */
+	uint32_t q_expansion, t_expansion;    /* the duplex, indices in Word::begin()/next() order; on the diagonal: equal */
+	uint8_t  run, extension;              /* Watson-Crick pairs from the query's 3' base on; target bases 5' of the paired end (= the placement j) */
+	uint8_t  overlap, overlap_matches;    /* positions where the strands face each other; the Watson-Crick pairs among them */
+	uint32_t flags;                       /* PCR_DIMER_HOMO, PCR_DIMER_END3_MUTUAL */
+	float    dG, tm, dH, dS;              /* of the run alone as a heterodimer; dG = dH - 310.15 * dS in float (kcal/mol), tm in degrees C */
+} pcr_dimer_placement;
+
+/* One cell of the pool's 3'-anchored dimer matrix, reduced over its qualifying placements (48 bytes). */
+typedef struct {
+	uint32_t query_oligo, target_oligo;   /* as pcr_pool_dimer */
+	uint32_t n_duplexes;                  /* D(query) * D(target); on the diagonal D(query) */
+	uint32_t n_placements;                /* qualifying placements over all duplexes of the cell, before the dG filter */
+	uint32_t q_expansion, t_expansion;    /* the best placement's duplex */
+	uint8_t  run, extension, overlap, overlap_matches;   /* the best placement's */
+	uint32_t flags;                       /* PCR_DIMER_HOMO; PCR_DIMER_END3_MUTUAL of the best placement */
+	float    dG, tm, dH, dS;              /* the best placement's */
+} pcr_pool_dimer_end3;
+
+#define PCR_DIMER_END3_MUTUAL 2u   /* the run reaches the target's 3' end: both oligos extend */
+
+/* Which oligos of a pool extend on each other (Primer3's "end" complementarity, with the engine's energies).  pcr_pool_dimers
+ * melts the best duplex of two whole oligos and does not say where it sits; a primer-dimer artefact needs less and something
+ * else: a few clean base pairs at a 3' end and, beyond it, template for the polymerase to copy.
+ *   Oligo ids, cells and duplexes are pcr_pool_dimers': ids in order of first appearance (oligo_id[2*n_pool] receives them), a
+ * cell per ordered (query q, target t), off the diagonal D(q)*D(t) duplexes, duplex iq * D(t) + it (query expansion outer).
+ * On the diagonal the cell has D(q) duplexes: expansion x against a second copy of x, the oligo priming on its own kind.
+ *   Placements.  Both strands are spelt 5'->3' as the words hold them, x with Lx bases, y with Ly.  Placement j, 0 <= j < Ly,
+ * puts x's 3' base opposite y[j], antiparallel: x[Lx-1-k] faces y[j+k] for 0 <= k < overlap = min(Lx, Ly - j).  run = the
+ * number of consecutive Watson-Crick pairs (A.T and C.G only) counted from k = 0; overlap_matches = the Watson-Crick pairs
+ * among all overlap positions; extension = j, the bases of y 5' of the paired end, which the polymerase copies: the product
+ * is x + revcomp(y[0 .. j-1]).  A placement qualifies if run >= min_run and extension >= min_extension.
+ * PCR_DIMER_END3_MUTUAL is set where j + run == Ly: the run reaches y's 3' end and both oligos extend.  Corner cases: the run
+ * never exceeds the overlap, so oligos shorter than min_run have no placement; j = 0 has nothing to copy and qualifies only
+ * with min_extension = 0; a run of the whole query (run == Lx) is legal; on the diagonal, a palindromic 3' end of r bases
+ * gives run >= r at j = Lx - r, which is MUTUAL.
+ *   Melt.  Every qualifying placement is melted as the heterodimer of the run alone: NucCruc::approximate_tm_heterodimer with
+ * query = x's last `run` bases and target = y[j .. j+run-1], on the diagonal too.  Salt and strand concentration are
+ * pcr_pool_dimers' `rule` for cell (q, t) off the diagonal; on the diagonal the same off-diagonal rule with t = q (under
+ * PCR_DIMER_RULE_ASSAY half of primer_strand / D(q)).  It yields tm, dH and dS; dG = dH - 310.15f * dS in float, as
+ * pcr_thermo_result.dG.  The engine gives all zeros to perfect duplexes of 1 and 2 bases and energies from 3 bases on, so
+ * min_run is 3 .. 32; min_extension is 0 .. 31.
+ *   Placement records (place_out): in cell order, then duplex order, then j ascending; kept where the placement's own
+ * dG <= dg_max (+INFINITY keeps all).
+ *   Cell records (out): the cells with at least one kept placement, in cell order.  n_placements counts the qualifying
+ * placements before the dG filter.  The best placement has the lowest dG; on a tie the longer run, then the lower duplex
+ * number, then the lower j (ties are common: the same 3-mer duplex at two places of a target gives identical floats).  Its
+ * expansions, its four byte fields, its four floats and its MUTUAL flag are the cell's.
+ *   Returns the number of cell records or a negative error; *n_place, if not NULL, receives the number of placement
+ * records.  Past cap the contents of out are unspecified, past place_cap those of place_out; cap = 0 and place_cap = 0
+ * count only, and with dg_max = +INFINITY such a count call runs no thermodynamics.  n_pool = 0 returns 0.
+ *   PCR_ERR_ARG (from the arguments alone, checked before the handle, in this order): null pointers, cap without out or
+ * place_cap without place_out; n_pool > PCR_POOL_MAX_PAIRS; an unknown rule; primer_strand <= 0; salt outside [1e-6, 1];
+ * min_run outside 3 .. 32; min_extension above 31; dg_max NaN; then the oligos as pcr_pool_dimers (empty, a hole, too many
+ * expansions).  PCR_ERR_CAPACITY as pcr_pool_dimers.  Then a null handle.  PCR_ERR_RANGE if a trace-back fails.
+ *   Needs no sequence set and no word DB, changes nothing other calls read, makes no collective on a sharded handle.
+ *   Out of scope: anchors with gaps or bulges, or a mismatch inside the run; hairpin self-priming of a single strand;
+ * treating probes (3'-blocked oligos) differently; and pcr_pool_conflicts, whose dimer half still reads pcr_pool_dimers. */
+int64_t pcr_pool_dimers_end3(pcr_ctx *ctx, const pcr_pair *pool, uint32_t n_pool, const pcr_thermo_args *args, int rule,
+	uint32_t min_run, uint32_t min_extension, float dg_max, uint32_t *oligo_id,
+	pcr_pool_dimer_end3 *out, uint64_t cap, pcr_dimer_placement *place_out, uint64_t place_cap, uint64_t *n_place);
+
 /* ---- Products of a pool with the Tm of their two sites, Tm-floored, and the pool's amplification bitsets at that floor */
 
 /* One product with the duplex Tm of its plus site and of its minus site (48 bytes). */

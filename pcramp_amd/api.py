@@ -96,6 +96,20 @@ DIMER_HOMO = 1                                # PCR_DIMER_HOMO
 DIMER_RULE_POOL, DIMER_RULE_ASSAY = 0, 1      # PCR_DIMER_RULE_*
 POOL_DIMER_BATCH_JOBS = 1 << 21               # POOL_DIMER_BATCH_JOBS of pcr_pool_dimers.inc: the duplexes melted per batch
 
+# pcr_pool_dimer_end3 / pcr_dimer_placement: a cell of the pool's 3'-anchored dimer matrix and one qualifying placement
+# (Screener.pool_dimers_end3)
+POOL_DIMER_END3_DTYPE = np.dtype([("query_oligo", np.uint32), ("target_oligo", np.uint32), ("n_duplexes", np.uint32),
+                                  ("n_placements", np.uint32), ("q_expansion", np.uint32), ("t_expansion", np.uint32),
+                                  ("run", np.uint8), ("extension", np.uint8), ("overlap", np.uint8), ("overlap_matches", np.uint8),
+                                  ("flags", np.uint32), ("dG", np.float32), ("tm", np.float32), ("dH", np.float32), ("dS", np.float32)])
+DIMER_PLACEMENT_DTYPE = np.dtype([("query_oligo", np.uint32), ("target_oligo", np.uint32), ("q_expansion", np.uint32),
+                                  ("t_expansion", np.uint32), ("run", np.uint8), ("extension", np.uint8), ("overlap", np.uint8),
+                                  ("overlap_matches", np.uint8), ("flags", np.uint32), ("dG", np.float32), ("tm", np.float32),
+                                  ("dH", np.float32), ("dS", np.float32)])
+DIMER_END3_MUTUAL = 2                         # PCR_DIMER_END3_MUTUAL
+POOL_DIMER_END3_BATCH_DUPLEXES = 1 << 20      # of pcr_pool_dimers_end3.inc: the duplexes scanned per batch of cells
+POOL_DIMER_END3_BATCH_JOBS = 1 << 17          # of pcr_pool_dimers_end3.inc: the placements melted per launch
+
 # pcr_product_tm: a product with the Tm of its two sites (Screener.pool_products_tm)
 PRODUCT_TM_DTYPE = np.dtype([("plus_oligo", np.uint32), ("minus_oligo", np.uint32), ("sequence", np.uint32), ("begin", np.int32),
                              ("end", np.int32), ("inner_start", np.int32), ("inner_length", np.int32), ("intended", np.uint32),
@@ -202,7 +216,7 @@ ABI_SYMBOLS = [
     "pcr_sw_align_words", "pcr_background_match", "pcr_multiplex_match",
     "pcr_thermo", "pcr_valid_words", "pcr_dimer", "pcr_multiplex_compatible", "pcr_multiplex_screen",
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
-    "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers",
+    "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers", "pcr_pool_dimers_end3",
     "pcr_pool_products_tm", "pcr_pool_products_end3", "pcr_pool_anneal_profile", "pcr_pool_conflicts", "pcr_pool_probe_hits",
     "pcr_pool_anneal_profile_end3", "pcr_pool_conflicts_end3", "pcr_pool_probe_hits_end3", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants", "pcr_site_repair",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
@@ -344,6 +358,9 @@ def load_library():
     L.pcr_pool_dimers.restype = C.c_int64
     L.pcr_pool_dimers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ThermoArgs), C.c_int, C.c_float, C.c_void_p,
                                   C.c_void_p, C.c_uint64]
+    L.pcr_pool_dimers_end3.restype = C.c_int64
+    L.pcr_pool_dimers_end3.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ThermoArgs), C.c_int, C.c_uint32, C.c_uint32,
+                                       C.c_float, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.pcr_multiplex_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.pcr_multiplex_coverage.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_void_p]
     L.pcr_host_pool_overlaps.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -478,6 +495,37 @@ def merge_variant_flanks(variants, oligos, site_variant=None, sites=None):
     order = sorted(range(len(out)), key=lambda g: (int(out[g]["oligo"]), -int(out[g]["sequences"]), -int(out[g]["sites"]),
                                                    -int(out[g]["matches"]), _slot_planes(W.slots_from_word(out[g]["word"]))))
     return out[order]
+
+
+def _expansion_text(word, index):
+    """Expansion `index` of an oligo word in Word::begin() / next() order, as text: the index is a mixed-radix number over
+    the degenerate slots, slot 15 fastest, then 14 .. 0, then 31 .. 16; a digit picks among the slot's bases, A < C < G < T."""
+    slots = [int(v) for v in W.slots_from_word(word)]
+    pick = {}
+    for k in list(range(15, -1, -1)) + list(range(31, 15, -1)):
+        bases = [b for b in (1, 2, 4, 8) if slots[k] & b]
+        if len(bases) > 1:
+            index, d = divmod(index, len(bases))
+            pick[k] = bases[d]
+    return W.text_from_codes(np.array([pick.get(k, v) for k, v in enumerate(slots) if v], np.uint8))
+
+
+def dimer_products(placements, pool, ids):
+    """The extension product of every placement record of Screener.pool_dimers_end3(pool, placements=True), as text: the
+    query expansion x followed by the reverse complement of the `extension` target bases 5' of the paired end,
+    x + revcomp(y[:extension]).  `ids` are the call's oligo ids.  Host only."""
+    words = {}
+    for s, k in enumerate(np.asarray(ids).tolist()):
+        words.setdefault(int(k), pool[s // 2][s & 1])
+    text, out = {}, []
+    for p in placements:
+        x, y = ((int(p[o]), int(p[e])) for o, e in (("query_oligo", "q_expansion"), ("target_oligo", "t_expansion")))
+        for key in (x, y):
+            if key not in text:
+                text[key] = _expansion_text(words[key[0]], key[1])
+        head = text[y][:int(p["extension"])]
+        out.append(text[x] + W.text_from_codes(W.revcomp_codes(W.codes_from_text(head))) if head else text[x])
+    return out
 
 
 def live_resources():
@@ -1589,6 +1637,57 @@ class Screener:
         """pool_dimers' records as a dense float32 [n, n] matrix of `field` (row: query oligo, column: target oligo); 0 where
         there is no record."""
         m = np.zeros((int(n), int(n)), np.float32)
+        m[records["query_oligo"], records["target_oligo"]] = records[field]
+        return m
+
+    def pool_dimers_end3(self, pool, min_run=4, min_extension=1, dg_max=None, salt=0.05, primer_strand=9e-7, rule="pool",
+                         placements=False, cap=None):
+        """Which oligos of the pool extend on each other (pcr_pool_dimers_end3) -> (oligo_id, cells) or, with placements,
+        (oligo_id, cells, placement records); POOL_DIMER_END3_DTYPE in cell order, DIMER_PLACEMENT_DTYPE in cell, duplex
+        and placement order.
+
+        A placement puts the query's 3' base opposite target base j (both 5'->3' as held); it qualifies with `run` >=
+        min_run clean Watson-Crick pairs from that base on and `extension` = j >= min_extension target bases beyond it to
+        copy (DIMER_END3_MUTUAL: the run reaches the target's 3' end too).  Each is melted as the heterodimer of the run
+        alone under pool_dimers' `rule`; dG is at 37 C.  A cell reports n_placements and its best (lowest dG) placement;
+        the diagonal (DIMER_HOMO) is an oligo on a second copy of itself.  dg_max keeps the placements, and the cells
+        with a placement, at or below it (None: all).  `cap` is (cells, placements) or one number for both."""
+        rules = {"pool": DIMER_RULE_POOL, "assay": DIMER_RULE_ASSAY, DIMER_RULE_POOL: DIMER_RULE_POOL, DIMER_RULE_ASSAY: DIMER_RULE_ASSAY}
+        if rule not in rules:
+            raise ValueError("pool_dimers_end3: rule must be 'pool' or 'assay'")
+        a = W.pairs_array(pool)
+        ids = np.zeros(max(2 * len(pool), 1), np.uint32)
+        args = self._targs(salt, primer_strand, 0.0, 0.0, 0.0, 0.0)
+        dg = float("inf") if dg_max is None else float(dg_max)
+        n_place = C.c_uint64(0)
+
+        def call(out, cap, pout, pcap):
+            n = self.L.pcr_pool_dimers_end3(self.h, a.ctypes.data, len(pool), C.byref(args), rules[rule], int(min_run), int(min_extension),
+                                            dg, ids.ctypes.data, out, cap, pout, pcap, C.byref(n_place))
+            if n < 0:
+                raise PcrError(_err(self.L))
+            return int(n), int(n_place.value)
+
+        if cap is None:
+            ccap, pcap = call(None, 0, None, 0) if dg_max is None else (1 << 16, 1 << 18)   # all kept: the count is geometry alone
+        else:
+            ccap, pcap = (int(cap), int(cap)) if np.isscalar(cap) else (int(cap[0]), int(cap[1]))
+        if not placements:
+            pcap = 0
+        while True:
+            out = np.zeros(max(ccap, 1), POOL_DIMER_END3_DTYPE)
+            pout = np.zeros(max(pcap, 1), DIMER_PLACEMENT_DTYPE)
+            n, m = call(out.ctypes.data, ccap, pout.ctypes.data if pcap else None, pcap)
+            if n <= ccap and (not placements or m <= pcap):
+                head = (ids[:2 * len(pool)].copy(), out[:n].copy())
+                return head + (pout[:m].copy(),) if placements else head
+            ccap, pcap = max(ccap, n), (max(pcap, m) if placements else 0)   # the counts: one retry
+
+    @staticmethod
+    def dimer_end3_matrix(records, n, field="dG", fill=np.inf):
+        """pool_dimers_end3's cell records as a dense float32 [n, n] matrix of `field` (row: query oligo, column: target
+        oligo); `fill` where there is no record."""
+        m = np.full((int(n), int(n)), fill, np.float32)
         m[records["query_oligo"], records["target_oligo"]] = records[field]
         return m
 

@@ -31,6 +31,7 @@
 //   k_sv_items, k_sv_heads, k_sv_tm : the sites grouped by (oligo, template planes in the window) with radix sorts over the whole key, one melt per group (pcr_site_variants.inc)
 //   k_rp_candidates, k_rp_weigh, k_rp_step : a greedy union of variants into each oligo, every (oligo, candidate) weighed by what its union holds (pcr_site_repair.inc)
 //   k_pool_dimer, k_pool_dimer_reduce : the same engine over every ordered oligo pair of a pool, jobs derived from the job number (pcr_pool_dimers.inc)
+//   k_dimer_end3_scan, k_dimer_end3_melt, k_dimer_end3_merge : the 3'-anchored placements of those pairs, listed from the slot masks and melted run by run (pcr_pool_dimers_end3.inc)
 //   k_item_tm, k_products_join : k_site_tm's Tm per item, and k_pool_join's geometry with the two sites' Tm, the floor and the pool's bit rows (pcr_products_tm.inc)
 //   k_item_end3, k_end3_join : the 3' end of every item's site (clamp, mismatches in a window, identity with the TaqMAMA factor), and k_products_join with a rule on the two sites' ends (pcr_products_end3.inc)
 //   k_anneal_join, k_anneal_rows : the same join without a floor: per (pool pair, sequence) the highest min-Tm by integer atomicMax, LDS histograms over an ascending temperature list (pcr_anneal_profile.inc)
@@ -886,6 +887,11 @@ struct pcr_ctx {
 	// struct is that file's), the per-item counts before the rule, their sum and its scratch, the pool's bit rows, records, sort keys and order.
 	DevBuf<uint2> pe3_end; DevBuf<uint32_t> pe3_before, pe3_ord; DevBuf<uint64_t> pe3_sum, pe3_keys, pe3_bits; DevBuf<uint8_t> pe3_tmp;
 	DevBuf<pcr_product_end3> pe3_rec;
+	// pcr_pool_dimers_end3 (pcr_pool_dimers_end3.inc), beside pdim_in / pdim_tmp / pdim_flag: the placements per duplex and their scan, the job list,
+	// a launch's results, per-cell records and the kept ones, keep flags and their scan (cells, then a launch's jobs), the kept placements.
+	DevBuf<uint32_t> pde3_cnt, pde3_off, pde3_keep, pde3_koff; DevBuf<uint2> pde3_jobs; DevBuf<float4> pde3_res;
+	DevBuf<pcr_pool_dimer_end3> pde3_rec, pde3_out; DevBuf<pcr_dimer_placement> pde3_place;
+	bool pde3_attr_set = false;
 };
 
 namespace {
@@ -2211,6 +2217,7 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_site_variants.inc"
 #include "pcr_site_repair.inc"
 #include "pcr_pool_dimers.inc"
+#include "pcr_pool_dimers_end3.inc"
 #include "pcr_products_tm.inc"
 #include "pcr_products_end3.inc"
 #include "pcr_anneal_profile.inc"

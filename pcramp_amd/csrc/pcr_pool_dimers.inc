@@ -81,6 +81,24 @@ __device__ __forceinline__ unsigned char pdim_code(const Planes &m, unsigned s, 
 	return (unsigned char)(set ? (unsigned)__ffs(set) - 1u : 0u);
 }
 
+// enumerate_parallel reports the winner's Tm only; its energies are still in the lanes' slabs: the same merge again (lowest
+// dG, earliest cell on a tie) -> the winner's dH and dS, zeros where no lane has one.  There are three copies of this rule --
+// the end of enumerate_parallel (pcr_thermo.inc), k_site_tm (pcr_site_tm.inc) and this one, which k_pool_dimer and
+// k_dimer_end3_melt (pcr_pool_dimers_end3.inc) share: they must change together.
+__device__ __forceinline__ void pdim_winner(const thermo::ParLane *par, float &dH, float &dS)
+{
+	using namespace thermo;
+	int win = -1;
+	float wdg = 0.0f;
+	dH = dS = 0.0f;
+	for(int l = 0;l < WAVE_PAR;++l){
+		const ParLane &L = par[l];
+		if(L.win < 0) continue;
+		const float dgl = L.best.dH - TARGET_T*L.best.dS;
+		if(win < 0 || dgl < wdg || (dgl == wdg && L.win < win)){ win = L.win; wdg = dgl; dH = L.best.dH; dS = L.best.dS; }
+	}
+}
+
 // Duplex j (numbered over the whole matrix), j0 <= j < j0 + n_jobs: (tm, dH, dS, status) -> res[j - j0].
 __global__ __launch_bounds__(PDIM_THREADS) void k_pool_dimer(DimerPlan P, uint32_t j0, uint32_t n_jobs, const int *__restrict__ dg_global, float log_na,
 	float4 *__restrict__ res)
@@ -133,17 +151,8 @@ __global__ __launch_bounds__(PDIM_THREADS) void k_pool_dimer(DimerPlan P, uint32
 		unsigned status = 0;
 		const float tm = enumerate_parallel<false>(e, w.par, w.rowmask, e.qlen, homo, status);
 		if(lane == 0){
-			// enumerate_parallel reports the winner's Tm only; its energies are still in the lanes' slabs: the same merge again
-			// (lowest dG, earliest cell on a tie).  There are three copies of this rule -- the end of enumerate_parallel
-			// (pcr_thermo.inc), k_site_tm (pcr_site_tm.inc) and this one: they must change together.
-			int win = -1;
-			float wdg = 0.0f, dH = 0.0f, dS = 0.0f;
-			for(int l = 0;l < WAVE_PAR;++l){
-				const ParLane &L = w.par[l];
-				if(L.win < 0) continue;
-				const float dgl = L.best.dH - TARGET_T*L.best.dS;
-				if(win < 0 || dgl < wdg || (dgl == wdg && L.win < win)){ win = L.win; wdg = dgl; dH = L.best.dH; dS = L.best.dS; }
-			}
+			float dH, dS;
+			pdim_winner(w.par, dH, dS);
 			res[jl] = make_float4(tm, dH, dS, __uint_as_float((status & 1u) ? PDIM_ST_ERROR : 0u));
 		}
 		wave_sync();                                                               // before the next job overwrites the sequences
@@ -184,6 +193,92 @@ __global__ __launch_bounds__(POOL_THREADS) void k_pool_dimer_compact(const pcr_p
 	if(k < n_cells && keep[k]) out[off[k]] = rec[k];
 }
 
+// What the host works out from a pool before it looks at the handle (pcr_pool_dimers and pcr_pool_dimers_end3 refuse the same
+// pools in the same order, `who` begins the message): the distinct oligos in order of first appearance, the two prefix arrays
+// and the log strand concentration of every pair of degeneracy classes.
+struct DimerHostPlan { std::vector<DimerOligo> ol; std::vector<uint32_t> pref, row; std::vector<float> logs; uint32_t n = 0, n_cls = 0; };
+
+int pdim_host_plan(const char *who, const pcr_pair *pool, uint32_t n_pool, const pcr_thermo_args *args, int rule, uint32_t *oligo_id, DimerHostPlan &H)
+{
+	const std::string w = std::string(who) + ": ";
+	// the distinct oligos, in order of first appearance (as pcr_pool_products)
+	std::vector<DimerOligo> &ol = H.ol;
+	std::vector<uint32_t> cls_degen;                                              // the distinct degeneracies
+	std::map<std::pair<uint64_t, uint64_t>, uint32_t> id_of;
+	for(uint32_t s = 0;s < 2*n_pool;++s){
+		const pcr_word128 &wd = (s & 1) ? pool[s/2].r : pool[s/2].f;
+		auto ins = id_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)ol.size()));
+		if(ins.second){
+			DimerOligo d;
+			d.m = pcrhost::planes_of_word(wd.w);
+			d.start = pcrhost::planes_start(d.m); d.stop = pcrhost::planes_stop(d.m);
+			const uint32_t occ = pcrhost::planes_occupied(d.m);
+			if(!occ || __builtin_popcount(occ) != d.stop - d.start + 1){
+				g_err = w + "an oligo is empty or has a hole between its ends (NucCruc::set_query throws)"; return PCR_ERR_ARG;
+			}
+			const double degen = pcrhost::planes_degeneracy(d.m);
+			if(degen > (double)PCR_SITE_MAX_EXPANSIONS){ g_err = w + "an oligo has more than PCR_SITE_MAX_EXPANSIONS expansions"; return PCR_ERR_ARG; }
+			d.n_exp = (uint32_t)degen;
+			const auto at = std::find(cls_degen.begin(), cls_degen.end(), d.n_exp);
+			d.cls = (uint32_t)(at - cls_degen.begin());
+			if(at == cls_degen.end()) cls_degen.push_back(d.n_exp);
+			ol.push_back(d);
+		}
+		oligo_id[s] = ins.first->second;
+	}
+	const uint32_t n = H.n = (uint32_t)ol.size(), n_cls = H.n_cls = (uint32_t)cls_degen.size();
+	std::vector<uint32_t> &pref = H.pref, &row = H.row;
+	pref.assign(n + 1, 0); row.assign(n + 1, 0);
+	for(uint32_t t = 0;t < n;++t) pref[t + 1] = pref[t] + ol[t].n_exp;            // at most 2 048 * 256
+	{
+		uint64_t total = 0;
+		for(uint32_t q = 0;q < n;++q){
+			row[q] = (uint32_t)total;
+			total += (uint64_t)ol[q].n_exp*(pref[n] - ol[q].n_exp) + ol[q].n_exp;
+			if(total >= (uint64_t(1) << 31)){ g_err = w + "the pool's duplexes number 2^31 or more"; return PCR_ERR_CAPACITY; }
+		}
+		row[n] = (uint32_t)total;
+	}
+	// the log strand concentration of every pair of degeneracy classes (every log() on the host, as everywhere)
+	std::vector<float> &logs = H.logs;
+	logs.assign((size_t)n_cls*n_cls + n_cls, 0.0f);
+	for(uint32_t a = 0;a < n_cls;++a){
+		const float ca = (float)(args->primer_strand/(double)cls_degen[a]);
+		for(uint32_t b = 0;b < n_cls;++b){
+			const float cb = (float)(args->primer_strand/(double)cls_degen[b]);
+			const float strand = (rule == PCR_DIMER_RULE_POOL) ? args->primer_strand                    // pcr_assay.cpp:819-821
+				: ((ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca);                                            // pcr_assay.cpp:244, nuc_cruc.h:832-837
+			if(!(strand > 0.0f)){ g_err = w + "primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
+			logs[(size_t)a*n_cls + b] = logf(strand);
+		}
+		const float own = (rule == PCR_DIMER_RULE_POOL) ? args->primer_strand : ca;                     // valid_pcr.cpp:13
+		if(!(own > 0.0f)){ g_err = w + "primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
+		logs[(size_t)n_cls*n_cls + a] = logf(own);
+	}
+	return PCR_OK;
+}
+
+// The plan's tables as one blob (the caller's, which must outlive the copy) into pdim_in, on the handle's stream -> what the kernels read.
+int pdim_upload_plan(pcr_ctx *ctx, const DimerHostPlan &H, std::vector<uint8_t> &blob, DimerPlan &P)
+{
+	int rc;
+	const size_t ol_bytes = (size_t)H.n*sizeof(DimerOligo), pre_bytes = (size_t)(H.n + 1)*sizeof(uint32_t), log_bytes = H.logs.size()*sizeof(float);
+	blob.resize(ol_bytes + 2*pre_bytes + log_bytes);
+	memcpy(blob.data(), H.ol.data(), ol_bytes);
+	memcpy(blob.data() + ol_bytes, H.pref.data(), pre_bytes);
+	memcpy(blob.data() + ol_bytes + pre_bytes, H.row.data(), pre_bytes);
+	memcpy(blob.data() + ol_bytes + 2*pre_bytes, H.logs.data(), log_bytes);
+	if((rc = ctx->pdim_in.ensure(blob.size())) != PCR_OK) return rc;
+	HIP_TRY(hipMemcpyAsync(ctx->pdim_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+	P.ol = (const DimerOligo *)ctx->pdim_in.p;
+	P.pref = (const uint32_t *)(ctx->pdim_in.p + ol_bytes);
+	P.row = (const uint32_t *)(ctx->pdim_in.p + ol_bytes + pre_bytes);
+	P.log_off = (const float *)(ctx->pdim_in.p + ol_bytes + 2*pre_bytes);
+	P.log_diag = P.log_off + (size_t)H.n_cls*H.n_cls;
+	P.n = H.n; P.n_cls = H.n_cls;
+	return PCR_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -199,58 +294,11 @@ int64_t pcr_pool_dimers(pcr_ctx *ctx, const pcr_pair *pool, uint32_t n_pool, con
 	if(rule != PCR_DIMER_RULE_POOL && rule != PCR_DIMER_RULE_ASSAY){ g_err = "pcr_pool_dimers: unknown rule (PCR_DIMER_RULE_POOL or PCR_DIMER_RULE_ASSAY)"; return PCR_ERR_ARG; }
 	if(!(args->primer_strand > 0.0f)){ g_err = "pcr_pool_dimers: primer_strand must be positive (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
 	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = "pcr_pool_dimers: salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
-	// the distinct oligos, in order of first appearance (as pcr_pool_products)
-	std::vector<DimerOligo> ol;
-	std::vector<uint32_t> cls_degen;                                              // the distinct degeneracies
-	std::map<std::pair<uint64_t, uint64_t>, uint32_t> id_of;
-	for(uint32_t s = 0;s < 2*n_pool;++s){
-		const pcr_word128 &wd = (s & 1) ? pool[s/2].r : pool[s/2].f;
-		auto ins = id_of.insert(std::make_pair(std::make_pair(wd.w[0], wd.w[1]), (uint32_t)ol.size()));
-		if(ins.second){
-			DimerOligo d;
-			d.m = pcrhost::planes_of_word(wd.w);
-			d.start = pcrhost::planes_start(d.m); d.stop = pcrhost::planes_stop(d.m);
-			const uint32_t occ = pcrhost::planes_occupied(d.m);
-			if(!occ || __builtin_popcount(occ) != d.stop - d.start + 1){
-				g_err = "pcr_pool_dimers: an oligo is empty or has a hole between its ends (NucCruc::set_query throws)"; return PCR_ERR_ARG;
-			}
-			const double degen = pcrhost::planes_degeneracy(d.m);
-			if(degen > (double)PCR_SITE_MAX_EXPANSIONS){ g_err = "pcr_pool_dimers: an oligo has more than PCR_SITE_MAX_EXPANSIONS expansions"; return PCR_ERR_ARG; }
-			d.n_exp = (uint32_t)degen;
-			const auto at = std::find(cls_degen.begin(), cls_degen.end(), d.n_exp);
-			d.cls = (uint32_t)(at - cls_degen.begin());
-			if(at == cls_degen.end()) cls_degen.push_back(d.n_exp);
-			ol.push_back(d);
-		}
-		oligo_id[s] = ins.first->second;
-	}
-	const uint32_t n = (uint32_t)ol.size(), n_cls = (uint32_t)cls_degen.size();
-	std::vector<uint32_t> pref(n + 1, 0), row(n + 1, 0);
-	for(uint32_t t = 0;t < n;++t) pref[t + 1] = pref[t] + ol[t].n_exp;            // at most 2 048 * 256
-	{
-		uint64_t total = 0;
-		for(uint32_t q = 0;q < n;++q){
-			row[q] = (uint32_t)total;
-			total += (uint64_t)ol[q].n_exp*(pref[n] - ol[q].n_exp) + ol[q].n_exp;
-			if(total >= (uint64_t(1) << 31)){ g_err = "pcr_pool_dimers: the pool's duplexes number 2^31 or more"; return PCR_ERR_CAPACITY; }
-		}
-		row[n] = (uint32_t)total;
-	}
-	// the log strand concentration of every pair of degeneracy classes (every log() on the host, as everywhere)
-	std::vector<float> logs((size_t)n_cls*n_cls + n_cls);
-	for(uint32_t a = 0;a < n_cls;++a){
-		const float ca = (float)(args->primer_strand/(double)cls_degen[a]);
-		for(uint32_t b = 0;b < n_cls;++b){
-			const float cb = (float)(args->primer_strand/(double)cls_degen[b]);
-			const float strand = (rule == PCR_DIMER_RULE_POOL) ? args->primer_strand                    // pcr_assay.cpp:819-821
-				: ((ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca);                                            // pcr_assay.cpp:244, nuc_cruc.h:832-837
-			if(!(strand > 0.0f)){ g_err = "pcr_pool_dimers: primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
-			logs[(size_t)a*n_cls + b] = logf(strand);
-		}
-		const float own = (rule == PCR_DIMER_RULE_POOL) ? args->primer_strand : ca;                     // valid_pcr.cpp:13
-		if(!(own > 0.0f)){ g_err = "pcr_pool_dimers: primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
-		logs[(size_t)n_cls*n_cls + a] = logf(own);
-	}
+	DimerHostPlan H;
+	{ const int prc = pdim_host_plan("pcr_pool_dimers", pool, n_pool, args, rule, oligo_id, H); if(prc != PCR_OK) return prc; }
+	const std::vector<DimerOligo> &ol = H.ol;
+	const std::vector<uint32_t> &pref = H.pref, &row = H.row;
+	const uint32_t n = H.n;
 	if(!ctx){ g_err = "pcr_pool_dimers: null handle"; return PCR_ERR_ARG; }
 	FLUSH(ctx);
 	HIP_TRY(hipSetDevice(ctx->device));
@@ -260,21 +308,9 @@ int64_t pcr_pool_dimers(pcr_ctx *ctx, const pcr_pair *pool, uint32_t n_pool, con
 	if(keep_all && n_cells > cap) return (int64_t)n_cells;                        // count only: no thermodynamics needed, out is left as it is
 	// ---- the tables
 	int rc;
-	const size_t ol_bytes = (size_t)n*sizeof(DimerOligo), pre_bytes = (size_t)(n + 1)*sizeof(uint32_t), log_bytes = logs.size()*sizeof(float);
-	std::vector<uint8_t> blob(ol_bytes + 2*pre_bytes + log_bytes);
-	memcpy(blob.data(), ol.data(), ol_bytes);
-	memcpy(blob.data() + ol_bytes, pref.data(), pre_bytes);
-	memcpy(blob.data() + ol_bytes + pre_bytes, row.data(), pre_bytes);
-	memcpy(blob.data() + ol_bytes + 2*pre_bytes, logs.data(), log_bytes);
-	if((rc = ctx->pdim_in.ensure(blob.size())) != PCR_OK) return rc;
-	HIP_TRY(hipMemcpyAsync(ctx->pdim_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+	std::vector<uint8_t> blob;
 	DimerPlan P;
-	P.ol = (const DimerOligo *)ctx->pdim_in.p;
-	P.pref = (const uint32_t *)(ctx->pdim_in.p + ol_bytes);
-	P.row = (const uint32_t *)(ctx->pdim_in.p + ol_bytes + pre_bytes);
-	P.log_off = (const float *)(ctx->pdim_in.p + ol_bytes + 2*pre_bytes);
-	P.log_diag = P.log_off + (size_t)n_cls*n_cls;
-	P.n = n; P.n_cls = n_cls;
+	if((rc = pdim_upload_plan(ctx, H, blob, P)) != PCR_OK) return rc;
 	if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
 	if(!ctx->pdim_attr_set){
 		HIP_TRY(hipFuncSetAttribute((const void *)k_pool_dimer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PDIM_LDS));

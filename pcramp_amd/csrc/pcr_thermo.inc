@@ -665,7 +665,7 @@ template<bool HAIRPIN> __device__ float enumerate_parallel(Engine<1> &e, ParLane
 	wave_sync();
 	float tm = 0.0f;
 	if(lane == 0){
-		// (k_site_tm, pcr_site_tm.inc, and k_pool_dimer, pcr_pool_dimers.inc, repeat this merge to take the winner's dH and dS: change the three together)
+		// (k_site_tm, pcr_site_tm.inc, and pdim_winner, pcr_pool_dimers.inc, repeat this merge to take the winner's dH and dS: change the three together)
 		int win = -1;
 		float wdg = 0.0f;
 		for(int l = 0;l < WAVE_PAR;++l){
