@@ -785,7 +785,7 @@ typedef struct {
  * expansions).  PCR_ERR_CAPACITY as pcr_pool_dimers.  Then a null handle.  PCR_ERR_RANGE if a trace-back fails.
  *   Needs no sequence set and no word DB, changes nothing other calls read, makes no collective on a sharded handle.
  *   Out of scope: anchors with gaps or bulges, or a mismatch inside the run; hairpin self-priming of a single strand;
- * treating probes (3'-blocked oligos) differently; and pcr_pool_conflicts, whose dimer half still reads pcr_pool_dimers. */
+ * treating probes (3'-blocked oligos) differently.  pcr_pool_conflicts_ext reduces these cells to pairs of pool rows. */
 int64_t pcr_pool_dimers_end3(pcr_ctx *ctx, const pcr_pair *pool, uint32_t n_pool, const pcr_thermo_args *args, int rule,
 	uint32_t min_run, uint32_t min_extension, float dg_max, uint32_t *oligo_id,
 	pcr_pool_dimer_end3 *out, uint64_t cap, pcr_dimer_placement *place_out, uint64_t place_cap, uint64_t *n_place);
@@ -1041,6 +1041,63 @@ int64_t pcr_pool_conflicts(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, ui
 int64_t pcr_pool_conflicts_end3(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
 	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor,
 	const pcr_end3_rule *rule, int dimer_rule, float dimer_floor, uint32_t *oligo_id, pcr_pool_conflict *out, uint64_t cap);
+
+typedef struct {            /* how pcr_pool_conflicts_ext looks for extensible dimers; NULL = it does not */
+	int32_t  rule;          /* PCR_DIMER_RULE_POOL / PCR_DIMER_RULE_ASSAY: pcr_pool_dimers_end3's strand-concentration rule */
+	uint32_t min_run;       /* 3 .. 32 */
+	uint32_t min_extension; /* 0 .. 31 */
+	float    dg_max;        /* +INFINITY keeps every qualifying placement; NaN refused */
+} pcr_dimer_end3_args;
+
+typedef struct {            /* one unordered pair of pool rows (96 bytes) */
+	pcr_pool_conflict c;                              /* as pcr_pool_conflicts_end3 computes it; PCR_CONFLICT_EXTENSION added to c.flags */
+	uint32_t ext_cells;                               /* distinct ordered dimer cells of {a, b} with at least one kept placement (dG <= dg_max) */
+	uint32_t ext_placements;                          /* n_placements summed over the distinct dimer cells of {a, b}, before the dG filter */
+	uint32_t ext_query, ext_target;                   /* the ordered cell (q, t) that holds the best placement */
+	uint32_t ext_q_expansion, ext_t_expansion;        /* the best placement's duplex ... */
+	uint8_t  ext_run, ext_extension, ext_overlap, ext_overlap_matches;   /* ... its geometry ... */
+	uint32_t ext_flags;                               /* ... PCR_DIMER_HOMO, PCR_DIMER_END3_MUTUAL ... */
+	float    ext_dG, ext_tm, ext_dH, ext_dS;          /* ... and energies: that cell's pcr_pool_dimer_end3 record */
+} pcr_pool_conflict_ext;
+
+#define PCR_CONFLICT_EXTENSION 4u   /* in c.flags: ext_cells > 0 */
+
+/* pcr_pool_conflicts_end3 with a third half: the 3'-extensible dimers of pcr_pool_dimers_end3, reduced on the device to the
+ * unordered pairs of pool rows.  dimer_tm says how well two whole oligos stick; the extension half says whether a polymerase
+ * can copy one oligo off the other, which is what makes a primer-dimer artefact.
+ *   Base half.  c is what pcr_pool_conflicts_end3 computes for the same handle state, pool, threshold, amplicon range, args,
+ * template_strand, tm_floor, rule, dimer_rule and dimer_floor, byte for byte, also in a cell that call would not have kept
+ * (its products, melt and dimer fields are computed all the same; PCR_CONFLICT_DIMER is tested against dimer_floor).
+ * PCR_CONFLICT_EXTENSION is OR-ed into c.flags afterwards.
+ *   Extension half.  Only with ext != NULL.  The dimer cells of {a, b} are pcr_pool_conflicts': the ordered (q, t) with
+ * (q in O(a), t in O(b)) or (q in O(b), t in O(a)).  That list of up to eight has repeats when a = b, when a row has F = R
+ * or when the rows share an oligo; every distinct ordered cell counts once.  For each, take the cell record of
+ * pcr_pool_dimers_end3(pool, args, ext->rule, ext->min_run, ext->min_extension, ext->dg_max), bit for bit.  ext_placements
+ * is the sum of their n_placements (before the dG filter); ext_cells is the number of them that call keeps (at least one
+ * placement with dG <= dg_max).  The best placement of {a, b} is the best of the kept cells' best placements: the lowest
+ * dG, then the longer run, then the lowest (q, t).  The fields ext_query .. ext_dS are that cell record's; with
+ * ext_cells = 0 they are all zero, and ext_placements may still be positive (every placement failed dg_max).  No placement
+ * records are listed.  dimer_rule and ext are independent: PCR_CONFLICT_NO_DIMERS with ext set runs no whole-oligo
+ * thermodynamics, and ext->rule need not be dimer_rule.
+ *   Records.  One for every cell pcr_pool_conflicts_end3 keeps and for every cell with ext_cells > 0, sorted by
+ * (row_a, row_b).  With ext = NULL the record set and every c are pcr_pool_conflicts_end3's, byte for byte, and all ext
+ * fields are zero.  Each cell is reduced by one thread that walks its distinct dimer cells in (q, t) order: no atomics, the
+ * bytes do not depend on the order the device works in.
+ *   Returns the number of records or a negative error; if it exceeds cap the contents of out are unspecified (cap = 0:
+ * count only).  n_pool = 0 returns 0.
+ *   PCR_ERR_ARG, from the arguments alone and before the handle: pcr_pool_conflicts_end3's checks in its order; then, with
+ * ext set: an ext->rule that is neither PCR_DIMER_RULE_POOL nor PCR_DIMER_RULE_ASSAY; min_run outside 3 .. 32;
+ * min_extension above 31; dg_max NaN; primer_strand <= 0 or primer_strand / degeneracy underflowing to zero under
+ * ext->rule; then a null handle.  PCR_ERR_STATE without a word DB, also when only the extension half would produce
+ * records.  PCR_ERR_CAPACITY as pcr_pool_conflicts_end3, and with ext set for 2^31 or more duplexes; PCR_ERR_RANGE if a
+ * trace-back fails inside the engine.  The dense matrix of cell records takes 48 bytes per ordered pair of distinct oligos
+ * on the device.  Changes nothing other calls read.  On a handle with a target shard attached, sequence
+ * indices are local to the rank's block and no collective is made.
+ *   Out of scope: probes as 3'-blocked oligos; gapped or mismatched anchors; hairpin self-priming. */
+int64_t pcr_pool_conflicts_ext(pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
+	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor,
+	const pcr_end3_rule *rule, int dimer_rule, float dimer_floor, const pcr_dimer_end3_args *ext,
+	uint32_t *oligo_id, pcr_pool_conflict_ext *out, uint64_t cap);
 
 /* ---- Probe hits: which products of a pool a panel's hydrolysis probes bind inside, and which sequences each assay detects */
 

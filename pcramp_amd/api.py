@@ -134,6 +134,15 @@ POOL_CONFLICT_DTYPE = np.dtype([("row_a", np.uint32), ("row_b", np.uint32), ("pr
 CONFLICT_PRODUCT, CONFLICT_DIMER = 1, 2       # PCR_CONFLICT_PRODUCT, PCR_CONFLICT_DIMER
 CONFLICT_NO_DIMERS = -1                       # PCR_CONFLICT_NO_DIMERS
 
+# pcr_pool_conflict_ext: pcr_pool_conflict's twelve fields, then the extensible-dimer half (Screener.pool_conflicts with
+# ext_min_run > 0); 96 bytes
+POOL_CONFLICT_EXT_DTYPE = np.dtype(POOL_CONFLICT_DTYPE.descr + [
+    ("ext_cells", np.uint32), ("ext_placements", np.uint32), ("ext_query", np.uint32), ("ext_target", np.uint32),
+    ("ext_q_expansion", np.uint32), ("ext_t_expansion", np.uint32), ("ext_run", np.uint8), ("ext_extension", np.uint8),
+    ("ext_overlap", np.uint8), ("ext_overlap_matches", np.uint8), ("ext_flags", np.uint32), ("ext_dG", np.float32),
+    ("ext_tm", np.float32), ("ext_dH", np.float32), ("ext_dS", np.float32)])
+CONFLICT_EXTENSION = 4                        # PCR_CONFLICT_EXTENSION
+
 # pcr_probe_hit: one probe site inside one product (Screener.probe_hits)
 PROBE_HIT_DTYPE = np.dtype([("plus_oligo", np.uint32), ("minus_oligo", np.uint32), ("probe", np.uint32), ("sequence", np.uint32),
                             ("begin", np.int32), ("end", np.int32), ("inner_start", np.int32), ("inner_length", np.int32),
@@ -190,6 +199,11 @@ class AssayRecord(C.Structure):
                 ("num_active_background", C.c_uint32), ("target_match", C.c_void_p), ("background_match", C.c_void_p)]
 
 
+class DimerEnd3Args(C.Structure):
+    """pcr_dimer_end3_args"""
+    _fields_ = [("rule", C.c_int32), ("min_run", C.c_uint32), ("min_extension", C.c_uint32), ("dg_max", C.c_float)]
+
+
 class End3Rule(C.Structure):
     _fields_ = [("min_clamp3", C.c_uint32), ("window", C.c_uint32), ("max_end_mismatch", C.c_uint32),
                 ("use_taq_mama", C.c_int32), ("ident_threshold", C.c_float)]
@@ -218,7 +232,7 @@ ABI_SYMBOLS = [
     "pcr_random_assays", "pcr_host_rand_r", "pcr_host_max_overlap", "pcr_host_oligo_overlap", "pcr_host_pool_overlaps",
     "pcr_multiplex_load", "pcr_multiplex_coverage", "pcr_collect_amplicons", "pcr_pool_products", "pcr_site_tm", "pcr_pool_dimers", "pcr_pool_dimers_end3",
     "pcr_pool_products_tm", "pcr_pool_products_end3", "pcr_pool_anneal_profile", "pcr_pool_conflicts", "pcr_pool_probe_hits",
-    "pcr_pool_anneal_profile_end3", "pcr_pool_conflicts_end3", "pcr_pool_probe_hits_end3", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants", "pcr_site_repair",
+    "pcr_pool_anneal_profile_end3", "pcr_pool_conflicts_end3", "pcr_pool_conflicts_ext", "pcr_pool_probe_hits_end3", "pcr_pool_amplicons", "pcr_pool_probe_candidates", "pcr_site_variants", "pcr_site_repair",
     "pcr_format_oligos", "pcr_format_header", "pcr_format_preamble", "pcr_format_iteration", "pcr_format_assay", "pcr_format_footer",
     "pcr_optimize_batch", "pcr_optimization_move", "pcr_make_degenerate", "pcr_staging_mode", "pcr_launcher_stats", "pcr_live_resources",
     "pcr_design", "pcr_design_output", "pcr_comm_init_host", "pcr_shard_targets", "pcr_shard_combine_mode",
@@ -340,6 +354,10 @@ def load_library():
     L.pcr_pool_conflicts_end3.restype = C.c_int64
     L.pcr_pool_conflicts_end3.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
                                           C.c_float, C.c_float, C.POINTER(End3Rule), C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.pcr_pool_conflicts_ext.restype = C.c_int64
+    L.pcr_pool_conflicts_ext.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32, C.POINTER(ThermoArgs),
+                                         C.c_float, C.c_float, C.POINTER(End3Rule), C.c_int, C.c_float, C.POINTER(DimerEnd3Args),
+                                         C.c_void_p, C.c_void_p, C.c_uint64]
     L.pcr_pool_probe_hits.restype = C.c_int64
     L.pcr_pool_probe_hits.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_int32,
                                       C.POINTER(ThermoArgs), C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
@@ -704,13 +722,17 @@ def anneal_ceiling(points, pair_sequences, keep=1.0):
     return int(ok[-1]) if len(ok) else -1
 
 
-def conflict_matrix(conflicts, n_pool, anneal=None, max_dimer=None):
-    """Screener.pool_conflicts' records -> bool [n_pool, n_pool], symmetric: which pairs of pool rows conflict.  A cell is set
-    iff it has products and (anneal is None or melt >= anneal, in float32), or max_dimer is not None and the record carries
-    CONFLICT_DIMER and dimer_tm >= max_dimer.  The diagonal is an assay against itself."""
+def conflict_matrix(conflicts, n_pool, anneal=None, max_dimer=None, max_extension_dg=None):
+    """Screener.pool_conflicts' records (either dtype) -> bool [n_pool, n_pool], symmetric: which pairs of pool rows conflict.
+    A cell is set iff it has products and (anneal is None or melt >= anneal, in float32), or max_dimer is not None and the
+    record carries CONFLICT_DIMER and dimer_tm >= max_dimer, or max_extension_dg is not None and the record carries
+    CONFLICT_EXTENSION and ext_dG <= max_extension_dg (POOL_CONFLICT_EXT_DTYPE records only: ValueError otherwise).  The
+    diagonal is an assay against itself."""
     n = int(n_pool)
     m = np.zeros((n, n), bool)
     c = np.asarray(conflicts)
+    if max_extension_dg is not None and (c.dtype.names is None or "ext_dG" not in c.dtype.names):
+        raise ValueError("conflict_matrix: max_extension_dg needs POOL_CONFLICT_EXT_DTYPE records (pool_conflicts with ext_min_run > 0)")
     if len(c) == 0:
         return m
     hit = c["products"] > 0
@@ -718,6 +740,8 @@ def conflict_matrix(conflicts, n_pool, anneal=None, max_dimer=None):
         hit &= c["melt"] >= np.float32(anneal)
     if max_dimer is not None:
         hit |= ((c["flags"] & CONFLICT_DIMER) != 0) & (c["dimer_tm"] >= np.float32(max_dimer))
+    if max_extension_dg is not None:
+        hit |= ((c["flags"] & CONFLICT_EXTENSION) != 0) & (c["ext_dG"] <= np.float32(max_extension_dg))
     a, b = c["row_a"][hit].astype(np.int64), c["row_b"][hit].astype(np.int64)
     m[a, b] = True
     m[b, a] = True
@@ -1393,7 +1417,8 @@ class Screener:
 
     def pool_conflicts(self, pool, threshold=1.0, tm_floor=0.0, salt=0.05, primer_strand=9e-7, template_strand=0.0,
                        amp_min=80, amp_max=200, dimers="pool", dimer_floor=0.0, which=TARGET, select=False, cap=None,
-                       min_clamp3=0, window=0, max_end_mismatch=0, use_taq_mama=False, ident_threshold=0.0):
+                       min_clamp3=0, window=0, max_end_mismatch=0, use_taq_mama=False, ident_threshold=0.0,
+                       ext_min_run=0, ext_min_extension=1, ext_dg_max=None, ext_rule=None):
         """Which assays of the pool cannot share a tube (pcr_pool_conflicts) -> (oligo_id uint32[2 * len(pool)], conflicts:
         POOL_CONFLICT_DTYPE array sorted by (row_a, row_b)).
 
@@ -1408,11 +1433,26 @@ class Screener:
         assign_tubes turn the records into a split of the pool.  min_clamp3, window, max_end_mismatch, use_taq_mama and
         ident_threshold are pool_products_end3's 3'-end rule (pcr_pool_conflicts_end3): with any of them set, only spurious
         products that also pass it are attributed -- a cross product the polymerase does not extend is no conflict.  The
-        dimer fields do not depend on the rule."""
+        dimer fields do not depend on the rule.
+
+        ext_min_run > 0 (pcr_pool_conflicts_ext) adds the 3'-extensible dimers of pool_dimers_end3(min_run=ext_min_run,
+        min_extension=ext_min_extension, dg_max=ext_dg_max, rule=ext_rule) between the oligos of the two rows and returns
+        POOL_CONFLICT_EXT_DTYPE records: the fields above, then ext_cells (distinct oligo-by-oligo cells with a placement at
+        or below ext_dg_max), ext_placements (qualifying placements before that filter) and the best placement (lowest dG,
+        then the longer run, then the lowest (ext_query, ext_target)) as that cell's record; zero where ext_cells is 0.  A
+        pair with ext_cells > 0 carries CONFLICT_EXTENSION and has a record whatever the other halves say.  ext_rule=None
+        takes the rule of `dimers` ("pool" when dimers is None), ext_dg_max=None keeps every placement.  dimers=None with
+        ext_min_run set runs no whole-oligo thermodynamics."""
         rules = {"pool": DIMER_RULE_POOL, "assay": DIMER_RULE_ASSAY, None: CONFLICT_NO_DIMERS, DIMER_RULE_POOL: DIMER_RULE_POOL,
                  DIMER_RULE_ASSAY: DIMER_RULE_ASSAY, CONFLICT_NO_DIMERS: CONFLICT_NO_DIMERS}
         if dimers not in rules:
             raise ValueError("pool_conflicts: dimers must be 'pool', 'assay' or None")
+        ext = None
+        if ext_min_run:
+            xr = ext_rule if ext_rule is not None else (dimers if rules[dimers] != CONFLICT_NO_DIMERS else "pool")
+            if xr not in rules or rules[xr] == CONFLICT_NO_DIMERS:
+                raise ValueError("pool_conflicts: ext_rule must be 'pool', 'assay' or None")
+            ext = DimerEnd3Args(rules[xr], int(ext_min_run), int(ext_min_extension), float("inf") if ext_dg_max is None else float(ext_dg_max))
         thr2 = float(np.float32(threshold) * np.float32(threshold))
         if isinstance(select, str):
             if select != "all":
@@ -1426,7 +1466,10 @@ class Screener:
         head = (self.h, which, a.ctypes.data, len(pool), float(threshold), int(amp_min), int(amp_max), C.byref(args), float(template_strand),
                 float(tm_floor))
         rule = _end3_rule(min_clamp3, window, max_end_mismatch, use_taq_mama, ident_threshold)
-        if rule is None:
+        if ext is not None:
+            call = lambda out, cap: self.L.pcr_pool_conflicts_ext(*head, C.byref(rule) if rule is not None else None, rules[dimers],
+                                                                  float(dimer_floor), C.byref(ext), ids.ctypes.data, out, cap)
+        elif rule is None:
             call = lambda out, cap: self.L.pcr_pool_conflicts(*head, rules[dimers], float(dimer_floor), ids.ctypes.data, out, cap)
         else:
             call = lambda out, cap: self.L.pcr_pool_conflicts_end3(*head, C.byref(rule), rules[dimers], float(dimer_floor),
@@ -1437,7 +1480,7 @@ class Screener:
                 raise PcrError(_err(self.L))
             cap = int(n)
         while True:
-            out = np.zeros(max(cap, 1), POOL_CONFLICT_DTYPE)
+            out = np.zeros(max(cap, 1), POOL_CONFLICT_DTYPE if ext is None else POOL_CONFLICT_EXT_DTYPE)
             n = call(out.ctypes.data, cap)
             if n < 0:
                 raise PcrError(_err(self.L))

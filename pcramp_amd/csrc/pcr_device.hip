@@ -892,6 +892,9 @@ struct pcr_ctx {
 	DevBuf<uint32_t> pde3_cnt, pde3_off, pde3_keep, pde3_koff; DevBuf<uint2> pde3_jobs; DevBuf<float4> pde3_res;
 	DevBuf<pcr_pool_dimer_end3> pde3_rec, pde3_out; DevBuf<pcr_dimer_placement> pde3_place;
 	bool pde3_attr_set = false;
+	// pcr_pool_conflicts_ext (pcr_pool_conflicts_ext.inc), beside pcf_* and pde3_*: the dense n_ol x n_ol matrix of pcr_pool_dimers_end3's cell
+	// records, the cells' 96-byte records and the kept ones.
+	DevBuf<pcr_pool_dimer_end3> pcx_dense; DevBuf<pcr_pool_conflict_ext> pcx_rec, pcx_out;
 };
 
 namespace {
@@ -2222,6 +2225,7 @@ int64_t pcr_host_move_trials(const pcr_word128 *oligo, int move, double max_dege
 #include "pcr_products_end3.inc"
 #include "pcr_anneal_profile.inc"
 #include "pcr_pool_conflicts.inc"
+#include "pcr_pool_conflicts_ext.inc"
 #include "pcr_probe_hits.inc"
 #include "pcr_pool_amplicons.inc"
 #include "pcr_probe_candidates.inc"

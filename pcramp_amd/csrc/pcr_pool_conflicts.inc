@@ -23,6 +23,8 @@
 // pcr_pool_conflicts_end3 is the same call with a 3'-end rule (pcr_products_end3.inc, included before this file) on the products
 // of steps 1-6: k_item_end3 fills an ItemEnd per item before the melt, and the join's functor makes k_end3_join's tests behind
 // the floor.  Steps 7 and 8 do not know the rule.
+// pcr_pool_conflicts_ext (pcr_pool_conflicts_ext.inc, included after this file) is pool_conflicts_impl as well: with a ConflictExt
+// the arguments of ext are checked behind the rule's, and after step 8 conflict_ext_tail takes over from pcf_rec and pcf_keep.
 
 #include <rocprim/device/device_reduce_by_key.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -371,17 +373,55 @@ int conflict_dimers(const std::string &who, pcr_ctx *ctx, const pcr_thermo_args 
 	return PCR_OK;
 }
 
-// pcr_pool_conflicts (rule = NULL) and pcr_pool_conflicts_end3; who: the entry point's name, for the refusals
+// What pcr_pool_dimers asks of primer_strand under `rule`, and its log strand concentrations: the degeneracy class of every oligo
+// (q.cls, cls_degen) and logs[n_cls*n_cls + n_cls] as pdim_host_plan lays them out.  what: the argument that asked, for the refusals.
+int conflict_dimer_logs(const std::string &who, const char *what, const pcr_thermo_args *args, int rule, std::vector<DimerOligo> &dol,
+	std::vector<uint32_t> &cls_degen, std::vector<float> &logs)
+{
+	if(!(args->primer_strand > 0.0f)){ g_err = who + ": with " + what + " primer_strand must be positive (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
+	cls_degen.clear();
+	for(DimerOligo &q : dol){
+		const auto at = std::find(cls_degen.begin(), cls_degen.end(), q.n_exp);
+		q.cls = (uint32_t)(at - cls_degen.begin());
+		if(at == cls_degen.end()) cls_degen.push_back(q.n_exp);
+	}
+	const uint32_t n_cls = (uint32_t)cls_degen.size();
+	logs.assign((size_t)n_cls*n_cls + n_cls, 0.0f);
+	for(uint32_t a = 0;a < n_cls;++a){
+		const float ca = (float)(args->primer_strand/(double)cls_degen[a]);
+		for(uint32_t b = 0;b < n_cls;++b){
+			const float cb = (float)(args->primer_strand/(double)cls_degen[b]);
+			const float strand = (rule == PCR_DIMER_RULE_POOL) ? args->primer_strand                      // pcr_assay.cpp:819-821
+				: ((ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca);                                            // pcr_assay.cpp:244, nuc_cruc.h:832-837
+			if(!(strand > 0.0f)){ g_err = who + ": primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
+			logs[(size_t)a*n_cls + b] = logf(strand);
+		}
+		const float own = (rule == PCR_DIMER_RULE_POOL) ? args->primer_strand : ca;                       // valid_pcr.cpp:13
+		if(!(own > 0.0f)){ g_err = who + ": primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
+		logs[(size_t)n_cls*n_cls + a] = logf(own);
+	}
+	return PCR_OK;
+}
+
+// pcr_pool_conflicts_ext's side of pool_conflicts_impl (pcr_pool_conflicts_ext.inc): its arguments, and the tail that joins the
+// extension half to the cells' records (pcf_rec, pcf_keep) and hands out the 96-byte records.
+struct ConflictExt { const pcr_dimer_end3_args *ext; pcr_pool_conflict_ext *out; };
+int conflict_ext_check(const std::string &who, const pcr_dimer_end3_args *ext);
+int64_t conflict_ext_tail(const std::string &who, pcr_ctx *ctx, const pcr_thermo_args *args, const ConflictExt &X, const DimerHostPlan *H,
+	const uint2 *d_row_ol, uint32_t n_pool, uint32_t n_cells, uint64_t cap);
+
+// pcr_pool_conflicts (rule = NULL), pcr_pool_conflicts_end3 and, with X, pcr_pool_conflicts_ext (out = NULL then: the records go
+// to X->out); who: the entry point's name, for the refusals
 int64_t pool_conflicts_impl(const std::string &who, pcr_ctx *ctx, pcr_set which, const pcr_pair *pool, uint32_t n_pool, float threshold,
 	int32_t amp_min, int32_t amp_max, const pcr_thermo_args *args, float template_strand, float tm_floor, const pcr_end3_rule *rule,
-	int dimer_rule, float dimer_floor, uint32_t *oligo_id, pcr_pool_conflict *out, uint64_t cap)
+	int dimer_rule, float dimer_floor, uint32_t *oligo_id, pcr_pool_conflict *out, uint64_t cap, const ConflictExt *X = nullptr)
 {
 	static_assert(sizeof(pcr_pool_conflict) == 48, "record layout");
 	static_assert(sizeof(ConflictAgg) == 16 && sizeof(uint4) == 16, "the dense array is kept as uint4");
 	// ---- the arguments, before the handle (pcr_pool_products_tm's checks in its order, the oligo table, then the dimer arguments)
 	if(!set_ok(which)){ g_err = who + ": unknown sequence set"; return PCR_ERR_ARG; }
 	if(which != PCR_SET_TARGET && which != PCR_SET_BACKGROUND){ g_err = who + ": PCR_SET_MULTIPLEX is not supported (PCR_SET_TARGET or PCR_SET_BACKGROUND)"; return PCR_ERR_ARG; }
-	if(!args || (n_pool && (!pool || !oligo_id)) || (cap && !out)){ g_err = who + ": bad argument"; return PCR_ERR_ARG; }
+	if(!args || (n_pool && (!pool || !oligo_id)) || (cap && !(X ? (const void *)X->out : (const void *)out))){ g_err = who + ": bad argument"; return PCR_ERR_ARG; }
 	if(n_pool > PCR_POOL_MAX_PAIRS){ g_err = who + ": pool larger than PCR_POOL_MAX_PAIRS"; return PCR_ERR_ARG; }
 	if(!(template_strand >= 0.0f) || !(args->primer_strand >= 0.0f)){ g_err = who + ": negative strand concentration (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
 	if(!(args->salt >= 1.0e-6f && args->salt <= 1.0f)){ g_err = who + ": salt outside [1e-6, 1] (NucCruc::salt, nuc_cruc.h:780-788)"; return PCR_ERR_ARG; }
@@ -406,33 +446,20 @@ int64_t pool_conflicts_impl(const std::string &who, pcr_ctx *ctx, pcr_set which,
 	// with a dimer rule, what pcr_pool_dimers asks of the arguments: its strand concentrations, per pair of degeneracy classes
 	std::vector<uint32_t> cls_degen, pref, row;
 	std::vector<float> logs;
-	if(dimers){
-		if(!(args->primer_strand > 0.0f)){ g_err = who + ": with a dimer rule primer_strand must be positive (NucCruc::strand, nuc_cruc.h:818-826)"; return PCR_ERR_ARG; }
-		for(DimerOligo &q : dol){
-			const auto at = std::find(cls_degen.begin(), cls_degen.end(), q.n_exp);
-			q.cls = (uint32_t)(at - cls_degen.begin());
-			if(at == cls_degen.end()) cls_degen.push_back(q.n_exp);
-		}
-		const uint32_t n_cls = (uint32_t)cls_degen.size();
-		logs.resize((size_t)n_cls*n_cls + n_cls);
-		for(uint32_t a = 0;a < n_cls;++a){
-			const float ca = (float)(args->primer_strand/(double)cls_degen[a]);
-			for(uint32_t b = 0;b < n_cls;++b){
-				const float cb = (float)(args->primer_strand/(double)cls_degen[b]);
-				const float strand = (dimer_rule == PCR_DIMER_RULE_POOL) ? args->primer_strand                  // pcr_assay.cpp:819-821
-					: ((ca > cb) ? ca - 0.5f*cb : cb - 0.5f*ca);                                            // pcr_assay.cpp:244, nuc_cruc.h:832-837
-				if(!(strand > 0.0f)){ g_err = who + ": primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
-				logs[(size_t)a*n_cls + b] = logf(strand);
-			}
-			const float own = (dimer_rule == PCR_DIMER_RULE_POOL) ? args->primer_strand : ca;                   // valid_pcr.cpp:13
-			if(!(own > 0.0f)){ g_err = who + ": primer_strand / degeneracy underflows to zero"; return PCR_ERR_ARG; }
-			logs[(size_t)n_cls*n_cls + a] = logf(own);
-		}
-	}
+	if(dimers && conflict_dimer_logs(who, "a dimer rule", args, dimer_rule, dol, cls_degen, logs) != PCR_OK) return PCR_ERR_ARG;
 	End3Rule R;
 	int use_taq;
 	if(end3_rule_of(who, rule, R, use_taq) != PCR_OK) return PCR_ERR_ARG;
 	const bool ruled = end3_ruled(R);                                            // else: no ItemEnd is computed, the join is the base call's
+	// with ext, what pcr_pool_dimers_end3 asks of its arguments, and its plan of the same oligos under ext->rule
+	const bool extend = X && X->ext;
+	DimerHostPlan XH;
+	if(extend){
+		if(conflict_ext_check(who, X->ext) != PCR_OK) return PCR_ERR_ARG;
+		std::vector<uint32_t> xcls;
+		if(conflict_dimer_logs(who, "ext", args, X->ext->rule, dol, xcls, XH.logs) != PCR_OK) return PCR_ERR_ARG;   // (the classes are the same under every rule)
+		XH.n_cls = (uint32_t)xcls.size();
+	}
 	if(!ctx){ g_err = who + ": null handle"; return PCR_ERR_ARG; }
 	{ const int drc = drain(ctx); if(drc != PCR_OK) return drc; }
 	HIP_TRY(hipSetDevice(ctx->device));
@@ -440,7 +467,7 @@ int64_t pool_conflicts_impl(const std::string &who, pcr_ctx *ctx, pcr_set which,
 	if(!S.have_db){ g_err = who + ": no word DB (call pcr_select_words or pcr_select_sites first)"; return PCR_ERR_STATE; }
 	if(n_pool == 0) return 0;
 	const uint32_t n_ol = (uint32_t)ol.size();
-	if(dimers){
+	if(dimers || extend){
 		// pcr_pool_dimers' duplex numbering: pref[t] = expansions of the oligos before t; row[q] = duplexes of the rows before q
 		pref.assign(n_ol + 1, 0); row.assign(n_ol + 1, 0);
 		for(uint32_t t = 0;t < n_ol;++t) pref[t + 1] = pref[t] + dol[t].n_exp;
@@ -452,6 +479,7 @@ int64_t pool_conflicts_impl(const std::string &who, pcr_ctx *ctx, pcr_set which,
 		}
 		row[n_ol] = (uint32_t)total;
 	}
+	if(extend){ XH.ol = dol; XH.pref = pref; XH.row = row; XH.n = n_ol; }
 	{ const int erc = ensure_touched(ctx, S); if(erc != PCR_OK) return erc; }
 	int rc;
 	const uint32_t n_cells = n_pool*(n_pool + 1u)/2u;
@@ -470,6 +498,7 @@ int64_t pool_conflicts_impl(const std::string &who, pcr_ctx *ctx, pcr_set which,
 		(const ConflictAgg *)ctx->pcf_dense.p, dimers ? (const float *)ctx->pcf_dmat.p : (const float *)nullptr, n_ol, d_row_ol, n_pool, dimer_floor,
 		ctx->pcf_rec.p, ctx->pcf_keep.p);
 	HIP_TRY(hipGetLastError());
+	if(X) return conflict_ext_tail(who, ctx, args, *X, extend ? &XH : nullptr, d_row_ol, n_pool, n_cells, cap);
 	uint32_t kept = 0;
 	if((rc = scan_total(ctx, ctx->pcf_keep.p, ctx->pcf_koff, ctx->shared.tmp, n_cells, kept)) != PCR_OK) return rc;
 	if(kept == 0 || kept > cap) return (int64_t)kept;                            // count only: out is left as it is

@@ -20,6 +20,8 @@
 // Cells go in batches of consecutive whole cells of at most POOL_DIMER_END3_BATCH_DUPLEXES duplexes (DESIGN.md has the bounds).
 // The call owns its scratch (pcr_ctx::pde3_*, and pdim_in / pdim_tmp / pdim_flag, which every call fills anew); the dG table
 // is the handle's (th_dg, keyed by its salt).
+// The batch loop is end3_batches, which pcr_pool_conflicts_ext runs too, with a dense device array in place of the caller's
+// host arrays (End3Out): then a batch's records are merged where they stay and nothing is compacted or downloaded.
 
 namespace {
 
@@ -253,6 +255,155 @@ int end3_scan(pcr_ctx *ctx, uint32_t *keep, uint32_t *koff, uint32_t n, uint32_t
 	return PCR_OK;
 }
 
+// Where end3_batches leaves what it computes: the caller's arrays on the host (pcr_pool_dimers_end3), or `dense` on the device
+// (pcr_pool_conflicts_ext): n*n cell records, cell c = q*n + t at [c], every cell's final record whether or not the filter
+// keeps it (a cell without placements: its ids, n_duplexes and PCR_DIMER_HOMO, zero elsewhere).  With dense the batch's records
+// are merged in place there; nothing is kept, compacted or downloaded and no placement is listed.
+struct End3Out {
+	pcr_pool_dimer_end3 *out = nullptr; uint64_t cap = 0;
+	pcr_dimer_placement *place_out = nullptr; uint64_t place_cap = 0;
+	pcr_pool_dimer_end3 *dense = nullptr;
+};
+
+// The batch loop of pcr_pool_dimers_end3 over the n*n cells of the plan H (n > 0; the caller has checked the arguments, flushed
+// the handle and set the device): scan<false>, scan, cells, scan<true>, melt, merge, keep / compact.  who begins the messages.
+// kept_total = the kept cells, place_total = the kept placements (both 0 with O.dense).
+int end3_batches(const char *who, pcr_ctx *ctx, const DimerHostPlan &H, const pcr_thermo_args *args, uint32_t min_run, uint32_t min_extension,
+	float dg_max, const End3Out &O, uint64_t &kept_total, uint64_t &place_total)
+{
+	pcr_pool_dimer_end3 *const out = O.out;
+	pcr_dimer_placement *const place_out = O.place_out;
+	const uint64_t cap = O.cap, place_cap = O.place_cap;
+	const bool dense = O.dense != nullptr;
+	const uint32_t n = H.n;
+	const uint64_t n_cells = (uint64_t)n*n;
+	const bool keep_all = dg_max == INFINITY;
+	// ---- the tables
+	int rc;
+	std::vector<uint8_t> blob;
+	DimerPlan P;
+	if((rc = pdim_upload_plan(ctx, H, blob, P)) != PCR_OK) return rc;
+	if((rc = ctx->pdim_flag.ensure(1)) != PCR_OK) return rc;
+	HIP_TRY(hipMemsetAsync(ctx->pdim_flag.p, 0, sizeof(uint32_t), ctx->stream));
+	bool tables = false;                                                          // the dG table and the kernel's LDS size: only once something is melted
+	// duplexes before cell c (c = n_cells: all of them)
+	auto before = [&](uint64_t c) -> uint32_t {
+		if(c >= n_cells) return H.row[n];
+		const uint32_t q = (uint32_t)(c/n), t = (uint32_t)(c % n);
+		return pdim_before(H.row.data(), H.pref.data(), q, t, H.ol[q].n_exp);
+	};
+	const float log_na = logf(args->salt);
+	uint64_t c0 = 0;
+	kept_total = place_total = 0;
+	bool cells_live = cap > 0, place_live = place_cap > 0;                         // still within the caller's arrays
+	while(c0 < n_cells){
+		// ---- a batch: cells c0 .. c1 - 1; it closes before the cell that would take it past POOL_DIMER_END3_BATCH_DUPLEXES duplexes
+		const uint32_t d0 = before(c0);
+		uint64_t c1 = c0 + 1, above = n_cells + 1;
+		while(above - c1 > 1){
+			const uint64_t mid = c1 + (above - c1)/2;
+			if(before(mid) - d0 <= POOL_DIMER_END3_BATCH_DUPLEXES) c1 = mid; else above = mid;
+		}
+		const uint32_t nd = before(c1) - d0, nc = (uint32_t)(c1 - c0);
+		const size_t n_keep = (size_t)std::max(nc, POOL_DIMER_END3_BATCH_JOBS) + 1;
+		if((rc = ctx->pde3_cnt.ensure((size_t)nd + 1)) != PCR_OK) return rc;
+		if((rc = ctx->pde3_off.ensure((size_t)nd + 1)) != PCR_OK) return rc;
+		if(!dense && (rc = ctx->pde3_rec.ensure(nc)) != PCR_OK) return rc;
+		pcr_pool_dimer_end3 *const rec = dense ? O.dense + c0 : ctx->pde3_rec.p;     // the batch's cell records
+		if((rc = ctx->pde3_keep.ensure(n_keep)) != PCR_OK) return rc;
+		if((rc = ctx->pde3_koff.ensure(n_keep)) != PCR_OK) return rc;
+		// ---- count, scan
+		const unsigned grid_d = (unsigned)(((uint64_t)nd*32u + POOL_THREADS - 1)/POOL_THREADS), grid_c = (nc + POOL_THREADS - 1)/POOL_THREADS;
+		hipLaunchKernelGGL(k_dimer_end3_scan<false>, dim3(grid_d), dim3(POOL_THREADS), 0, ctx->stream, P, (uint32_t)c0, d0, nd, min_run, min_extension,
+			ctx->pde3_cnt.p, (const uint32_t *)nullptr, (uint2 *)nullptr);
+		HIP_TRY(hipGetLastError());
+		uint32_t n_jobs = 0;
+		if((rc = end3_scan(ctx, ctx->pde3_cnt.p, ctx->pde3_off.p, nd, &n_jobs)) != PCR_OK) return rc;
+		hipLaunchKernelGGL(k_dimer_end3_cells, dim3(grid_c), dim3(POOL_THREADS), 0, ctx->stream, P, (uint32_t)c0, nc, d0, (const uint32_t *)ctx->pde3_off.p, rec);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(ctx->stream));
+		// ---- fill and melt, while anything still needs the energies
+		const bool melt = n_jobs && (!keep_all || cells_live || place_live || dense);
+		if(melt){
+			if(!tables){
+				if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
+				if(!ctx->pde3_attr_set){
+					HIP_TRY(hipFuncSetAttribute((const void *)k_dimer_end3_melt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PDIM_LDS));
+					ctx->pde3_attr_set = true;
+				}
+				tables = true;
+			}
+			if((rc = ctx->pde3_jobs.ensure(n_jobs)) != PCR_OK) return rc;
+			if((rc = ctx->pde3_res.ensure(std::min(n_jobs, POOL_DIMER_END3_BATCH_JOBS))) != PCR_OK) return rc;
+			hipLaunchKernelGGL(k_dimer_end3_scan<true>, dim3(grid_d), dim3(POOL_THREADS), 0, ctx->stream, P, (uint32_t)c0, d0, nd, min_run, min_extension,
+				(uint32_t *)nullptr, (const uint32_t *)ctx->pde3_off.p, ctx->pde3_jobs.p);
+			HIP_TRY(hipGetLastError());
+			for(uint32_t a = 0;a < n_jobs;a += POOL_DIMER_END3_BATCH_JOBS){
+				const uint32_t nj = std::min(POOL_DIMER_END3_BATCH_JOBS, n_jobs - a);
+				// at most one block per CU (a block takes most of a CU's LDS), the waves striding over the jobs
+				const unsigned grid_j = std::max(1u, std::min<unsigned>((nj + PDIM_WAVES - 1)/PDIM_WAVES, (unsigned)ctx->n_cu));
+				hipLaunchKernelGGL(k_dimer_end3_melt, dim3(grid_j), dim3(PDIM_THREADS), PDIM_LDS, ctx->stream, P, (uint32_t)c0, (const uint2 *)(ctx->pde3_jobs.p + a), nj,
+					(const int *)ctx->th_dg.p, log_na, ctx->pde3_res.p);
+				HIP_TRY(hipGetLastError());
+				hipLaunchKernelGGL(k_dimer_end3_merge, dim3(grid_c), dim3(POOL_THREADS), 0, ctx->stream, P, (uint32_t)c0, nc, d0, (const uint32_t *)ctx->pde3_off.p,
+					(const uint2 *)ctx->pde3_jobs.p, a, nj, (const float4 *)ctx->pde3_res.p, rec, ctx->pdim_flag.p);
+				HIP_TRY(hipGetLastError());
+				uint32_t pk = nj;
+				if(dense) continue;                                                     // (no placement is listed or counted)
+				if(!keep_all || place_live){
+					// ---- the launch's kept placements, in job order
+					const unsigned grid_p = (nj + POOL_THREADS - 1)/POOL_THREADS;
+					hipLaunchKernelGGL(k_dimer_end3_place_keep, dim3(grid_p), dim3(POOL_THREADS), 0, ctx->stream, (const float4 *)ctx->pde3_res.p, nj, dg_max, ctx->pde3_keep.p);
+					HIP_TRY(hipGetLastError());
+					if((rc = end3_scan(ctx, ctx->pde3_keep.p, ctx->pde3_koff.p, nj, &pk)) != PCR_OK) return rc;
+					HIP_TRY(hipStreamSynchronize(ctx->stream));
+					if(place_live && place_total + pk > place_cap) place_live = false;   // (past place_cap the call only counts)
+					if(place_live && pk){
+						if((rc = ctx->pde3_place.ensure(pk)) != PCR_OK) return rc;
+						hipLaunchKernelGGL(k_dimer_end3_place_write, dim3(grid_p), dim3(POOL_THREADS), 0, ctx->stream, P, (uint32_t)c0, (const uint2 *)(ctx->pde3_jobs.p + a),
+							(const float4 *)ctx->pde3_res.p, (const uint32_t *)ctx->pde3_keep.p, (const uint32_t *)ctx->pde3_koff.p, nj, ctx->pde3_place.p);
+						HIP_TRY(hipGetLastError());
+						HIP_TRY(hipMemcpyAsync(place_out + place_total, ctx->pde3_place.p, (size_t)pk*sizeof(pcr_dimer_placement), hipMemcpyDeviceToHost, ctx->stream));
+						HIP_TRY(hipStreamSynchronize(ctx->stream));                     // the next launch reuses the scratch
+					}
+				}
+				place_total += pk;
+			}
+		}
+		else place_total += n_jobs;                                                 // (dg_max = +INFINITY keeps every qualifying placement)
+		if(dense){
+			uint32_t bad = 0;
+			HIP_TRY(hipMemcpyAsync(&bad, ctx->pdim_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+			HIP_TRY(hipStreamSynchronize(ctx->stream));                               // the next batch reuses the scratch
+			if(bad & 1u){ g_err = std::string(who) + ": internal trace-back error"; return PCR_ERR_RANGE; }
+			c0 = c1;
+			continue;
+		}
+		// ---- the kept cells, in cell order
+		hipLaunchKernelGGL(k_dimer_end3_cell_keep, dim3(grid_c), dim3(POOL_THREADS), 0, ctx->stream, (const pcr_pool_dimer_end3 *)rec, nc, keep_all ? 1 : 0, dg_max,
+			ctx->pde3_keep.p);
+		HIP_TRY(hipGetLastError());
+		uint32_t kept = 0, bad = 0;
+		if((rc = end3_scan(ctx, ctx->pde3_keep.p, ctx->pde3_koff.p, nc, &kept)) != PCR_OK) return rc;
+		HIP_TRY(hipMemcpyAsync(&bad, ctx->pdim_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(hipStreamSynchronize(ctx->stream));
+		if(bad & 1u){ g_err = std::string(who) + ": internal trace-back error"; return PCR_ERR_RANGE; }
+		if(cells_live && kept_total + kept > cap) cells_live = false;               // (past cap the call only counts)
+		if(cells_live && kept){
+			if((rc = ctx->pde3_out.ensure(kept)) != PCR_OK) return rc;
+			hipLaunchKernelGGL(k_dimer_end3_cell_compact, dim3(grid_c), dim3(POOL_THREADS), 0, ctx->stream, (const pcr_pool_dimer_end3 *)rec,
+				(const uint32_t *)ctx->pde3_keep.p, (const uint32_t *)ctx->pde3_koff.p, nc, ctx->pde3_out.p);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipMemcpyAsync(out + kept_total, ctx->pde3_out.p, (size_t)kept*sizeof(pcr_pool_dimer_end3), hipMemcpyDeviceToHost, ctx->stream));
+			HIP_TRY(hipStreamSynchronize(ctx->stream));                               // the next batch reuses the scratch
+		}
+		kept_total += kept;
+		c0 = c1;
+	}
+	if(dense) place_total = 0;
+	return PCR_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -277,121 +428,11 @@ int64_t pcr_pool_dimers_end3(pcr_ctx *ctx, const pcr_pair *pool, uint32_t n_pool
 	FLUSH(ctx);
 	HIP_TRY(hipSetDevice(ctx->device));
 	if(n_place) *n_place = 0;
-	const uint32_t n = H.n;
-	if(n == 0) return 0;
-	const uint64_t n_cells = (uint64_t)n*n;
-	const bool keep_all = dg_max == INFINITY;
-	// ---- the tables
-	int rc;
-	std::vector<uint8_t> blob;
-	DimerPlan P;
-	if((rc = pdim_upload_plan(ctx, H, blob, P)) != PCR_OK) return rc;
-	if((rc = ctx->pdim_flag.ensure(1)) != PCR_OK) return rc;
-	HIP_TRY(hipMemsetAsync(ctx->pdim_flag.p, 0, sizeof(uint32_t), ctx->stream));
-	bool tables = false;                                                          // the dG table and the kernel's LDS size: only once something is melted
-	// duplexes before cell c (c = n_cells: all of them)
-	auto before = [&](uint64_t c) -> uint32_t {
-		if(c >= n_cells) return H.row[n];
-		const uint32_t q = (uint32_t)(c/n), t = (uint32_t)(c % n);
-		return pdim_before(H.row.data(), H.pref.data(), q, t, H.ol[q].n_exp);
-	};
-	const float log_na = logf(args->salt);
-	uint64_t kept_total = 0, place_total = 0, c0 = 0;
-	bool cells_live = cap > 0, place_live = place_cap > 0;                         // still within the caller's arrays
-	while(c0 < n_cells){
-		// ---- a batch: cells c0 .. c1 - 1; it closes before the cell that would take it past POOL_DIMER_END3_BATCH_DUPLEXES duplexes
-		const uint32_t d0 = before(c0);
-		uint64_t c1 = c0 + 1, above = n_cells + 1;
-		while(above - c1 > 1){
-			const uint64_t mid = c1 + (above - c1)/2;
-			if(before(mid) - d0 <= POOL_DIMER_END3_BATCH_DUPLEXES) c1 = mid; else above = mid;
-		}
-		const uint32_t nd = before(c1) - d0, nc = (uint32_t)(c1 - c0);
-		const size_t n_keep = (size_t)std::max(nc, POOL_DIMER_END3_BATCH_JOBS) + 1;
-		if((rc = ctx->pde3_cnt.ensure((size_t)nd + 1)) != PCR_OK) return rc;
-		if((rc = ctx->pde3_off.ensure((size_t)nd + 1)) != PCR_OK) return rc;
-		if((rc = ctx->pde3_rec.ensure(nc)) != PCR_OK) return rc;
-		if((rc = ctx->pde3_keep.ensure(n_keep)) != PCR_OK) return rc;
-		if((rc = ctx->pde3_koff.ensure(n_keep)) != PCR_OK) return rc;
-		// ---- count, scan
-		const unsigned grid_d = (unsigned)(((uint64_t)nd*32u + POOL_THREADS - 1)/POOL_THREADS), grid_c = (nc + POOL_THREADS - 1)/POOL_THREADS;
-		hipLaunchKernelGGL(k_dimer_end3_scan<false>, dim3(grid_d), dim3(POOL_THREADS), 0, ctx->stream, P, (uint32_t)c0, d0, nd, min_run, min_extension,
-			ctx->pde3_cnt.p, (const uint32_t *)nullptr, (uint2 *)nullptr);
-		HIP_TRY(hipGetLastError());
-		uint32_t n_jobs = 0;
-		if((rc = end3_scan(ctx, ctx->pde3_cnt.p, ctx->pde3_off.p, nd, &n_jobs)) != PCR_OK) return rc;
-		hipLaunchKernelGGL(k_dimer_end3_cells, dim3(grid_c), dim3(POOL_THREADS), 0, ctx->stream, P, (uint32_t)c0, nc, d0, (const uint32_t *)ctx->pde3_off.p, ctx->pde3_rec.p);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(ctx->stream));
-		// ---- fill and melt, while anything still needs the energies
-		const bool melt = n_jobs && (!keep_all || cells_live || place_live);
-		if(melt){
-			if(!tables){
-				if((rc = ensure_dg_table(ctx, args->salt)) != PCR_OK) return rc;
-				if(!ctx->pde3_attr_set){
-					HIP_TRY(hipFuncSetAttribute((const void *)k_dimer_end3_melt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PDIM_LDS));
-					ctx->pde3_attr_set = true;
-				}
-				tables = true;
-			}
-			if((rc = ctx->pde3_jobs.ensure(n_jobs)) != PCR_OK) return rc;
-			if((rc = ctx->pde3_res.ensure(std::min(n_jobs, POOL_DIMER_END3_BATCH_JOBS))) != PCR_OK) return rc;
-			hipLaunchKernelGGL(k_dimer_end3_scan<true>, dim3(grid_d), dim3(POOL_THREADS), 0, ctx->stream, P, (uint32_t)c0, d0, nd, min_run, min_extension,
-				(uint32_t *)nullptr, (const uint32_t *)ctx->pde3_off.p, ctx->pde3_jobs.p);
-			HIP_TRY(hipGetLastError());
-			for(uint32_t a = 0;a < n_jobs;a += POOL_DIMER_END3_BATCH_JOBS){
-				const uint32_t nj = std::min(POOL_DIMER_END3_BATCH_JOBS, n_jobs - a);
-				// at most one block per CU (a block takes most of a CU's LDS), the waves striding over the jobs
-				const unsigned grid_j = std::max(1u, std::min<unsigned>((nj + PDIM_WAVES - 1)/PDIM_WAVES, (unsigned)ctx->n_cu));
-				hipLaunchKernelGGL(k_dimer_end3_melt, dim3(grid_j), dim3(PDIM_THREADS), PDIM_LDS, ctx->stream, P, (uint32_t)c0, (const uint2 *)(ctx->pde3_jobs.p + a), nj,
-					(const int *)ctx->th_dg.p, log_na, ctx->pde3_res.p);
-				HIP_TRY(hipGetLastError());
-				hipLaunchKernelGGL(k_dimer_end3_merge, dim3(grid_c), dim3(POOL_THREADS), 0, ctx->stream, P, (uint32_t)c0, nc, d0, (const uint32_t *)ctx->pde3_off.p,
-					(const uint2 *)ctx->pde3_jobs.p, a, nj, (const float4 *)ctx->pde3_res.p, ctx->pde3_rec.p, ctx->pdim_flag.p);
-				HIP_TRY(hipGetLastError());
-				uint32_t pk = nj;
-				if(!keep_all || place_live){
-					// ---- the launch's kept placements, in job order
-					const unsigned grid_p = (nj + POOL_THREADS - 1)/POOL_THREADS;
-					hipLaunchKernelGGL(k_dimer_end3_place_keep, dim3(grid_p), dim3(POOL_THREADS), 0, ctx->stream, (const float4 *)ctx->pde3_res.p, nj, dg_max, ctx->pde3_keep.p);
-					HIP_TRY(hipGetLastError());
-					if((rc = end3_scan(ctx, ctx->pde3_keep.p, ctx->pde3_koff.p, nj, &pk)) != PCR_OK) return rc;
-					HIP_TRY(hipStreamSynchronize(ctx->stream));
-					if(place_live && place_total + pk > place_cap) place_live = false;   // (past place_cap the call only counts)
-					if(place_live && pk){
-						if((rc = ctx->pde3_place.ensure(pk)) != PCR_OK) return rc;
-						hipLaunchKernelGGL(k_dimer_end3_place_write, dim3(grid_p), dim3(POOL_THREADS), 0, ctx->stream, P, (uint32_t)c0, (const uint2 *)(ctx->pde3_jobs.p + a),
-							(const float4 *)ctx->pde3_res.p, (const uint32_t *)ctx->pde3_keep.p, (const uint32_t *)ctx->pde3_koff.p, nj, ctx->pde3_place.p);
-						HIP_TRY(hipGetLastError());
-						HIP_TRY(hipMemcpyAsync(place_out + place_total, ctx->pde3_place.p, (size_t)pk*sizeof(pcr_dimer_placement), hipMemcpyDeviceToHost, ctx->stream));
-						HIP_TRY(hipStreamSynchronize(ctx->stream));                     // the next launch reuses the scratch
-					}
-				}
-				place_total += pk;
-			}
-		}
-		else place_total += n_jobs;                                                 // (dg_max = +INFINITY keeps every qualifying placement)
-		// ---- the kept cells, in cell order
-		hipLaunchKernelGGL(k_dimer_end3_cell_keep, dim3(grid_c), dim3(POOL_THREADS), 0, ctx->stream, (const pcr_pool_dimer_end3 *)ctx->pde3_rec.p, nc, keep_all ? 1 : 0, dg_max,
-			ctx->pde3_keep.p);
-		HIP_TRY(hipGetLastError());
-		uint32_t kept = 0, bad = 0;
-		if((rc = end3_scan(ctx, ctx->pde3_keep.p, ctx->pde3_koff.p, nc, &kept)) != PCR_OK) return rc;
-		HIP_TRY(hipMemcpyAsync(&bad, ctx->pdim_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-		HIP_TRY(hipStreamSynchronize(ctx->stream));
-		if(bad & 1u){ g_err = "pcr_pool_dimers_end3: internal trace-back error"; return PCR_ERR_RANGE; }
-		if(cells_live && kept_total + kept > cap) cells_live = false;               // (past cap the call only counts)
-		if(cells_live && kept){
-			if((rc = ctx->pde3_out.ensure(kept)) != PCR_OK) return rc;
-			hipLaunchKernelGGL(k_dimer_end3_cell_compact, dim3(grid_c), dim3(POOL_THREADS), 0, ctx->stream, (const pcr_pool_dimer_end3 *)ctx->pde3_rec.p,
-				(const uint32_t *)ctx->pde3_keep.p, (const uint32_t *)ctx->pde3_koff.p, nc, ctx->pde3_out.p);
-			HIP_TRY(hipGetLastError());
-			HIP_TRY(hipMemcpyAsync(out + kept_total, ctx->pde3_out.p, (size_t)kept*sizeof(pcr_pool_dimer_end3), hipMemcpyDeviceToHost, ctx->stream));
-			HIP_TRY(hipStreamSynchronize(ctx->stream));                               // the next batch reuses the scratch
-		}
-		kept_total += kept;
-		c0 = c1;
-	}
+	if(H.n == 0) return 0;
+	End3Out O;
+	O.out = out; O.cap = cap; O.place_out = place_out; O.place_cap = place_cap;
+	uint64_t kept_total = 0, place_total = 0;
+	{ const int brc = end3_batches("pcr_pool_dimers_end3", ctx, H, args, min_run, min_extension, dg_max, O, kept_total, place_total); if(brc != PCR_OK) return brc; }
 	if(n_place) *n_place = place_total;
 	return (int64_t)kept_total;
 }
